@@ -4,7 +4,14 @@ second and achieved HBM GB/s on the bidomain_3d nrefs=6 system
 (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--nrefs 6] [--dim 3]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (multi-GPU)
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the
+last step when --dump-outputs is given, and prints the result line.  --full
+adds every other leg (the apply-loop re-timing, the per-class breakdown, the
+PCG solves, the profile comparison, the CPU baseline, N > 1: the one-GPU
+check); their fields of the result line are null without it.
 
 A step = one preconditioner application z = B r (one V-cycle from x0 = 0) on
 a resident seeded r (uniform(-1,1), seed 1234) -- the unit of work of the
@@ -14,10 +21,10 @@ events around the two dominant kernels of every step (level-0 residual SpMV
 and the fused prolongation + post-smoothing kernel), bracketed by barrier +
 synchronize; `roofline` is the one with the larger time.  value = K / max-over-ranks wall time
 (applies of the whole problem per second).
-N = 1: the whole hierarchy on one GPU (BSR2 layout, hipGraph replay also
-reported).  N > 1: the same problem row-partitioned over N GPUs (one process
-per GPU, RCCL halo exchange over xGMI; strong scaling).
-The cpu_baseline leg (rank 0, N = 1) times the oracle's C restatement
+N = 1: the whole hierarchy on one GPU (BSR2 layout; --full also reports the
+apply loop between two stream events).  N > 1: the same problem row-partitioned
+over N GPUs (one process per GPU, RCCL halo exchange over xGMI; strong scaling).
+The cpu_baseline leg (--full, rank 0, N = 1) times the oracle's C restatement
 (oracle/vcycle_ref.c) of the same cycle on the same hierarchy on the host.
 """
 import argparse
@@ -33,6 +40,8 @@ sys.path.insert(0, ROOT)
 
 METRIC = "V-cycle applies/sec + HBM GB/s, bidomain_3d nrefs=6 @1/2/4/8 GPU"
 HBM_PEAK_GBPS = 8000.0        # MI355X HBM3E spec (MI355X_MICROARCH.md); 6290 measured copy
+DUMP_MAX = 1 << 22            # --dump-outputs: entries written over all ranks (32 MB of f64)
+DUMP_SEED = 4321              # seed of the sample's indices when the output is larger
 CLASS_NAMES = ['L0_resid', 'L0_smooth_spmv', 'L0_smoother', 'L0_restrict', 'L0_prolong',
                'coarse_levels', 'coarsest_dense', 'misc', 'comm']
 
@@ -93,6 +102,22 @@ def cpu_model():
     except OSError:
         pass
     return None
+
+
+def dump_outputs(dirname, z, rank, world):
+    """--dump-outputs: z = B r as the last timed step left it (this rank's
+    slice for N > 1), float64, as DIR/z.npy (N > 1: DIR/z_rank<k>.npy).  Above
+    DUMP_MAX / N entries: its values at sorted indices drawn once from
+    default_rng(DUMP_SEED + rank), the same for every run of one size."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    cap = max(1, DUMP_MAX // world)
+    if z.numel() > cap:
+        idx = np.sort(np.random.default_rng(DUMP_SEED + rank).integers(0, z.numel(), size=cap))
+        z = z[torch.as_tensor(idx).to(z.device)]
+    name = 'z.npy' if world == 1 else 'z_rank%d.npy' % rank
+    np.save(os.path.join(dirname, name), z.cpu().numpy().astype(np.float64, copy=False))
+    log('rank %d: wrote %d entries of z to %s' % (rank, z.numel(), os.path.join(dirname, name)))
 
 
 def one_gpu_check(args, M, B, r, z, r_full, sysm, prof, dev, rdev, gloo, rank, world, dist_res, barrier, allsum):
@@ -198,7 +223,20 @@ def main():
                          'in each rank\'s HBM')
     ap.add_argument('--compare-host-setup', action='store_true',
                     help='also time the host setup of the same hierarchy (N = 1)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run the other legs: apply-loop re-timing, per-class '
+                         'breakdown, PCG, profile comparison, CPU baseline, N > 1: eager re-timing and the one-GPU '
+                         'check (each still switched by its own option).  Off: only what the headline figure needs')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write z = B r of the last timed step as DIR/z.npy (N > 1: '
+                         'DIR/z_rank<k>.npy, this rank\'s slice), float64; a vector above %d entries is '
+                         'sampled at fixed seeded indices (seed %d)' % (DUMP_MAX, DUMP_SEED))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if not args.full:       # a plain run: the legs below the timed steps stay off
+        args.no_breakdown = True
+        args.pcg = args.cpu_sample = args.compare_profiles = args.check_1gpu = 0
     prof = dict(smoother={'jacobi': 3, 'poly': 12, 'sgs': 11, 'gs': 10}[args.smoother], coarse_scaling=args.scaling,
                 cycle_type={'V': 1, 'W': 2}[args.cycle], poly_degree=args.poly_degree,
                 Schwarz_type={'sgs': 7, 'gs': 7}.get(args.smoother, 4))
@@ -352,7 +390,9 @@ def main():
     ms_per_step = 1e3 * wall / args.steps
     value = args.steps / wall
     apply_bytes = allsum(B.apply_bytes)
-    if use_graph:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, z, rank, world)
+    if use_graph and args.full:
         # the eager path on the same handles, for the record, and its kernel
         # events (graph replays carry none) for the roofline
         barrier()
@@ -362,11 +402,13 @@ def main():
         wall_e = allmax(time.perf_counter() - t0)
         graph_info.update(ms_per_step_graph=round(ms_per_step, 4),
                           ms_per_step_eager=round(1e3 * wall_e / args.steps, 4))
+    elif use_graph:
+        graph_info.update(ms_per_step_graph=round(ms_per_step, 4), ms_per_step_eager=None)
     elif graph_info is not None:
         graph_info.update(ms_per_step_graph=None, ms_per_step_eager=round(ms_per_step, 4))
 
     graph_ms = None
-    if world == 1:                          # hipGraph replay of the same work
+    if world == 1 and args.full:            # hipGraph replay of the same work
         barrier()
         g0 = torch.cuda.Event(enable_timing=True)
         g1 = torch.cuda.Event(enable_timing=True)
@@ -600,6 +642,7 @@ def main():
         'n_gpus': world,
         'steps': args.steps,
         'warmup': args.warmup,
+        'full': args.full,
         'ms_per_step': round(ms_per_step, 4),
         'higher_is_better': True,
         'scaling': 'strong',

@@ -3,7 +3,7 @@
 #   [BENCH_ARGS="--dim 2"] bash scripts/ab_env.sh TAG "CFG1" "CFG2" ...   (CFG = space-separated VAR=value, or X=0 for the default)
 TAG=$1; shift
 mkdir -p gpurun_out/$TAG
-L="--steps 30 --warmup 3 --cpu-sample 0 --pcg 0 --compare-profiles 0 ${BENCH_ARGS:-}"
+L="--full --steps 30 --warmup 3 --cpu-sample 0 --pcg 0 --compare-profiles 0 ${BENCH_ARGS:-}"
 for cfg in "$@"; do
   env $cfg timeout -k 10 200 python -u bench.py $L > gpurun_out/$TAG/run.log 2>&1 || exit 1
   python3 -c "

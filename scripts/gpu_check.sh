@@ -4,7 +4,7 @@
 # STEPS (default all): any of smoke tests bench trace pmc dist, comma-separated.
 #   smoke  __graft_entry__.smoke()
 #   tests  pytest -m gpu
-#   bench  python bench.py (N = 1 defaults) -> gpurun_out/TAG/bench.json
+#   bench  python bench.py --full (N = 1 defaults, every leg) -> TAG/bench.json
 #   trace  rocprofv3 --kernel-trace --stats of a bench run -> TAG/trace/*_kernel_stats.csv
 #   pmc    rocprofv3 --pmc FETCH_SIZE, then --pmc WRITE_SIZE (separate passes) ->
 #          scripts/traffic.py -> profiles/traffic.json (tagged with device.hip's sha256)
@@ -32,7 +32,7 @@ LIGHT="--steps 10 --warmup 2 --cpu-sample 0 --no-breakdown --pcg 0 --compare-pro
 want smoke && step smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()"
 want tests && step tests 1100 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread
 if want bench; then
-  step bench 600 python -u bench.py && tail -1 $OUT/bench.log > $OUT/bench.json
+  step bench 600 python -u bench.py --full && tail -1 $OUT/bench.log > $OUT/bench.json
 fi
 if want trace; then
   cd /tmp && step trace 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench \
