@@ -57,7 +57,19 @@ enum {                                                          /* smoother   */
    * poly_degree in W A on [relaxation/poly_ratio, relaxation], W the
    * JACOBI_RHO (block) smoother, applied as poly_degree weighted steps
    * x += w_k W (b - A x); pre steps k = 1..m, post m..1 (default profile) */
-  MAMG_SMOOTHER_POLY = 12
+  MAMG_SMOOTHER_POLY = 12,
+  /* HAZmath's point-wise GS / SGS (the smoother of the reference's plain AMG,
+   * AMGhaz) in a multicolour order: per level the rows of the scalar A_l are
+   * coloured on its off-diagonal pattern and swept colour by colour,
+   * x_i += (b_i - sum_j a_ij x_j) / a_ii (forward / forward+backward);
+   * relaxation does not enter.  CSR layout, num_functions 1 or 2 (2: nodal
+   * aggregation, point sweeps); the setup resolves node_block_smoother to 0
+   * and builds the hierarchy of SMOOTHER_JACOBI_RHO (winv is exported, the
+   * sweeps do not use it).  Level-0 seeds (Schwarz_levels >= 1 with idofs),
+   * a non-symmetric pattern or more than 64 colours: MAMG_ERR_UNSUPPORTED; a
+   * missing or non-positive diagonal entry: MAMG_ERR_SETUP.  Single GPU. */
+  MAMG_SMOOTHER_GS_POINT = 13,
+  MAMG_SMOOTHER_SGS_POINT = 14
 };
 enum {                                                   /* aggregation_type  */
   MAMG_VMB = 1, MAMG_MIS = 2, MAMG_MWM = 3, MAMG_HEC = 4, MAMG_HEM = 5
@@ -394,8 +406,9 @@ void mamg_destroy(mamg_handle* h);
 
 int64_t mamg_nrows(const mamg_handle* h);
 int mamg_num_levels(const mamg_handle* h);
-/* Device layout chosen at upload: 0 = CSR (general), 1 = BSR2 (nodal
- * hierarchy with num_functions == 2 and node-block smoothers). */
+/* Device layout chosen at upload: 0 = CSR (general; always with the
+ * point-wise SMOOTHER_GS_POINT / SGS_POINT), 1 = BSR2 (nodal hierarchy with
+ * num_functions == 2 and node-block smoothers). */
 int mamg_device_layout(const mamg_handle* h);
 /* Storage of level l's operator on the device (BSR2 layout), bit flags:
  * MAMG_FMT_SELL (sliced-ELL, one lane per node row), MAMG_FMT_SYM (3 doubles
@@ -410,7 +423,8 @@ int mamg_device_layout(const mamg_handle* h);
 enum { MAMG_FMT_SELL = 1, MAMG_FMT_SYM = 2, MAMG_FMT_POST_FUSED = 4, MAMG_FMT_POST_K = 8,
        MAMG_FMT_POST_SELL = 16, MAMG_FMT_HALF = 32, MAMG_FMT_BANDS = 64,
        MAMG_FMT_PATCHES = 128,  /* smoother: multiplicative node-patch Schwarz (SCHWARZ_PATCHES) */
-       MAMG_FMT_GS = 256,       /* smoother: multicolour node-block GS / SGS sweeps */
+       MAMG_FMT_GS = 256,       /* smoother: multicolour GS / SGS sweeps (node-block: BSR2 layout;
+                                   point-wise, SMOOTHER_GS_POINT / SGS_POINT: CSR layout) */
        MAMG_FMT_RINGS = 512,    /* smoother: multiplicative seed-ring Schwarz + GS on the rest (SCHWARZ_RINGS) */
        MAMG_FMT_R_BANDS = 1024,    /* restriction rows walked plane band by plane band per XCD */
        MAMG_FMT_K_COL16 = 2048 };  /* K's columns as 16-bit offsets from a per-slice base */
@@ -422,7 +436,12 @@ int mamg_handle_params(const mamg_handle* h, mamg_params* out);
  * and the index kept (*kept = -1: no selection ran). */
 int mamg_kregion_info(const mamg_handle* h, double* ms, int cap, int* n, int* kept);
 /* Algorithmic HBM bytes of one apply (SURVEY 8d formula) and of its dominant
- * kernel class; see DESIGN.md section 4. */
+ * kernel class; see DESIGN.md section 4.  A point-wise GS colour step of
+ * `rows` rows holding `nnz` entries counts 12 nnz (values, columns) +
+ * 8 (rows + 1) (pointers) + 4 rows (perm) + 8 rows (1/a_ii) + 8 rows (b) +
+ * 16 rows (own x read, written) + 8 n / ncolours (the gathered x, every entry
+ * once per sweep); a small level's one-launch smoothing call counts the sum
+ * over its colour steps. */
 int mamg_apply_bytes(const mamg_handle* h, double* total_bytes);
 
 /* z = B r : one preconditioner application (`maxit` cycles from x0 = 0).

@@ -164,6 +164,123 @@ __global__ __launch_bounds__(256) void csr_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Point-wise multicolour Gauss-Seidel on the CSR layout (SMOOTHER_GS_POINT /
+// SGS_POINT): the smoother of the reference's plain AMG (AMGhaz,
+// src/utils.py:40, SGS of src/amg_parameters.py:72) in a parallel order.  The
+// rows of the scalar A_l are coloured on its off-diagonal pattern
+// (jp_round_kernel, as the node-block GS); G = A_l with its rows permuted
+// colour by colour (build_gs_csr), so one colour is one contiguous row range
+// [r0, r1):   x_I <- x_I + (b_I - sum_j a_Ij x_j) / a_II,   I = perm[i],
+// in place (no row of a colour reads an x another row of that colour writes).
+// dinv[i] = 1 / a_II in permuted order.  csr_gs_row is csr_kernel's lane-group
+// row loop; every lane of the group returns the row's sum.
+// ---------------------------------------------------------------------------
+template <int VL>
+__device__ __forceinline__ double csr_gs_row(bool on, int64_t i, int lane, const int64_t* __restrict__ ptr,
+                                             const int32_t* __restrict__ col, const double* __restrict__ val,
+                                             const double* x) {
+  double s0 = 0.0, s1 = 0.0;
+  if (on) {
+    const int64_t p0 = ptr[i], p1 = ptr[i + 1];
+    int64_t k = p0 + lane;
+    for (; k + VL < p1; k += 2 * VL) {
+      const int32_t c0 = col[k], c1 = col[k + VL];
+      const double v0 = val[k], v1 = val[k + VL];
+      s0 += v0 * x[c0];
+      s1 += v1 * x[c1];
+    }
+    if (k < p1) s0 += val[k] * x[col[k]];
+  }
+  double s = s0 + s1;
+#pragma unroll
+  for (int off = VL / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, VL);
+  return s;
+}
+
+// one colour: the permuted rows [r0, r1), one launch
+template <int VL>
+__global__ __launch_bounds__(256) void csr_gs_kernel(
+    int64_t r0, int64_t r1, const int32_t* __restrict__ perm, const int64_t* __restrict__ ptr,
+    const int32_t* __restrict__ col, const double* __restrict__ val, const double* __restrict__ dinv,
+    double* x, const double* __restrict__ b) {
+  const int lane = threadIdx.x & (VL - 1);
+  const int64_t i = r0 + ((int64_t)blockIdx.x * 256 + threadIdx.x) / VL;
+  const bool on = i < r1;
+  const double s = csr_gs_row<VL>(on, i, lane, ptr, col, val, x);
+  if (on && lane == 0) {
+    const int64_t I = perm[i];
+    x[I] = x[I] + dinv[i] * (b[I] - s);
+  }
+}
+
+// A whole smoothing call of a small level (n <= CSR_GS_SMALL_ROWS rows) in
+// one launch of one workgroup: nu x (sweep d0, then sweep d1), a sweep being
+// every colour in turn (d > 0 ascending, d < 0 descending, 0: no sweep).  x
+// lives in LDS (xs[n]; from zero if `zero`, else read from global memory), b
+// and the permuted operator are read from global memory, a workgroup barrier
+// separates the colours, x is written back coalesced at the end.  Every loop
+// is bounded by nu, the colour count and the row count.
+constexpr int CSR_GS_SMALL_THREADS = 1024;
+template <int VL>
+__global__ __launch_bounds__(CSR_GS_SMALL_THREADS) void csr_gs_small_kernel(
+    int64_t n, int ncol, const int64_t* __restrict__ cs, const int32_t* __restrict__ perm,
+    const int64_t* __restrict__ ptr, const int32_t* __restrict__ col, const double* __restrict__ val,
+    const double* __restrict__ dinv, double* x, const double* __restrict__ b, int zero, int nu, int d0, int d1) {
+  extern __shared__ double csr_gs_xs[];
+  double* xs = csr_gs_xs;
+  const int tid = threadIdx.x, lane = tid & (VL - 1);
+  constexpr int RPP = CSR_GS_SMALL_THREADS / VL;   // rows per pass
+  for (int64_t i = tid; i < n; i += CSR_GS_SMALL_THREADS) xs[i] = zero ? 0.0 : x[i];
+  __syncthreads();
+  for (int rep = 0; rep < nu; ++rep)
+    for (int leg = 0; leg < 2; ++leg) {
+      const int d = leg ? d1 : d0;
+      if (d == 0) continue;
+      for (int k = 0; k < ncol; ++k) {
+        const int c = d > 0 ? k : ncol - 1 - k;
+        const int64_t r0 = cs[c], r1 = cs[c + 1];
+        for (int64_t base = r0; base < r1; base += RPP) {
+          const int64_t i = base + tid / VL;
+          const bool on = i < r1;
+          const double s = csr_gs_row<VL>(on, i, lane, ptr, col, val, xs);
+          if (on && lane == 0) {
+            const int64_t I = perm[i];
+            xs[I] = xs[I] + dinv[i] * (b[I] - s);
+          }
+        }
+        __syncthreads();
+      }
+    }
+  for (int64_t i = tid; i < n; i += CSR_GS_SMALL_THREADS) x[i] = xs[i];
+}
+
+// permuted row i = row perm[i] of A: its columns and values copied in order,
+// dinv[i] = 1 / a_II; *bad set where the diagonal entry is missing or <= 0
+// (or not a number)
+__global__ __launch_bounds__(256) void csr_gs_fill_kernel(int64_t n, const int32_t* __restrict__ perm,
+                                                          const int64_t* __restrict__ ptr,
+                                                          const int32_t* __restrict__ col,
+                                                          const double* __restrict__ val,
+                                                          const int64_t* __restrict__ gptr, int32_t* __restrict__ gcol,
+                                                          double* __restrict__ gval, double* __restrict__ dinv,
+                                                          int* bad) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t I = perm[i];
+  const int64_t a = ptr[I], e = ptr[I + 1], g = gptr[i];
+  double d = 0.0;
+  for (int64_t k = a; k < e; ++k) {
+    const int32_t c = col[k];
+    const double v = val[k];
+    gcol[g + (k - a)] = c;
+    gval[g + (k - a)] = v;
+    if (c == I) d = v;
+  }
+  if (!(d > 0.0)) { *bad = 1; d = 1.0; }
+  dinv[i] = 1.0 / d;
+}
+
+// ---------------------------------------------------------------------------
 // BSR2 kernels (nodal layout).  Vector element (node I, field f):
 //   node-major:  v[2I + f]          (stride argument 0)
 //   field-major: v[f * stride + I]  (the caller's [u1; u2] order)
@@ -2675,6 +2792,15 @@ struct DLevel {
   int32_t* gperm = nullptr;
   dv4* Gd = nullptr;
   std::vector<int64_t> gcs, gbk;     // colour row starts / block starts (+ end)
+  // point-wise multicolour GS (SMOOTHER_GS_POINT / SGS_POINT, CSR layout):
+  // A_l's rows permuted colour by colour (Gc; gperm = the row of each
+  // permuted row, gcs / gbk as above, unpadded), 1 / a_ii in that order
+  // (gdinv), the colour row starts on the device (gcs_d: the one-launch
+  // smoothing call of a small level, gsmall)
+  DCsr Gc;
+  double* gdinv = nullptr;
+  int64_t* gcs_d = nullptr;
+  bool gsmall = false;
   // level-0 node-patch Schwarz (Schwarz_type PATCHES): A_0 as plain BSR2 in
   // node order (Sptr, Scol, Sval: the patch rows), the patch centres colour by
   // colour (pperm), colour c = patches [pcs[c], pcs[c + 1]), the packed upper
@@ -2707,7 +2833,9 @@ struct DLevel {
 };
 
 enum OpKind { OP_CSR = 0, OP_SCALE = 1, OP_GEMV = 2, OP_AXPY = 3, OP_BSR = 4, OP_BD = 5, OP_POST = 6, OP_ILV = 7,
-              OP_GS = 8, OP_ZERO = 9, OP_DOT2 = 10, OP_CSCALE = 11, OP_PATCH = 12, OP_TAIL = 13, OP_RING = 14 };
+              OP_GS = 8, OP_ZERO = 9, OP_DOT2 = 10, OP_CSCALE = 11, OP_PATCH = 12, OP_TAIL = 13, OP_RING = 14,
+              OP_CGS = 15,     // point-wise GS, one colour of a CSR level (csr_gs_kernel)
+              OP_CGSF = 16 };  // point-wise GS, a small level's whole smoothing call (csr_gs_small_kernel)
 // kernel classes (kernel_ms / class_bytes slots)
 enum Cls {
   C_L0_RESID = 0,   // dominant: r = b - A0 x (once per apply)
@@ -4143,6 +4271,93 @@ int build_gs(HT* h, TmpPool* T, const TBsr& B, const double* W, int level, DLeve
   return rc;
 }
 
+// rows of a level whose whole smoothing call runs as one launch of one
+// workgroup (csr_gs_small_kernel: x in LDS, 8 bytes per row).  Measured at
+// 1024 / 2048 / 4096 / 8192 on the hazmath preset, 2-D n = 128 (DESIGN.md
+// section 2.8).  MAMG_CSR_GS_SMALL (diagnosis build) overrides it, at most
+// 8192 (64 KB of LDS).
+constexpr int64_t CSR_GS_SMALL_ROWS = 4096;
+constexpr int64_t CSR_GS_SMALL_MAX = 8192;
+static_assert(CSR_GS_SMALL_ROWS <= CSR_GS_SMALL_MAX && CSR_GS_SMALL_MAX * 8 <= 64 * 1024, "x of a small level in LDS");
+inline int64_t csr_gs_small_rows() {
+#if MAMG_DIAG
+  if (const char* e = std::getenv("MAMG_CSR_GS_SMALL"))
+    return std::min<int64_t>(std::max<int64_t>(std::atoll(e), 0), CSR_GS_SMALL_MAX);
+#endif
+  return CSR_GS_SMALL_ROWS;
+}
+
+// Point-wise multicolour GS layout of one CSR level from A_l on the device
+// (A: the handle's copy): the rows coloured on A's off-diagonal pattern
+// (gs_colour: the node-block GS's pattern check and Jones-Plassmann rounds on
+// the scalar graph), a stable radix sort of the rows by colour, the
+// colour-contiguous permuted copy (D->Gc), perm, 1 / a_ii per permuted row and
+// the colour ranges.  Shared by dev_upload and dev_from_ghier.
+template <class HT>
+int build_gs_csr(HT* h, TmpPool* T, const DCsr& A, int level, int lanes, DLevel* D, std::string* err) {
+  int rc;
+  const int64_t n = A.n;
+  TBsr B;                        // the scalar graph as gs_colour reads it (ptr, col)
+  B.nr = n; B.nc = A.m; B.nb = A.nnz; B.ptr = A.ptr; B.col = A.col;
+  int8_t* ca = nullptr;
+  int ncol = 0;
+  if ((rc = gs_colour(T, B, level, &ca, &ncol, err))) return rc;
+  int* flag = nullptr;
+  unsigned long long* cnt = nullptr;
+  int32_t *ci = nullptr, *cs = nullptr;
+  int64_t *iota = nullptr, *sorted = nullptr, *gcs_t = nullptr;
+  if ((rc = T->alloc(&flag, 1, err))) return rc;
+  if ((rc = T->alloc(&cnt, 64, err))) return rc;
+  if ((rc = T->alloc(&ci, n, err))) return rc;
+  if ((rc = T->alloc(&cs, n, err))) return rc;
+  if ((rc = T->alloc(&iota, n, err))) return rc;
+  if ((rc = T->alloc(&sorted, n, err))) return rc;
+  if ((rc = T->alloc(&gcs_t, 65, err))) return rc;
+  HIPCHK(dev_memset(flag, 0, sizeof(int)));
+  HIPCHK(dev_memset(cnt, 0, 64 * sizeof(unsigned long long)));
+  colour_count_kernel<<<nblocks(n), 256>>>(n, ca, ci, iota, cnt);
+  HIPCHK(hipGetLastError());
+  if ((rc = dsort_pairs_i32_i64(ci, cs, iota, sorted, n, 6, nullptr, err))) return rc;
+  unsigned long long hc[64];
+  HIPCHK(hipMemcpy(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost));
+  std::vector<int64_t> gcs(65, 0);
+  for (int c = 0; c < 64; ++c) gcs[c + 1] = gcs[c] + (c < ncol ? (int64_t)hc[c] : 0);
+  HIPCHK(hipMemcpy(gcs_t, gcs.data(), 65 * sizeof(int64_t), hipMemcpyHostToDevice));
+  D->gcs.assign(gcs.begin(), gcs.begin() + ncol + 1);
+  if ((rc = dalloc(h, &D->gcs_d, 65, err))) return rc;
+  HIPCHK(dev_copy(D->gcs_d, gcs_t, 65 * sizeof(int64_t)));
+  DCsr& G = D->Gc;
+  G.n = n; G.m = A.m; G.nnz = A.nnz;
+  G.lanes = lanes > 0 ? lanes : pick_lanes(n, A.nnz);
+  if ((rc = dalloc(h, &G.ptr, n + 1, err))) return rc;
+  if ((rc = dalloc(h, &G.col, std::max<int64_t>(A.nnz, 1), err))) return rc;
+  if ((rc = dalloc(h, &G.val, std::max<int64_t>(A.nnz, 1), err))) return rc;
+  if ((rc = dalloc(h, &D->gperm, n, err))) return rc;
+  if ((rc = dalloc(h, &D->gdinv, n, err))) return rc;
+  HIPCHK(dev_memset(G.ptr, 0, sizeof(int64_t)));
+  // unpadded: permuted row = sorted position (pcs = gcs)
+  perm_place_kernel<<<nblocks(n), 256>>>(n, cs, sorted, gcs_t, gcs_t, D->gperm);
+  HIPCHK(hipGetLastError());
+  perm_len_kernel<<<nblocks(n), 256>>>(n, D->gperm, A.ptr, G.ptr);
+  HIPCHK(hipGetLastError());
+  if ((rc = dscan_incl_i64(G.ptr, G.ptr, n + 1, nullptr, err))) return rc;
+  csr_gs_fill_kernel<<<nblocks(n), 256>>>(n, D->gperm, A.ptr, A.col, A.val, G.ptr, G.col, G.val, D->gdinv, flag);
+  HIPCHK(hipGetLastError());
+  int hf = 0;
+  HIPCHK(hipMemcpy(&hf, flag, sizeof(int), hipMemcpyDeviceToHost));
+  if (hf) {
+    *err = "point-wise multicolour GS: a diagonal entry of level " + std::to_string(level) + " is missing or not positive";
+    return MAMG_ERR_SETUP;
+  }
+  D->gbk.assign(ncol + 1, 0);
+  for (int c = 0; c <= ncol; ++c)
+    HIPCHK(hipMemcpy(&D->gbk[c], G.ptr + D->gcs[c], sizeof(int64_t), hipMemcpyDeviceToHost));
+  D->gsmall = n <= csr_gs_small_rows();
+  for (void* q : {(void*)ca, (void*)flag, (void*)cnt, (void*)ci, (void*)cs, (void*)iota, (void*)sorted, (void*)gcs_t})
+    T->release(q);
+  return MAMG_OK;
+}
+
 __global__ __launch_bounds__(256) void split_blocks_kernel(int64_t nbs, const dv4* __restrict__ in, dv2* __restrict__ out) {
   const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (k >= nbs) return;
@@ -4564,12 +4779,95 @@ Op axpy_op(int64_t n, const double* e, double* x) {
 
 void scale_ops(const DeviceHandle* h, int lc, std::vector<Op>* ops);
 
+// algorithmic bytes of one point-wise GS colour step (mamg.h mamg_apply_bytes):
+// values + columns, pointers, perm, 1 / a_ii, b, own x read and written, and
+// the gathered x (every entry once per sweep, spread over the colours)
+double cgs_bytes(const DLevel& L, int c) {
+  const double rows = (double)(L.gcs[c + 1] - L.gcs[c]), ncol = (double)(L.gcs.size() - 1);
+  return 12.0 * (double)(L.gbk[c + 1] - L.gbk[c]) + 8.0 * (rows + 1) + 4.0 * rows + 8.0 * rows + 8.0 * rows +
+         16.0 * rows + 8.0 * (double)L.n / ncol;
+}
+
+// one point-wise GS sweep of a CSR level in place on x, one launch per colour
+// (colours ascending if fwd, else descending)
+void cgs_sweep_ops(const DLevel& L, bool fwd, double* x, const double* b, int cls, std::vector<Op>* ops) {
+  const int nc = (int)L.gcs.size() - 1;
+  for (int k = 0; k < nc; ++k) {
+    const int c = fwd ? k : nc - 1 - k;
+    if (L.gcs[c + 1] <= L.gcs[c]) continue;
+    Op o;
+    o.kind = OP_CGS; o.cls = cls; o.M = &L.Gc; o.perm = L.gperm; o.w = L.gdinv;
+    o.x = x; o.out = x; o.b = b;
+    o.r0 = L.gcs[c]; o.r1 = L.gcs[c + 1]; o.n = o.r1 - o.r0;
+    o.bytes = cgs_bytes(L, c);
+    ops->push_back(o);
+  }
+}
+
+// a whole point-wise GS smoothing call on x: nu x (sweep d0, sweep d1), d > 0
+// forward, d < 0 backward, 0 none; from x = 0 if zero.  A small level
+// (L.gsmall): one launch (csr_gs_small_kernel, which then starts from zero in
+// LDS and never reads x); else an OP_ZERO and one launch per colour.
+void cgs_smooth_ops(const DLevel& L, bool zero, int nu, int d0, int d1, double* x, const double* b, int clsS,
+                    int clsW, std::vector<Op>* ops) {
+  const int nc = (int)L.gcs.size() - 1;
+  if (L.gsmall) {
+    Op o;
+    o.kind = OP_CGSF; o.cls = clsS; o.lev = &L; o.M = &L.Gc; o.perm = L.gperm; o.w = L.gdinv;
+    o.x = x; o.out = x; o.b = b; o.n = nu;
+    o.epi = (zero ? 1 : 0) | ((d0 > 0 ? 1 : d0 < 0 ? 2 : 0) << 1) | ((d1 > 0 ? 1 : d1 < 0 ? 2 : 0) << 3);
+    double per = 0.0;
+    for (int c = 0; c < nc; ++c) per += cgs_bytes(L, c);
+    o.bytes = nu * ((d0 ? 1 : 0) + (d1 ? 1 : 0)) * per;
+    ops->push_back(o);
+    return;
+  }
+  if (zero) {
+    Op z;
+    z.kind = OP_ZERO; z.cls = clsW; z.n = L.n; z.out = x; z.bytes = 8.0 * L.n;
+    ops->push_back(z);
+  }
+  for (int s = 0; s < nu; ++s) {
+    if (d0) cgs_sweep_ops(L, d0 > 0, x, b, clsS, ops);
+    if (d1) cgs_sweep_ops(L, d1 > 0, x, b, clsS, ops);
+  }
+}
+
+// CSR cycle with the point-wise multicolour GS / SGS (cycle_ops_bsr's GS
+// branch restated for CSR): x = 0, nu1 x (forward [+ backward if SGS]),
+// r = b - A x, restrict, recurse (W: a second visit on the updated residual),
+// coarse scaling, x += P e, nu2 x ([forward if SGS] + backward); in place on xout
+void cycle_ops_csr(const DeviceHandle* h, int l, const double* b, double* xout, std::vector<Op>* ops);
+void cycle_ops_csr_gs(const DeviceHandle* h, int l, const double* b, double* xout, std::vector<Op>* ops) {
+  const DLevel& L = h->L[l];
+  const DLevel& C = h->L[l + 1];
+  const mamg_params& p = h->p;
+  const bool l0 = l == 0, sgs = p.smoother == MAMG_SMOOTHER_SGS_POINT;
+  const int tagA = l0 ? 0 : 1;
+  const int clsS = l0 ? C_L0_SMOOTH : C_COARSE;
+  const int clsW = l0 ? C_L0_WB : C_COARSE;
+  double* X = xout;
+  cgs_smooth_ops(L, true, p.presmooth_iter, 1, sgs ? -1 : 0, X, b, clsS, clsW, ops);
+  ops->push_back(csr_op(L.A, EPI_RESID, l0 ? C_L0_RESID : C_COARSE, tagA, X, nullptr, b, nullptr, L.r));
+  ops->push_back(csr_op(L.R, EPI_Y, l0 ? C_L0_R : C_COARSE, tagA, L.r, nullptr, nullptr, nullptr, C.b));
+  cycle_ops_csr(h, l + 1, C.b, C.x, ops);
+  if (p.cycle_type == MAMG_W_CYCLE && !C.coarsest) {
+    ops->push_back(csr_op(C.A, EPI_RESID, C_MISC, 1, C.x, nullptr, C.b, nullptr, C.c));
+    cycle_ops_csr(h, l + 1, C.c, C.e, ops);
+    ops->push_back(axpy_op(C.n, C.e, C.x));
+  }
+  if (p.coarse_scaling) scale_ops(h, l + 1, ops);
+  ops->push_back(csr_op(L.P, EPI_YADD, l0 ? C_L0_P : C_COARSE, tagA, C.x, X, nullptr, nullptr, X));
+  cgs_smooth_ops(L, false, p.postsmooth_iter, sgs ? 1 : 0, -1, X, b, clsS, clsW, ops);
+}
+
 // ---- CSR layout: cycle from zero initial guess: xout = MG_l(b) --------------
 void cycle_ops_csr(const DeviceHandle* h, int l, const double* b, double* xout, std::vector<Op>* ops) {
   const DLevel& L = h->L[l];
   const mamg_params& p = h->p;
   const bool l0 = l == 0;
   if (L.coarsest) { ops->push_back(gemv_op(L, b, xout)); return; }
+  if (L.gcs.size() > 1) { cycle_ops_csr_gs(h, l, b, xout, ops); return; }
   const DLevel& C = h->L[l + 1];
   const bool blk = L.WB.n > 0;
   const int tagA = l0 ? 0 : 1;
@@ -5510,8 +5808,38 @@ void launch_gs(const Op& o, hipStream_t s) {
   }
 }
 
+template <int VL>
+void launch_cgs_vl(const Op& o, hipStream_t s) {
+  const DCsr& M = *o.M;
+  if (o.kind == OP_CGS) {
+    csr_gs_kernel<VL><<<nblocks(o.n * (int64_t)VL), 256, 0, s>>>(o.r0, o.r1, o.perm, M.ptr, M.col, M.val, o.w, o.out,
+                                                                o.b);
+    return;
+  }
+  const DLevel& L = *o.lev;
+  auto dir = [](int v) { return v == 1 ? 1 : v == 2 ? -1 : 0; };
+  csr_gs_small_kernel<VL><<<1, CSR_GS_SMALL_THREADS, (size_t)M.n * sizeof(double), s>>>(
+      M.n, (int)L.gcs.size() - 1, L.gcs_d, o.perm, M.ptr, M.col, M.val, o.w, o.out, o.b, o.epi & 1, (int)o.n,
+      dir((o.epi >> 1) & 3), dir((o.epi >> 3) & 3));
+}
+
+void launch_cgs(const Op& o, hipStream_t s) {
+  switch (o.M->lanes) {
+    case 2: launch_cgs_vl<2>(o, s); break;
+    case 4: launch_cgs_vl<4>(o, s); break;
+    case 8: launch_cgs_vl<8>(o, s); break;
+    case 16: launch_cgs_vl<16>(o, s); break;
+    case 32: launch_cgs_vl<32>(o, s); break;
+    default: launch_cgs_vl<64>(o, s); break;
+  }
+}
+
 void launch(const Op& o, hipStream_t s) {
   switch (o.kind) {
+    case OP_CGS:
+    case OP_CGSF:
+      if (o.n > 0) launch_cgs(o, s);
+      break;
     case OP_CSR:
       if (o.tag == 0) launch_csr_tag<0>(o, s); else launch_csr_tag<1>(o, s);
       break;
@@ -5866,7 +6194,7 @@ int dev_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, Devi
   HIPCHK(hipStreamCreateWithFlags(&h->cap, hipStreamNonBlocking));
   const int nl = (int)H.levels.size();
   h->L.resize(nl);
-  h->bsr = bsr_eligible(H, A0, p);
+  h->bsr = !point_gs(p) && bsr_eligible(H, A0, p);   // point-wise GS: the CSR layout, nodal hierarchies too
   read_knobs();
   if ((gs_smoother(p) || patch_schwarz(p) || rings_schwarz(p)) && !h->bsr) {
     *err = layout_error(p);
@@ -5919,6 +6247,10 @@ int dev_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, Devi
       } else {
         if ((rc = dalloc(h.get(), &D.winv, D.n, err))) return rc;
         HIPCHK(hipMemcpy(D.winv, hl.winv.data(), D.n * sizeof(double), hipMemcpyHostToDevice));
+      }
+      if (point_gs(p)) {
+        TmpPool T;
+        if ((rc = build_gs_csr(h.get(), &T, D.A, l, p.spmv_lanes, &D, err))) return rc;
       }
       if (p.smoother == MAMG_SMOOTHER_POLY) {   // step smoothers w_k W (values only)
         std::vector<double*> wk;
@@ -6032,7 +6364,7 @@ int dev_from_ghier(GHier* G, const DevMat& A0, const mamg_params& p, DeviceHandl
   HIPCHK(hipSetDevice(p.device));
   HIPCHK(hipStreamCreateWithFlags(&h->cap, hipStreamNonBlocking));
   read_knobs();
-  h->bsr = !G->generic;   // a general block or point smoother: the CSR layout (as dev_upload)
+  h->bsr = !G->generic && !point_gs(p);   // a general block or point smoother: the CSR layout (as dev_upload)
   if ((gs_smoother(p) || patch_schwarz(p) || rings_schwarz(p)) && !h->bsr) {
     *err = layout_error(p);
     return MAMG_ERR_UNSUPPORTED;
@@ -6058,6 +6390,10 @@ int dev_from_ghier(GHier* G, const DevMat& A0, const mamg_params& p, DeviceHandl
         } else {
           if ((rc = dalloc(h.get(), &D.winv, D.n, err))) return rc;
           HIPCHK(dev_copy(D.winv, g.winv, D.n * sizeof(double)));
+        }
+        if (point_gs(p)) {
+          TmpPool T;
+          if ((rc = build_gs_csr(h.get(), &T, D.A, l, p.spmv_lanes, &D, err))) return rc;
         }
         if (p.smoother == MAMG_SMOOTHER_POLY) {   // step smoothers w_k W (values only)
           std::vector<double*> wk;
@@ -8131,6 +8467,11 @@ int dev_rank_ops(DistHandle* h, const GHier& G, const DevMat& A0d, const DistPla
 int dist_check(const mamg_params& p, std::string* err) {
   if (p.maxit != 1) {
     *err = "multi-GPU apply supports maxit 1 (one cycle per application, src/amg_parameters.py:71)";
+    return MAMG_ERR_UNSUPPORTED;
+  }
+  if (point_gs(p)) {
+    *err = "multi-GPU apply has no point-wise multicolour GS/SGS (SMOOTHER_GS_POINT / SGS_POINT run on one GPU; "
+           "the multi-GPU smoothers are the node-block ones)";
     return MAMG_ERR_UNSUPPORTED;
   }
   return MAMG_OK;

@@ -2845,6 +2845,16 @@ int gpu_setup(const DevMat& A0, const int32_t* idofs, int64_t n_idofs, const mam
               std::string* err) {
   int rc = check_params(p, err);
   if (rc) return rc;
+  if ((rc = check_point_gs_seeds(p, idofs, n_idofs, err))) return rc;
+  if (point_gs(p)) {   // as host_setup: the hierarchy of the point JACOBI_RHO smoother
+    mamg_params pj = p;
+    pj.smoother = MAMG_SMOOTHER_JACOBI_RHO;
+    pj.node_block_smoother = 0;
+    rc = gpu_setup(A0, idofs, n_idofs, pj, G, err);
+    G->params = p;
+    G->params.node_block_smoother = 0;
+    return rc;
+  }
   if ((rc = check_patch_seeds(p, idofs, n_idofs, A0.n, err))) return rc;
   const int nf = p.num_functions;
   if (nf != 1 && nf != 2) {

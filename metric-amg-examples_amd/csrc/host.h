@@ -71,6 +71,11 @@ int host_setup(const CsrView& A, const int32_t* idofs, int64_t n_idofs,
 mamg_params resolve_params(const mamg_params& in, const int32_t* idofs, int64_t n_idofs, int64_t n);
 mamg_params resolve_like(const mamg_params& in, const mamg_params& built);
 int check_params(const mamg_params& p, std::string* err);
+// point-wise multicolour GS / SGS (CSR layout; device.hip build_gs_csr)
+inline bool point_gs(const mamg_params& p) {
+  return p.smoother == MAMG_SMOOTHER_GS_POINT || p.smoother == MAMG_SMOOTHER_SGS_POINT;
+}
+int check_point_gs_seeds(const mamg_params& p, const int32_t* idofs, int64_t n_idofs, std::string* err);
 int check_patch_seeds(const mamg_params& p, const int32_t* idofs, int64_t n_idofs, int64_t n, std::string* err);
 int check_ring_seeds(const mamg_params& p, const int32_t* idofs, int64_t n_idofs, int64_t n, std::string* err);
 // SCHWARZ_RINGS: most dofs per seed block (one 128-thread workgroup per block

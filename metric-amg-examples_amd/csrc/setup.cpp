@@ -1037,6 +1037,7 @@ int poly_weights(const mamg_params& p, double* w) {
 // mamg_oracle.resolve_params.
 mamg_params resolve_params(const mamg_params& in, const int32_t* idofs, int64_t n_idofs, int64_t n) {
   mamg_params p = in;
+  if (point_gs(p)) p.node_block_smoother = 0;   // point sweeps on the CSR layout (nodal aggregation stays)
   if (p.Schwarz_levels < 1) return p;
   if (p.Schwarz_type == MAMG_SCHWARZ_SYMMETRIC && p.Schwarz_maxlvl >= 1 && p.num_functions == 2 &&
       p.node_block_smoother) {
@@ -1061,6 +1062,7 @@ mamg_params resolve_params(const mamg_params& in, const int32_t* idofs, int64_t 
 // Schwarz name resolves as it did at setup
 mamg_params resolve_like(const mamg_params& in, const mamg_params& built) {
   mamg_params p = in;
+  if (point_gs(p)) p.node_block_smoother = 0;
   if (p.Schwarz_levels >= 1 && p.Schwarz_type == MAMG_SCHWARZ_SYMMETRIC && p.Schwarz_maxlvl >= 1) {
     p.Schwarz_type = built.Schwarz_type;
     p.Schwarz_levels = built.Schwarz_levels;
@@ -1073,8 +1075,10 @@ int check_params(const mamg_params& p, std::string* err) {
   if (p.AMG_type != MAMG_SA_AMG && p.AMG_type != MAMG_UA_AMG) { *err = "AMG_type must be SA_AMG or UA_AMG"; return MAMG_ERR_UNSUPPORTED; }
   if (p.cycle_type != MAMG_V_CYCLE && p.cycle_type != MAMG_W_CYCLE) { *err = "cycle_type must be V_CYCLE or W_CYCLE (AMLI/NL_AMLI/ADD not implemented)"; return MAMG_ERR_UNSUPPORTED; }
   if (p.smoother != MAMG_SMOOTHER_JACOBI && p.smoother != MAMG_SMOOTHER_L1DIAG && p.smoother != MAMG_SMOOTHER_JACOBI_RHO &&
-      p.smoother != MAMG_SMOOTHER_GS && p.smoother != MAMG_SMOOTHER_SGS && p.smoother != MAMG_SMOOTHER_POLY) {
-    *err = "smoother must be SMOOTHER_JACOBI, SMOOTHER_L1DIAG, SMOOTHER_JACOBI_RHO, SMOOTHER_GS, SMOOTHER_SGS or SMOOTHER_POLY";
+      p.smoother != MAMG_SMOOTHER_GS && p.smoother != MAMG_SMOOTHER_SGS && p.smoother != MAMG_SMOOTHER_POLY &&
+      !point_gs(p)) {
+    *err = "smoother must be SMOOTHER_JACOBI, SMOOTHER_L1DIAG, SMOOTHER_JACOBI_RHO, SMOOTHER_GS, SMOOTHER_SGS, "
+           "SMOOTHER_POLY, SMOOTHER_GS_POINT or SMOOTHER_SGS_POINT";
     return MAMG_ERR_UNSUPPORTED;
   }
   if (p.smoother == MAMG_SMOOTHER_POLY &&
@@ -1206,10 +1210,31 @@ int check_ring_seeds(const mamg_params& p, const int32_t* idofs, int64_t n_idofs
   return MAMG_OK;
 }
 
+// SMOOTHER_GS_POINT / SGS_POINT: the level smoother everywhere, so level-0
+// seed blocks are refused
+int check_point_gs_seeds(const mamg_params& p, const int32_t* idofs, int64_t n_idofs, std::string* err) {
+  if (!point_gs(p) || p.Schwarz_levels < 1 || !idofs || n_idofs <= 0) return MAMG_OK;
+  *err = "point-wise multicolour GS/SGS (SMOOTHER_GS_POINT / SGS_POINT) has no level-0 seed blocks. Alternatives: "
+         "Schwarz_levels 0 (the point sweeps everywhere), the node-block SMOOTHER_GS / SGS with "
+         "SCHWARZ_SEED_BLOCKS or SCHWARZ_SYMMETRIC (num_functions 2), or a Jacobi-family smoother with "
+         "SCHWARZ_BLOCK_JACOBI / SCHWARZ_ADDITIVE";
+  return MAMG_ERR_UNSUPPORTED;
+}
+
 int host_setup(const CsrView& A0, const int32_t* idofs, int64_t n_idofs,
                const mamg_params& p, Hierarchy* H, std::string* err) {
   int rc = check_params(p, err);
   if (rc) return rc;
+  if ((rc = check_point_gs_seeds(p, idofs, n_idofs, err))) return rc;
+  if (point_gs(p)) {   // the hierarchy of the point JACOBI_RHO smoother; the sweeps are built with the apply layout
+    mamg_params pj = p;
+    pj.smoother = MAMG_SMOOTHER_JACOBI_RHO;
+    pj.node_block_smoother = 0;
+    rc = host_setup(A0, idofs, n_idofs, pj, H, err);
+    H->params = p;
+    H->params.node_block_smoother = 0;
+    return rc;
+  }
   if ((rc = check_patch_seeds(p, idofs, n_idofs, A0.n, err))) return rc;
   if (A0.n != A0.m || A0.n <= 0) { *err = "A must be square and non-empty"; return MAMG_ERR_ARG; }
   for (int64_t i = 0; i < A0.n; ++i)

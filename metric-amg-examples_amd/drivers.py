@@ -26,8 +26,11 @@ src/bidomain_2d.py:150,239-270) to results/<problem>/error_<...>.txt;
 ``-rhs random`` uses the bench's seeded uniform(-1,1) vector instead.
 ``-profile reference`` (default) takes the AMG parameters the reference's
 driver takes (metric_mono: parameters_metric_schwarz; metric / amg: the
-factories' default dicts); ``-profile mi355x`` the GPU profile
-(parameters_metric_mi355x) for every -precond choice.
+factories' default dicts; hazmath / hazmath_Schwarz: parameters_standard /
+parameters_standard_schwarz through the point-wise AMG factory, AMGhaz;
+hazmath_HEM: parameters_metric through the monolithic metric factory);
+``-profile mi355x`` the GPU profile (parameters_metric_mi355x) for every
+-precond choice.
 Differences (stated, not hidden): the matrices come from the in-library
 generators (problems.py; FEniCS is absent); the EMI drivers' manufactured
 solutions are restated in mms.py (src/emi_2d.py:8-128); the 3D-1D neuron mesh
@@ -75,7 +78,23 @@ def _profile_params(profile, precond):
         return P.parameters_metric_mi355x
     if precond in ('metric_mono', 'metric_hazmath'):
         return P.parameters_metric_schwarz
+    if precond in HAZMATH_TAGS:           # src/bidomain_2d.py:194-199, src/bidomain_3d.py:140-143
+        return HAZMATH_TAGS[precond]
     return None
+
+
+# the reference drivers' hazmath tags and the dicts they pass
+HAZMATH_TAGS = {'hazmath': P.parameters_standard, 'hazmath_Schwarz': P.parameters_standard_schwarz,
+                'hazmath_HEM': P.parameters_metric}
+_printed_substitutions = set()
+
+
+def _print_substitutions(precond, BB):
+    """a factory's stated substitutions, once per tag and text"""
+    for note in getattr(BB, 'substitutions', None) or []:
+        if (precond, note) not in _printed_substitutions:
+            _printed_substitutions.add((precond, note))
+            print('[mamg] -precond %s: %s' % (precond, note), flush=True)
 
 
 def _solve(A, W, b, precond, idofs, tol, maxiter, monolithic_params=None):
@@ -83,10 +102,14 @@ def _solve(A, W, b, precond, idofs, tol, maxiter, monolithic_params=None):
     then = time.time()
     Asp = A.scipy() if hasattr(A, 'scipy') else A
     nf = 2 if W[0] == W[1] else 1
-    if precond == 'metric_mono':
+    if precond in ('metric_mono', 'hazmath_HEM'):   # hazmath_HEM: the same factory, parameters_metric
         BB = get_hazmath_metric_precond_mono(A, W, parameters=monolithic_params, interface_dofs=idofs,
                                              num_functions=nf)
         Aop = A                              # same object: device-resident PCG
+    elif precond in ('hazmath', 'hazmath_Schwarz'):   # AMGhaz: no W, no seeds (src/utils.py:40)
+        BB = get_hazmath_amg_precond(Asp, W, parameters=monolithic_params, pointwise=True)
+        _print_substitutions(precond, BB)
+        Aop = BB._Aop
     elif precond == 'metric':
         BB = get_hazmath_metric_precond(Asp, W, parameters=monolithic_params, interface_dofs=idofs,
                                         num_functions=nf)
@@ -108,7 +131,8 @@ def _solve(A, W, b, precond, idofs, tol, maxiter, monolithic_params=None):
     return x, niters, cond, dt, solver.residuals[-1], BB
 
 
-def bidomain(argv, dim):
+def bidomain_parser(dim):
+    """the bidomain drivers' command line (src/bidomain_2d.py:110-130, src/bidomain_3d.py:58-78)"""
     ap = argparse.ArgumentParser(prog='bidomain_%dd' % dim)
     ap.add_argument('-nrefs', type=int, default=1)
     ap.add_argument('-kappa1', type=float, default=2)
@@ -116,13 +140,19 @@ def bidomain(argv, dim):
     ap.add_argument('-gamma', type=float, default=1)
     ap.add_argument('-pdegree', type=int, default=1, choices=(1,))
     ap.add_argument('-precond', type=str, default='metric_mono',
-                    choices=('metric_mono', 'metric', 'amg', 'diag', 'metric_hazmath'))
+                    choices=('metric_mono', 'metric', 'amg', 'diag', 'metric_hazmath', 'hazmath', 'hazmath_HEM')
+                    + (('hazmath_Schwarz',) if dim == 2 else ()))   # src/bidomain_2d.py:122-123, src/bidomain_3d.py:70-71
     ap.add_argument('-save', type=int, default=0)
     ap.add_argument('-results', type=str, default='./results')
     ap.add_argument('-rhs', type=str, default='mms', choices=('mms', 'random'))
     ap.add_argument('-profile', type=str, default='reference', choices=('reference', 'mi355x'),
                     help="AMG parameters: the reference driver's dicts, or the GPU profile")
-    args, _ = ap.parse_known_args(argv)
+    return ap
+
+
+def bidomain(argv, dim):
+    args, _ = bidomain_parser(dim).parse_known_args(argv)
+    _printed_substitutions.clear()           # stated once per run, not per mesh
     prm = _profile_params(args.profile, args.precond)
     rdir = os.path.join(args.results, 'bidomain_%dd' % dim)
     os.makedirs(rdir, exist_ok=True)

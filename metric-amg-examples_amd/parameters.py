@@ -14,8 +14,10 @@ values are build-defined (HAZmath's are not available here).
   seeds' overlapping 1-ring blocks, which on a nodal system with a seed on
   every node is exactly ``SCHWARZ_PATCHES``, and ``SCHWARZ_RINGS`` for sparse
   seed sets) or raises MAMG_ERR_UNSUPPORTED naming the component it lacks
-  (SGS and multiplicative Schwarz on scalar systems); there is no silent
-  substitution under these names.  ``MetricAMG(A, W, ...)``
+  (the node-block SGS and multiplicative Schwarz on scalar systems; the
+  point-wise SGS of a scalar system is ``SMOOTHER_SGS_POINT``, which
+  ``precond.get_hazmath_amg_precond(pointwise=True)`` selects); there is no
+  silent substitution under these names.  ``MetricAMG(A, W, ...)``
   takes ``num_functions`` from W (equal-sized blocks) when the dict does
   not set it, as the reference's metricAMG receives the block space W.
 * ``parameters_metric_mi355x``: the GPU profile "mi355x_sa_v" (nodal SA,
@@ -58,6 +60,8 @@ V_CYCLE, W_CYCLE = 1, 2
 SMOOTHER_JACOBI, SMOOTHER_L1DIAG, SMOOTHER_JACOBI_RHO = 1, 2, 3
 SMOOTHER_GS, SMOOTHER_SGS = 10, 11
 SMOOTHER_POLY = 12            # Chebyshev polynomial in W A (HAZmath/FASP SMOOTHER_POLY)
+SMOOTHER_GS_POINT, SMOOTHER_SGS_POINT = 13, 14   # point-wise multicolour GS / SGS (CSR layout; AMGhaz's smoother,
+                                                 # precond.get_hazmath_amg_precond(pointwise=True))
 VMB, MIS, MWM, HEC, HEM = 1, 2, 3, 4, 5
 SCHWARZ_FORWARD, SCHWARZ_BACKWARD, SCHWARZ_SYMMETRIC, SCHWARZ_BLOCK_JACOBI = 1, 2, 3, 4
 SCHWARZ_ADDITIVE = 5          # overlapping seed + Schwarz_maxlvl-ring blocks, additive (sparse seed sets)

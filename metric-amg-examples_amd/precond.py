@@ -118,23 +118,59 @@ def get_hazmath_metric_precond(A, W, bcs=None, parameters=None, interface_dofs=N
     return op
 
 
-def get_hazmath_amg_precond(A, W=None, bcs=None, parameters=None, interface_dofs=None, **kw):
+POINTWISE_ORDER_NOTE = ("point-wise SGS/GS in a multicolour order instead of HAZmath's sequential dof order "
+                        '(SMOOTHER_SGS_POINT / SMOOTHER_GS_POINT)')
+
+
+def amg_pointwise_parameters(parameters=None):
+    """The dict ``get_hazmath_amg_precond(..., pointwise=True)`` runs and its
+    substitutions: AMGhaz as the reference calls it (src/utils.py:40, no W, no
+    seeds).  SGS / GS become the point-wise multicolour SMOOTHER_SGS_POINT /
+    SMOOTHER_GS_POINT, num_functions is 1 (point-wise aggregation), and a
+    Schwarz level of the dict is dropped, since AMGhaz receives no seeds.
+    Needs no device."""
+    params = dict(P.parameters_amg_default) if parameters is None else dict(parameters)
+    notes = []
+    point = {P.SMOOTHER_SGS: P.SMOOTHER_SGS_POINT, P.SMOOTHER_GS: P.SMOOTHER_GS_POINT}
+    if params.get('smoother') in point:
+        params['smoother'] = point[params['smoother']]
+        notes.append(POINTWISE_ORDER_NOTE)
+    params['num_functions'] = 1
+    if params.get('Schwarz_levels', 0) >= 1:
+        notes.append('Schwarz_levels %d -> 0 (AMGhaz receives no seeds, src/utils.py:40: no Schwarz level, '
+                     'the level smoother everywhere)' % params['Schwarz_levels'])
+    params['Schwarz_levels'] = 0
+    return params, notes
+
+
+def get_hazmath_amg_precond(A, W=None, bcs=None, parameters=None, interface_dofs=None, pointwise=False, **kw):
     """Plain (non-metric) AMG on the monolithic matrix (src/utils.py:15-42):
     no interface seeds.  ``parameters`` None -> the reference's default dict
     (src/utils.py:20-38, ``parameters.parameters_amg_default``: UA + VMB + W +
     SGS + scaling).
 
-    Substitution: the reference's AMGhaz (src/utils.py:40) never
-    receives W, so HAZmath aggregates point-wise there.  Here W, when given,
+    ``pointwise=True`` is AMGhaz as the reference calls it (src/utils.py:40:
+    it never receives W): point-wise aggregation (num_functions 1; W is not
+    used) and the point-wise SGS / GS of the dict as the multicolour
+    SMOOTHER_SGS_POINT / SMOOTHER_GS_POINT on the CSR layout
+    (``amg_pointwise_parameters``).  ``.substitutions`` records the multicolour
+    order (HAZmath sweeps in the sequential dof order) and a dropped Schwarz
+    level.
+
+    Default (``pointwise=False``), a substitution: W, when given,
     makes the hierarchy nodal (num_functions = the number of equal blocks:
-    nodal aggregation and node-block SGS, the only SGS this build has);
-    ``num_functions=1`` gives point-wise aggregation with a point smoother
-    (SGS then needs a Jacobi-family ``smoother``: this build's SGS is the
-    node-block multicolour one, so a point-wise default would substitute the
-    smoother instead).  The choice is recorded in ``.substitutions`` instead
-    of the num_functions warning on every call; every other warning of the
-    construction still reaches the caller."""
+    nodal aggregation and the node-block multicolour SGS); ``num_functions=1``
+    gives point-wise aggregation, for which SMOOTHER_SGS / SMOOTHER_GS (the
+    node-block smoothers) are refused: pass ``pointwise=True`` or a
+    Jacobi-family ``smoother``.  The choice is recorded in ``.substitutions``
+    instead of the num_functions warning on every call; every other warning
+    of the construction still reaches the caller."""
     import warnings
+    if pointwise:
+        params, notes = amg_pointwise_parameters(parameters)
+        B = MetricAMG(to_monolithic(A), None, idofs=None, parameters=params, **kw)
+        B.substitutions = [n for n in getattr(B, 'notes', [])] + notes
+        return B
     params = dict(P.parameters_amg_default) if parameters is None else dict(parameters)
     params['Schwarz_levels'] = 0
     with warnings.catch_warnings():
