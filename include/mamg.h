@@ -65,9 +65,10 @@ enum {                                                          /* smoother   */
    * relaxation does not enter.  CSR layout, num_functions 1 or 2 (2: nodal
    * aggregation, point sweeps); the setup resolves node_block_smoother to 0
    * and builds the hierarchy of SMOOTHER_JACOBI_RHO (winv is exported, the
-   * sweeps do not use it).  Level-0 seeds (Schwarz_levels >= 1 with idofs),
-   * a non-symmetric pattern or more than 64 colours: MAMG_ERR_UNSUPPORTED; a
-   * missing or non-positive diagonal entry: MAMG_ERR_SETUP.  Single GPU. */
+   * sweeps do not use it).  Level-0 seeds (Schwarz_levels >= 1 with idofs)
+   * with any Schwarz_type but MAMG_SCHWARZ_RINGS, a non-symmetric pattern or
+   * more than 64 colours: MAMG_ERR_UNSUPPORTED; a missing or non-positive
+   * diagonal entry: MAMG_ERR_SETUP.  Single GPU. */
   MAMG_SMOOTHER_GS_POINT = 13,
   MAMG_SMOOTHER_SGS_POINT = 14
 };
@@ -87,8 +88,9 @@ enum {                                                   /* Schwarz_type      */
    * smoother runs everywhere (Schwarz_levels resolved to 0).  With
    * Schwarz_maxlvl 0 the blocks are the seeds' nodes (no overlap) and the
    * type must match the smoother (SYMMETRIC: SGS, FORWARD: GS).  FORWARD /
-   * BACKWARD on overlapping blocks and scalar systems return
-   * MAMG_ERR_UNSUPPORTED. */
+   * BACKWARD on overlapping blocks, and all three names with rings on scalar
+   * systems, return MAMG_ERR_UNSUPPORTED (a scalar system takes the seed
+   * rings by their own name, MAMG_SCHWARZ_RINGS). */
   MAMG_SCHWARZ_FORWARD = 1, MAMG_SCHWARZ_BACKWARD = 2, MAMG_SCHWARZ_SYMMETRIC = 3,
   MAMG_SCHWARZ_BLOCK_JACOBI = 4, /* additive non-overlapping seed blocks (GPU) */
   MAMG_SCHWARZ_ADDITIVE = 5,     /* additive overlapping seed + maxlvl-ring blocks
@@ -114,7 +116,20 @@ enum {                                                   /* Schwarz_type      */
      Schwarz and the rest the GS smoother"): the reference's SCHWARZ_SYMMETRIC
      for any seed set that is not one seed per node with 1-rings (EMI's
      interface seeds, the default dict of src/utils.py:60-82); level 0, BSR2
-     layout (num_functions 2), 1 or N GPUs */
+     layout (num_functions 2), 1 or N GPUs.
+     Named explicitly it also runs on hierarchies that upload in the CSR
+     layout (num_functions 1, or 2 with node_block_smoother 0 or a point-GS
+     smoother; the 3D-1D system): the same blocks, inverses and colours, and
+     on the dofs in no block point-wise GS, coloured on A_0's pattern
+     restricted to uncovered x uncovered.  One level-0 step = ring colours
+     ascending, rest forward, rest backward, ring colours descending, nu1
+     times before and nu2 times after the coarse correction, whatever
+     `smoother` is; levels >= 1 run the level smoother (Jacobi family, POLY,
+     GS_POINT / SGS_POINT).  The hierarchy is the Schwarz_levels 0 one, bit
+     for bit.  More than 64 rest colours or a non-symmetric rest pattern:
+     MAMG_ERR_UNSUPPORTED; a missing or non-positive diagonal entry on an
+     uncovered row: MAMG_ERR_SETUP; without seeds Schwarz_levels resolves to
+     0.  Single GPU. */
   MAMG_SCHWARZ_RINGS = 8
 };
 enum { MAMG_OFF = 0, MAMG_ON = 1 };
@@ -290,7 +305,8 @@ int mamg_comm_unique_id(void* id);
  * with <= rep_nodes nodes are replicated.  V and W cycles, coarse-grid
  * scaling, nu1 / nu2 >= 1; Jacobi-family, POLY and multicolour GS / SGS
  * smoothers on BSR2 (nodal) hierarchies.  SCHWARZ_PATCHES / SCHWARZ_RINGS,
- * CSR-layout hierarchies and maxit > 1 return MAMG_ERR_UNSUPPORTED. */
+ * CSR-layout hierarchies (SCHWARZ_RINGS on them included) and maxit > 1
+ * return MAMG_ERR_UNSUPPORTED. */
 int mamg_setup_dist(const mamg_csr* A, const int32_t* idofs, int64_t n_idofs,
                     const mamg_params* params, int rank, int nranks, const void* comm_id,
                     int64_t rep_nodes, mamg_dhandle** out);
@@ -425,7 +441,8 @@ enum { MAMG_FMT_SELL = 1, MAMG_FMT_SYM = 2, MAMG_FMT_POST_FUSED = 4, MAMG_FMT_PO
        MAMG_FMT_PATCHES = 128,  /* smoother: multiplicative node-patch Schwarz (SCHWARZ_PATCHES) */
        MAMG_FMT_GS = 256,       /* smoother: multicolour GS / SGS sweeps (node-block: BSR2 layout;
                                    point-wise, SMOOTHER_GS_POINT / SGS_POINT: CSR layout) */
-       MAMG_FMT_RINGS = 512,    /* smoother: multiplicative seed-ring Schwarz + GS on the rest (SCHWARZ_RINGS) */
+       MAMG_FMT_RINGS = 512,    /* smoother: multiplicative seed-ring Schwarz + GS on the rest (SCHWARZ_RINGS;
+                                   on the CSR layout level 0 reports MAMG_FMT_RINGS | MAMG_FMT_GS) */
        MAMG_FMT_R_BANDS = 1024,    /* restriction rows walked plane band by plane band per XCD */
        MAMG_FMT_K_COL16 = 2048 };  /* K's columns as 16-bit offsets from a per-slice base */
 int mamg_level_format(const mamg_handle* h, int level);
@@ -441,7 +458,12 @@ int mamg_kregion_info(const mamg_handle* h, double* ms, int cap, int* n, int* ke
  * 8 (rows + 1) (pointers) + 4 rows (perm) + 8 rows (1/a_ii) + 8 rows (b) +
  * 16 rows (own x read, written) + 8 n / ncolours (the gathered x, every entry
  * once per sweep); a small level's one-launch smoothing call counts the sum
- * over its colour steps. */
+ * over its colour steps.  A seed-ring colour step
+ * on the CSR layout whose blocks hold d_k members each, `m` members in all
+ * with `nnz` entries in their rows of A_0, counts 8 sum d_k^2 (inverses) +
+ * 12 nnz (values, columns) + 8 nnz (the gathered x) + 16 m (pointers) +
+ * 4 m (members) + 8 m (b) + 16 m (own x read, written) + 16 per block
+ * (offsets). */
 int mamg_apply_bytes(const mamg_handle* h, double* total_bytes);
 
 /* z = B r : one preconditioner application (`maxit` cycles from x0 = 0).

@@ -2469,6 +2469,111 @@ __global__ __launch_bounds__(RING_THREADS) void ring_kernel(int64_t k0, const in
   }
 }
 
+// The same step on the CSR layout (scalar systems, nodal ones with point
+// smoothers): members are plain dof indices, a member's residual comes from
+// its scalar row of A_0.  Those rows hold 15 to ~400 entries (the 3D-1D
+// coupling rows), so a row is read by a group of RING_CSR_VL lanes with a
+// shuffle reduction (csr_gs_row), 64 rows per pass of the 1024-thread
+// workgroup; after the barrier the local solve delta_a = sum_c Minv(a, c) r_c
+// reads the transposed inverse coalesced over a, the c range cut into
+// RING_CSR_PARTS quarters (one per 256 threads) whose partial sums meet in
+// LDS and are added in a fixed order; x is updated in place.  A ring colour
+// holds a handful of blocks, so a launch is a few workgroups on an otherwise
+// idle device and its time is the latency of the two serial loops: 1024
+// threads instead of 256 cut a launch from 33 to 24 us at 200-dof blocks
+// with member rows of up to 93 entries and from 60 to 36 us with rows of up
+// to 388 (3D-1D n = 48, radius 1.0 / 5.0).  Every loop is bounded
+// by the block size (<= RING_MAX_DOFS) and the row length; no scratch.
+// Oracle: mamg_oracle.Rings.sweep (tests/pointrings_ref.py).
+constexpr int RING_CSR_THREADS = 1024;
+constexpr int RING_CSR_VL = 16;
+constexpr int RING_CSR_PARTS = RING_CSR_THREADS / RING_MAX_DOFS;
+static_assert(RING_CSR_PARTS == 4 && RING_CSR_PARTS * RING_MAX_DOFS == RING_CSR_THREADS, "four quarters of the local solve");
+__global__ __launch_bounds__(RING_CSR_THREADS) void ring_csr_kernel(int64_t k0, const int64_t* __restrict__ mo,
+                                                                 const int32_t* __restrict__ mem,
+                                                                 const int64_t* __restrict__ io,
+                                                                 const double* __restrict__ minvT,
+                                                                 const int64_t* __restrict__ ptr,
+                                                                 const int32_t* __restrict__ col,
+                                                                 const double* __restrict__ val, double* x,
+                                                                 const double* __restrict__ b) {
+  __shared__ double res[RING_MAX_DOFS];
+  __shared__ double part[RING_CSR_PARTS][RING_MAX_DOFS];
+  constexpr int RPP = RING_CSR_THREADS / RING_CSR_VL;   // member rows per pass
+  const int64_t k = k0 + blockIdx.x;
+  const int64_t m0 = mo[k];
+  const int d = (int)(mo[k + 1] - m0);                  // <= RING_MAX_DOFS (check_params)
+  const double* T = minvT + io[k];
+  const int lane = threadIdx.x & (RING_CSR_VL - 1), grp = threadIdx.x / RING_CSR_VL;
+  for (int base = 0; base < d; base += RPP) {
+    const int a = base + grp;
+    const bool on = a < d;
+    const int64_t g = on ? mem[m0 + a] : 0;
+    const double s = csr_gs_row<RING_CSR_VL>(on, g, lane, ptr, col, val, x);
+    if (on && lane == 0) res[a] = b[g] - s;
+  }
+  __syncthreads();
+  const int a = threadIdx.x & (RING_MAX_DOFS - 1), q = threadIdx.x / RING_MAX_DOFS;
+  if (a < d) {
+    const int chunk = (d + RING_CSR_PARTS - 1) / RING_CSR_PARTS;
+    const int c0 = q * chunk, c1 = min(d, c0 + chunk);
+    double dl = 0.0;
+    for (int c = c0; c < c1; ++c) dl += T[(int64_t)c * d + a] * res[c];
+    part[q][a] = dl;
+  }
+  __syncthreads();
+  if (threadIdx.x < d)
+    x[mem[m0 + threadIdx.x]] += (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
+}
+
+// the rest's point GS (RINGS on the CSR layout) colours the uncovered rows
+// only: A_0's pattern with every covered row emptied and every covered column
+// dropped (the coupling rows, all covered, would need more than 64 colours).
+// Row lengths into flen[I + 1], then the columns in order.
+__global__ __launch_bounds__(256) void rest_pattern_len_kernel(int64_t n, const int64_t* __restrict__ ptr,
+                                                               const int32_t* __restrict__ col,
+                                                               const uint8_t* __restrict__ cov,
+                                                               int64_t* __restrict__ flen) {
+  const int64_t I = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (I >= n) return;
+  int64_t c = 0;
+  if (!cov[I])
+    for (int64_t k = ptr[I]; k < ptr[I + 1]; ++k) c += cov[col[k]] ? 0 : 1;
+  flen[I + 1] = c;
+}
+__global__ __launch_bounds__(256) void rest_pattern_fill_kernel(int64_t n, const int64_t* __restrict__ ptr,
+                                                                const int32_t* __restrict__ col,
+                                                                const uint8_t* __restrict__ cov,
+                                                                const int64_t* __restrict__ fptr,
+                                                                int32_t* __restrict__ fcol) {
+  const int64_t I = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (I >= n || cov[I]) return;
+  int64_t o = fptr[I];
+  for (int64_t k = ptr[I]; k < ptr[I + 1]; ++k)
+    if (!cov[col[k]]) fcol[o++] = col[k];
+}
+// colour_count_kernel for the rest: a covered row sorts behind every colour
+// (key 64) and is counted in no colour
+__global__ __launch_bounds__(256) void rest_count_kernel(int64_t n, const int8_t* __restrict__ c,
+                                                         const uint8_t* __restrict__ cov, int32_t* __restrict__ ci,
+                                                         int64_t* __restrict__ iota, unsigned long long* cnt) {
+  __shared__ unsigned int hist[64];
+  if (threadIdx.x < 64) hist[threadIdx.x] = 0;
+  __syncthreads();
+  const int64_t I = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (I < n) {
+    iota[I] = I;
+    if (cov[I]) {
+      ci[I] = 64;
+    } else {
+      ci[I] = c[I];
+      atomicAdd(&hist[c[I]], 1u);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 64 && hist[threadIdx.x]) atomicAdd(cnt + threadIdx.x, (unsigned long long)hist[threadIdx.x]);
+}
+
 // block j of the colour order <- block ord[j] of ring_blocks_dev's output:
 // its inverse transposed into rinv at rio[j]
 __global__ __launch_bounds__(256) void ring_perm_inv_kernel(int64_t nb, const int32_t* __restrict__ ord,
@@ -2826,6 +2931,12 @@ struct DLevel {
   std::vector<int64_t> rcs;
   int64_t rnm = 0;          // members of all blocks
   double rinv_n = 0.0;      // inverse entries of all blocks
+  // ... on the CSR layout (scalar systems, point smoothers): rmem holds plain
+  // dof indices, the member rows are A's, the rest's point-wise GS over the
+  // uncovered rows is in Gc / gperm / gdinv / gcs; per colour c the members,
+  // inverse entries and member-row entries of its blocks, as prefix sums
+  // (the byte count of a colour step)
+  std::vector<int64_t> rcm, rci, rce;
   // coarse-grid correction scaling of the correction computed ON this level:
   // q = A_l e, partial sums of <b, e>, <q, e>
   double* q = nullptr;
@@ -2835,7 +2946,8 @@ struct DLevel {
 enum OpKind { OP_CSR = 0, OP_SCALE = 1, OP_GEMV = 2, OP_AXPY = 3, OP_BSR = 4, OP_BD = 5, OP_POST = 6, OP_ILV = 7,
               OP_GS = 8, OP_ZERO = 9, OP_DOT2 = 10, OP_CSCALE = 11, OP_PATCH = 12, OP_TAIL = 13, OP_RING = 14,
               OP_CGS = 15,     // point-wise GS, one colour of a CSR level (csr_gs_kernel)
-              OP_CGSF = 16 };  // point-wise GS, a small level's whole smoothing call (csr_gs_small_kernel)
+              OP_CGSF = 16,    // point-wise GS, a small level's whole smoothing call (csr_gs_small_kernel)
+              OP_CRING = 17 }; // one colour of a seed-ring sweep on the CSR layout (ring_csr_kernel)
 // kernel classes (kernel_ms / class_bytes slots)
 enum Cls {
   C_L0_RESID = 0,   // dominant: r = b - A0 x (once per apply)
@@ -4293,15 +4405,20 @@ inline int64_t csr_gs_small_rows() {
 // the scalar graph), a stable radix sort of the rows by colour, the
 // colour-contiguous permuted copy (D->Gc), perm, 1 / a_ii per permuted row and
 // the colour ranges.  Shared by dev_upload and dev_from_ghier.
+// With cov (one byte per row, device; the seed rings' rest, build_rings_csr)
+// the colouring runs on *pattern instead, and only the rows with cov == 0
+// enter the colour lists and the permuted copy (G.ptr then has one entry per
+// listed row + 1; G.n stays the length of x).
 template <class HT>
-int build_gs_csr(HT* h, TmpPool* T, const DCsr& A, int level, int lanes, DLevel* D, std::string* err) {
+int build_gs_csr(HT* h, TmpPool* T, const DCsr& A, int level, int lanes, DLevel* D, std::string* err,
+                 const TBsr* pattern = nullptr, const uint8_t* cov = nullptr) {
   int rc;
   const int64_t n = A.n;
   TBsr B;                        // the scalar graph as gs_colour reads it (ptr, col)
   B.nr = n; B.nc = A.m; B.nb = A.nnz; B.ptr = A.ptr; B.col = A.col;
   int8_t* ca = nullptr;
   int ncol = 0;
-  if ((rc = gs_colour(T, B, level, &ca, &ncol, err))) return rc;
+  if ((rc = gs_colour(T, pattern ? *pattern : B, level, &ca, &ncol, err))) return rc;
   int* flag = nullptr;
   unsigned long long* cnt = nullptr;
   int32_t *ci = nullptr, *cs = nullptr;
@@ -4315,33 +4432,42 @@ int build_gs_csr(HT* h, TmpPool* T, const DCsr& A, int level, int lanes, DLevel*
   if ((rc = T->alloc(&gcs_t, 65, err))) return rc;
   HIPCHK(dev_memset(flag, 0, sizeof(int)));
   HIPCHK(dev_memset(cnt, 0, 64 * sizeof(unsigned long long)));
-  colour_count_kernel<<<nblocks(n), 256>>>(n, ca, ci, iota, cnt);
+  if (cov) rest_count_kernel<<<nblocks(n), 256>>>(n, ca, cov, ci, iota, cnt);
+  else colour_count_kernel<<<nblocks(n), 256>>>(n, ca, ci, iota, cnt);
   HIPCHK(hipGetLastError());
-  if ((rc = dsort_pairs_i32_i64(ci, cs, iota, sorted, n, 6, nullptr, err))) return rc;
+  if ((rc = dsort_pairs_i32_i64(ci, cs, iota, sorted, n, cov ? 7 : 6, nullptr, err))) return rc;
   unsigned long long hc[64];
   HIPCHK(hipMemcpy(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost));
   std::vector<int64_t> gcs(65, 0);
   for (int c = 0; c < 64; ++c) gcs[c + 1] = gcs[c] + (c < ncol ? (int64_t)hc[c] : 0);
+  const int64_t nr = gcs[64];    // listed rows: n, or the uncovered ones (sorted first)
   HIPCHK(hipMemcpy(gcs_t, gcs.data(), 65 * sizeof(int64_t), hipMemcpyHostToDevice));
   D->gcs.assign(gcs.begin(), gcs.begin() + ncol + 1);
   if ((rc = dalloc(h, &D->gcs_d, 65, err))) return rc;
   HIPCHK(dev_copy(D->gcs_d, gcs_t, 65 * sizeof(int64_t)));
   DCsr& G = D->Gc;
   G.n = n; G.m = A.m; G.nnz = A.nnz;
-  G.lanes = lanes > 0 ? lanes : pick_lanes(n, A.nnz);
-  if ((rc = dalloc(h, &G.ptr, n + 1, err))) return rc;
-  if ((rc = dalloc(h, &G.col, std::max<int64_t>(A.nnz, 1), err))) return rc;
-  if ((rc = dalloc(h, &G.val, std::max<int64_t>(A.nnz, 1), err))) return rc;
-  if ((rc = dalloc(h, &D->gperm, n, err))) return rc;
-  if ((rc = dalloc(h, &D->gdinv, n, err))) return rc;
+  if ((rc = dalloc(h, &G.ptr, nr + 1, err))) return rc;
+  if (!cov) {
+    if ((rc = dalloc(h, &G.col, std::max<int64_t>(A.nnz, 1), err))) return rc;
+    if ((rc = dalloc(h, &G.val, std::max<int64_t>(A.nnz, 1), err))) return rc;
+  }
+  if ((rc = dalloc(h, &D->gperm, std::max<int64_t>(nr, 1), err))) return rc;
+  if ((rc = dalloc(h, &D->gdinv, std::max<int64_t>(nr, 1), err))) return rc;
   HIPCHK(dev_memset(G.ptr, 0, sizeof(int64_t)));
   // unpadded: permuted row = sorted position (pcs = gcs)
-  perm_place_kernel<<<nblocks(n), 256>>>(n, cs, sorted, gcs_t, gcs_t, D->gperm);
+  if (nr) perm_place_kernel<<<nblocks(nr), 256>>>(nr, cs, sorted, gcs_t, gcs_t, D->gperm);
   HIPCHK(hipGetLastError());
-  perm_len_kernel<<<nblocks(n), 256>>>(n, D->gperm, A.ptr, G.ptr);
+  if (nr) perm_len_kernel<<<nblocks(nr), 256>>>(nr, D->gperm, A.ptr, G.ptr);
   HIPCHK(hipGetLastError());
-  if ((rc = dscan_incl_i64(G.ptr, G.ptr, n + 1, nullptr, err))) return rc;
-  csr_gs_fill_kernel<<<nblocks(n), 256>>>(n, D->gperm, A.ptr, A.col, A.val, G.ptr, G.col, G.val, D->gdinv, flag);
+  if ((rc = dscan_incl_i64(G.ptr, G.ptr, nr + 1, nullptr, err))) return rc;
+  if (cov) {                     // the listed rows' entries only
+    HIPCHK(hipMemcpy(&G.nnz, G.ptr + nr, sizeof(int64_t), hipMemcpyDeviceToHost));
+    if ((rc = dalloc(h, &G.col, std::max<int64_t>(G.nnz, 1), err))) return rc;
+    if ((rc = dalloc(h, &G.val, std::max<int64_t>(G.nnz, 1), err))) return rc;
+  }
+  G.lanes = lanes > 0 ? lanes : pick_lanes(std::max<int64_t>(nr, 1), G.nnz);
+  if (nr) csr_gs_fill_kernel<<<nblocks(nr), 256>>>(nr, D->gperm, A.ptr, A.col, A.val, G.ptr, G.col, G.val, D->gdinv, flag);
   HIPCHK(hipGetLastError());
   int hf = 0;
   HIPCHK(hipMemcpy(&hf, flag, sizeof(int), hipMemcpyDeviceToHost));
@@ -4355,6 +4481,48 @@ int build_gs_csr(HT* h, TmpPool* T, const DCsr& A, int level, int lanes, DLevel*
   D->gsmall = n <= csr_gs_small_rows();
   for (void* q : {(void*)ca, (void*)flag, (void*)cnt, (void*)ci, (void*)cs, (void*)iota, (void*)sorted, (void*)gcs_t})
     T->release(q);
+  return MAMG_OK;
+}
+
+int build_ring_blocks(DeviceHandle* h, TmpPool* T, const DevMat& A, const std::vector<int32_t>& seeds, DLevel* D,
+                      std::vector<int32_t>* rm, std::string* err);
+
+// Seed-ring Schwarz data of level 0 on the CSR layout (SCHWARZ_RINGS on a
+// scalar system, or a nodal one with point smoothers) from the handle's A_0:
+// the blocks (build_ring_blocks) with their members as plain dof indices, and
+// the rest's point-wise multicolour GS over the rows in no block.  The rest
+// is coloured on A_0's pattern restricted to uncovered x uncovered: with the
+// 3D-1D averaging the coupling rows hold ~400 entries and the whole graph
+// needs more than 64 colours, while every such row lies in a block (DESIGN.md
+// section 2.12.1).  Covered rows take no update and enter no colour list.
+int build_rings_csr(DeviceHandle* h, TmpPool* T, const std::vector<int32_t>& seeds, int lanes, DLevel* D,
+                    std::string* err) {
+  const DCsr& A = D->A;
+  const int64_t n = A.n;
+  DevMat Am;
+  Am.n = A.n; Am.m = A.m; Am.nnz = A.nnz; Am.ptr = A.ptr; Am.col = A.col; Am.val = A.val;
+  std::vector<int32_t> rm;
+  int rc = build_ring_blocks(h, T, Am, seeds, D, &rm, err);
+  if (rc) return rc;
+  HIPCHK(hipMemcpy(D->rmem, rm.data(), rm.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  std::vector<uint8_t> cov(n, 0);
+  for (int32_t g : rm) cov[g] = 1;
+  uint8_t* dcov = nullptr;
+  TBsr F;                        // the filtered pattern (ptr, col)
+  F.nr = n; F.nc = n;
+  if ((rc = T->alloc(&dcov, n, err))) return rc;
+  if ((rc = T->alloc(&F.ptr, n + 1, err))) return rc;
+  HIPCHK(hipMemcpy(dcov, cov.data(), n, hipMemcpyHostToDevice));
+  HIPCHK(dev_memset(F.ptr, 0, sizeof(int64_t)));
+  rest_pattern_len_kernel<<<nblocks(n), 256>>>(n, A.ptr, A.col, dcov, F.ptr);
+  HIPCHK(hipGetLastError());
+  if ((rc = dscan_incl_i64(F.ptr, F.ptr, n + 1, nullptr, err))) return rc;
+  HIPCHK(hipMemcpy(&F.nb, F.ptr + n, sizeof(int64_t), hipMemcpyDeviceToHost));
+  if ((rc = T->alloc(&F.col, F.nb, err))) return rc;
+  rest_pattern_fill_kernel<<<nblocks(n), 256>>>(n, A.ptr, A.col, dcov, F.ptr, F.col);
+  HIPCHK(hipGetLastError());
+  if ((rc = build_gs_csr(h, T, A, 0, lanes, D, err, &F, dcov))) return rc;
+  T->release(F.ptr); T->release(F.col); T->release(dcov);
   return MAMG_OK;
 }
 
@@ -4515,24 +4683,25 @@ inline bool rings_schwarz(const mamg_params& p) {
   return p.Schwarz_levels >= 1 && p.Schwarz_type == MAMG_SCHWARZ_RINGS;
 }
 
-// Seed-ring Schwarz data of level 0 (Schwarz_type RINGS) from A_0's device
-// CSR S.A and node BSR2 B: the blocks and their inverses on the device
-// (ring_blocks_dev: the additive form's breadth-first rings and Gauss-Jordan
-// kernels), the greedy conflict colouring on the host (setup.cpp
+// The layout-independent half of the seed-ring Schwarz data of level 0
+// (Schwarz_type RINGS) from A_0's device CSR: the blocks and their inverses on
+// the device (ring_blocks_dev: the additive form's breadth-first rings and
+// Gauss-Jordan kernels), the greedy conflict colouring on the host (setup.cpp
 // ring_colouring, in seed order: the sequential step, as VMB's), the blocks
-// re-ordered colour by colour with their inverses transposed, A_0's plain
-// BSR2 copy for the block rows, and the rest's multicolour node-block GS with
-// the covered dofs masked out (mamg_oracle.rest_gs_inverse).
-int build_rings(DeviceHandle* h, TmpPool* T, const TBsr& B, const LevelSrc& S, DLevel* D, std::string* err) {
+// re-ordered colour by colour (rcs, rmo, rio) with their inverses transposed
+// (rinv).  *rm: the members as plain dof indices in that order; the caller
+// stores them in its layout's numbering (rmem).
+int build_ring_blocks(DeviceHandle* h, TmpPool* T, const DevMat& A, const std::vector<int32_t>& seeds, DLevel* D,
+                      std::vector<int32_t>* rm, std::string* err) {
   const mamg_params& p = h->p;
-  if (!S.seeds || S.seeds->empty()) { *err = "seed rings: no seeds"; return MAMG_ERR_ARG; }
-  const int64_t n = S.A.n, nv = n / 2, ns = (int64_t)S.seeds->size();
+  if (seeds.empty()) { *err = "seed rings: no seeds"; return MAMG_ERR_ARG; }
+  const int64_t n = A.n, ns = (int64_t)seeds.size();
   const auto t0 = std::chrono::steady_clock::now();
   auto ms_since = [](std::chrono::steady_clock::time_point a) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
   };
   RingBlocks RB;
-  int rc = ring_blocks_dev(S.A, S.seeds->data(), ns, p.Schwarz_maxlvl, p.Schwarz_mmsize, &RB, err);
+  int rc = ring_blocks_dev(A, seeds.data(), ns, p.Schwarz_maxlvl, p.Schwarz_mmsize, &RB, err);
   if (rc) return rc;
   struct Guard { RingBlocks* r; ~Guard() { ring_blocks_free(r); } } guard{&RB};
   const int mm = RB.mm;
@@ -4546,9 +4715,9 @@ int build_rings(DeviceHandle* h, TmpPool* T, const TBsr& B, const LevelSrc& S, D
   for (int64_t k = 0; k < ns; ++k) std::copy(blk.begin() + k * mm, blk.begin() + k * mm + blen[k], mem.begin() + bptr[k]);
   // A_0's pattern for the conflict graph
   std::vector<int64_t> aptr(n + 1);
-  std::vector<int32_t> acol(S.A.nnz);
-  HIPCHK(hipMemcpy(aptr.data(), S.A.ptr, (n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(acol.data(), S.A.col, S.A.nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
+  std::vector<int32_t> acol(A.nnz);
+  HIPCHK(hipMemcpy(aptr.data(), A.ptr, (n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(acol.data(), A.col, A.nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
   CsrView Av;
   Av.n = Av.m = n; Av.ptr = aptr.data(); Av.col = acol.data();
   std::vector<int32_t> colour;
@@ -4571,33 +4740,58 @@ int build_rings(DeviceHandle* h, TmpPool* T, const TBsr& B, const LevelSrc& S, D
   for (int32_t c : colour) D->rcs[c + 1]++;
   for (int c = 0; c < ncol; ++c) D->rcs[c + 1] += D->rcs[c];
   std::vector<int64_t> mo(ns + 1, 0), io(ns + 1, 0);
-  std::vector<int32_t> rm;
-  rm.reserve(mem.size());
-  std::vector<uint8_t> cov(nv, 0);
+  rm->clear();
+  rm->reserve(mem.size());
   for (int64_t j = 0; j < ns; ++j) {
     const int64_t o = ord[j], d = blen[o];
     mo[j + 1] = mo[j] + d;
     io[j + 1] = io[j] + d * d;
-    for (int64_t t = bptr[o]; t < bptr[o + 1]; ++t) {
-      const int64_t g = mem[t], I = g % nv, f = g / nv;
-      rm.push_back((int32_t)(2 * I + f));
-      cov[I] |= (uint8_t)(1u << f);
-    }
+    rm->insert(rm->end(), mem.begin() + bptr[o], mem.begin() + bptr[o + 1]);
   }
   D->rnm = mo[ns];
   D->rinv_n = (double)io[ns];
+  D->rcm.assign(ncol + 1, 0);
+  D->rci.assign(ncol + 1, 0);
+  D->rce.assign(ncol + 1, 0);
+  for (int c = 0; c < ncol; ++c) {
+    D->rcm[c + 1] = mo[D->rcs[c + 1]];
+    D->rci[c + 1] = io[D->rcs[c + 1]];
+    int64_t e = D->rce[c];
+    for (int64_t t = mo[D->rcs[c]]; t < mo[D->rcs[c + 1]]; ++t) e += aptr[(*rm)[t] + 1] - aptr[(*rm)[t]];
+    D->rce[c + 1] = e;
+  }
   if ((rc = dalloc(h, &D->rmo, ns + 1, err))) return rc;
   if ((rc = dalloc(h, &D->rio, ns + 1, err))) return rc;
   if ((rc = dalloc(h, &D->rmem, std::max<int64_t>(D->rnm, 1), err))) return rc;
   if ((rc = dalloc(h, &D->rinv, std::max<int64_t>(io[ns], 1), err))) return rc;
   HIPCHK(hipMemcpy(D->rmo, mo.data(), (ns + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(D->rio, io.data(), (ns + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(D->rmem, rm.data(), rm.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   int32_t* dord = nullptr;
   if ((rc = T->alloc(&dord, ns, err))) return rc;
   HIPCHK(hipMemcpy(dord, ord.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice));
   ring_perm_inv_kernel<<<(unsigned)ns, 256>>>(ns, dord, RB.blen, RB.sq, RB.inv, D->rio, D->rinv);
   HIPCHK(hipGetLastError());
+  return MAMG_OK;   // ring_blocks_dev's buffers: freed by the guard, null-stream ordered
+}
+
+// Seed-ring Schwarz data of level 0 on the BSR2 layout from A_0's device CSR
+// S.A and node BSR2 B: the blocks (build_ring_blocks) with their members as
+// node-interleaved dof indices, A_0's plain BSR2 copy for the block rows, and
+// the rest's multicolour node-block GS with the covered dofs masked out
+// (mamg_oracle.rest_gs_inverse).
+int build_rings(DeviceHandle* h, TmpPool* T, const TBsr& B, const LevelSrc& S, DLevel* D, std::string* err) {
+  if (!S.seeds || S.seeds->empty()) { *err = "seed rings: no seeds"; return MAMG_ERR_ARG; }
+  const int64_t n = S.A.n, nv = n / 2;
+  std::vector<int32_t> rm;
+  int rc = build_ring_blocks(h, T, S.A, *S.seeds, D, &rm, err);
+  if (rc) return rc;
+  std::vector<uint8_t> cov(nv, 0);
+  for (int32_t& g : rm) {
+    const int64_t I = g % nv, f = g / nv;
+    g = (int32_t)(2 * I + f);
+    cov[I] |= (uint8_t)(1u << f);
+  }
+  HIPCHK(hipMemcpy(D->rmem, rm.data(), rm.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   // A_0's block rows: plain BSR2 in node order
   D->Snb = B.nb;
   if ((rc = dalloc(h, &D->Sptr, B.nr + 1, err))) return rc;
@@ -4618,7 +4812,7 @@ int build_rings(DeviceHandle* h, TmpPool* T, const TBsr& B, const LevelSrc& S, D
   const int64_t nrp = D->gcs.empty() ? 0 : D->gcs.back();
   if (nrp) rest_mask_kernel<<<nblocks(nrp), 256>>>(nrp, D->gperm, dcov, D->Gd);
   HIPCHK(hipGetLastError());
-  return MAMG_OK;   // ring_blocks_dev's buffers: freed by the guard, null-stream ordered
+  return MAMG_OK;
 }
 
 int build_bsr_level(DeviceHandle* h, int l, const LevelSrc& S, int64_t nvc, int lanesA, std::string* err) {
@@ -4833,6 +5027,61 @@ void cgs_smooth_ops(const DLevel& L, bool zero, int nu, int d0, int d1, double* 
   }
 }
 
+// one colour of a seed-ring sweep on the CSR layout (mamg.h mamg_apply_bytes,
+// ring_op's count restated for scalar rows): the blocks' transposed inverses,
+// their members' rows of A_0 (values + columns and the gathered x per entry,
+// two pointers per row), members, b, own x read and written, two offsets per
+// block
+Op ring_csr_op(const DLevel& L, int c, double* x, const double* b, int cls) {
+  Op o;
+  o.kind = OP_CRING; o.cls = cls; o.lev = &L; o.M = &L.A;
+  o.out = x; o.b = b;
+  o.r0 = L.rcs[c]; o.r1 = L.rcs[c + 1]; o.n = o.r1 - o.r0;
+  const double m = (double)(L.rcm[c + 1] - L.rcm[c]), ent = (double)(L.rce[c + 1] - L.rce[c]);
+  o.bytes = 8.0 * (double)(L.rci[c + 1] - L.rci[c]) + 20.0 * ent + m * (16.0 + 4.0 + 8.0 + 16.0) + 16.0 * o.n;
+  return o;
+}
+
+// one symmetric level-0 step of the seed rings on the CSR layout
+// (tests/pointrings_ref.py step): ring colours ascending, the rest's point GS
+// forward then backward, ring colours descending.  A level of at most
+// CSR_GS_SMALL_ROWS rows runs the rest's two sweeps as one launch.
+void ring_csr_step_ops(const DLevel& L, double* x, const double* b, std::vector<Op>* ops) {
+  const int nc = (int)L.rcs.size() - 1;
+  for (int c = 0; c < nc; ++c)
+    if (L.rcs[c + 1] > L.rcs[c]) ops->push_back(ring_csr_op(L, c, x, b, C_L0_SMOOTH));
+  if (L.gcs.size() > 1 && L.gcs.back() > 0) cgs_smooth_ops(L, false, 1, 1, -1, x, b, C_L0_SMOOTH, C_L0_WB, ops);
+  for (int c = nc - 1; c >= 0; --c)
+    if (L.rcs[c + 1] > L.rcs[c]) ops->push_back(ring_csr_op(L, c, x, b, C_L0_SMOOTH));
+}
+
+// CSR cycle of level 0 with the seed-ring Schwarz (SCHWARZ_RINGS on the CSR
+// layout): x = 0, nu1 steps, r = b - A x, restrict, the level smoother's own
+// CSR cycle below (W: a second visit), coarse scaling, x += P e, nu2 steps;
+// the step is palindromic, so it serves both sides; in place on xout
+void cycle_ops_csr(const DeviceHandle* h, int l, const double* b, double* xout, std::vector<Op>* ops);
+void cycle_ops_csr_rings(const DeviceHandle* h, const double* b, double* xout, std::vector<Op>* ops) {
+  const DLevel& L = h->L[0];
+  const DLevel& C = h->L[1];
+  const mamg_params& p = h->p;
+  double* X = xout;
+  Op z;
+  z.kind = OP_ZERO; z.cls = C_L0_WB; z.n = L.n; z.out = X; z.bytes = 8.0 * L.n;
+  ops->push_back(z);
+  for (int s = 0; s < p.presmooth_iter; ++s) ring_csr_step_ops(L, X, b, ops);
+  ops->push_back(csr_op(L.A, EPI_RESID, C_L0_RESID, 0, X, nullptr, b, nullptr, L.r));
+  ops->push_back(csr_op(L.R, EPI_Y, C_L0_R, 0, L.r, nullptr, nullptr, nullptr, C.b));
+  cycle_ops_csr(h, 1, C.b, C.x, ops);
+  if (p.cycle_type == MAMG_W_CYCLE && !C.coarsest) {
+    ops->push_back(csr_op(C.A, EPI_RESID, C_MISC, 1, C.x, nullptr, C.b, nullptr, C.c));
+    cycle_ops_csr(h, 1, C.c, C.e, ops);
+    ops->push_back(axpy_op(C.n, C.e, C.x));
+  }
+  if (p.coarse_scaling) scale_ops(h, 1, ops);
+  ops->push_back(csr_op(L.P, EPI_YADD, C_L0_P, 0, C.x, X, nullptr, nullptr, X));
+  for (int s = 0; s < p.postsmooth_iter; ++s) ring_csr_step_ops(L, X, b, ops);
+}
+
 // CSR cycle with the point-wise multicolour GS / SGS (cycle_ops_bsr's GS
 // branch restated for CSR): x = 0, nu1 x (forward [+ backward if SGS]),
 // r = b - A x, restrict, recurse (W: a second visit on the updated residual),
@@ -4867,6 +5116,7 @@ void cycle_ops_csr(const DeviceHandle* h, int l, const double* b, double* xout, 
   const mamg_params& p = h->p;
   const bool l0 = l == 0;
   if (L.coarsest) { ops->push_back(gemv_op(L, b, xout)); return; }
+  if (l0 && L.rcs.size() > 1) { cycle_ops_csr_rings(h, b, xout, ops); return; }
   if (L.gcs.size() > 1) { cycle_ops_csr_gs(h, l, b, xout, ops); return; }
   const DLevel& C = h->L[l + 1];
   const bool blk = L.WB.n > 0;
@@ -5873,6 +6123,12 @@ void launch(const Op& o, hipStream_t s) {
         patch_kernel<<<(unsigned)((o.n + 3) / 4), 256, 0, s>>>(o.r0, o.r1, o.lev->pperm, o.lev->Sptr, o.lev->Scol,
                                                                 o.lev->Sval, o.lev->pu, o.lev->pus, o.out, o.b, o.bs);
       break;
+    case OP_CRING:
+      if (o.n > 0)
+        ring_csr_kernel<<<(unsigned)o.n, RING_CSR_THREADS, 0, s>>>(o.r0, o.lev->rmo, o.lev->rmem, o.lev->rio,
+                                                                  o.lev->rinv, o.M->ptr, o.M->col, o.M->val, o.out,
+                                                                  o.b);
+      break;
     case OP_RING:
       if (o.n > 0)
         ring_kernel<<<(unsigned)o.n, RING_THREADS, 0, s>>>(o.r0, o.lev->rmo, o.lev->rmem, o.lev->rio, o.lev->rinv,
@@ -6177,7 +6433,8 @@ std::string layout_error(const mamg_params& p) {
   if (patch_schwarz(p))
     return "SCHWARZ_PATCHES needs the BSR2 layout (num_functions 2, node-block smoothers on every level)";
   if (rings_schwarz(p))
-    return "SCHWARZ_RINGS needs the BSR2 layout (num_functions 2, node-block smoothers on every level)";
+    return "SCHWARZ_RINGS with node-block smoothers needs the BSR2 layout (node-block smoothers on every level; "
+           "with node_block_smoother 0 it runs on the CSR layout)";
   return "multicolour GS/SGS smoothers need the BSR2 layout (num_functions 2, node-aligned smoother blocks)";
 }
 
@@ -6196,7 +6453,7 @@ int dev_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, Devi
   h->L.resize(nl);
   h->bsr = !point_gs(p) && bsr_eligible(H, A0, p);   // point-wise GS: the CSR layout, nodal hierarchies too
   read_knobs();
-  if ((gs_smoother(p) || patch_schwarz(p) || rings_schwarz(p)) && !h->bsr) {
+  if ((gs_smoother(p) || patch_schwarz(p) || (rings_schwarz(p) && !rings_csr(p))) && !h->bsr) {
     *err = layout_error(p);
     return MAMG_ERR_UNSUPPORTED;
   }
@@ -6248,7 +6505,10 @@ int dev_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, Devi
         if ((rc = dalloc(h.get(), &D.winv, D.n, err))) return rc;
         HIPCHK(hipMemcpy(D.winv, hl.winv.data(), D.n * sizeof(double), hipMemcpyHostToDevice));
       }
-      if (point_gs(p)) {
+      if (l == 0 && rings_schwarz(p) && !H.seeds.empty()) {   // seed rings + point GS on the rest
+        TmpPool T;
+        if ((rc = build_rings_csr(h.get(), &T, H.seeds, p.spmv_lanes, &D, err))) return rc;
+      } else if (point_gs(p)) {
         TmpPool T;
         if ((rc = build_gs_csr(h.get(), &T, D.A, l, p.spmv_lanes, &D, err))) return rc;
       }
@@ -6365,7 +6625,7 @@ int dev_from_ghier(GHier* G, const DevMat& A0, const mamg_params& p, DeviceHandl
   HIPCHK(hipStreamCreateWithFlags(&h->cap, hipStreamNonBlocking));
   read_knobs();
   h->bsr = !G->generic && !point_gs(p);   // a general block or point smoother: the CSR layout (as dev_upload)
-  if ((gs_smoother(p) || patch_schwarz(p) || rings_schwarz(p)) && !h->bsr) {
+  if ((gs_smoother(p) || patch_schwarz(p) || (rings_schwarz(p) && !rings_csr(p))) && !h->bsr) {
     *err = layout_error(p);
     return MAMG_ERR_UNSUPPORTED;
   }
@@ -6391,7 +6651,10 @@ int dev_from_ghier(GHier* G, const DevMat& A0, const mamg_params& p, DeviceHandl
           if ((rc = dalloc(h.get(), &D.winv, D.n, err))) return rc;
           HIPCHK(dev_copy(D.winv, g.winv, D.n * sizeof(double)));
         }
-        if (point_gs(p)) {
+        if (l == 0 && rings_schwarz(p) && !G->seeds.empty()) {   // seed rings + point GS on the rest
+          TmpPool T;
+          if ((rc = build_rings_csr(h.get(), &T, G->seeds, p.spmv_lanes, &D, err))) return rc;
+        } else if (point_gs(p)) {
           TmpPool T;
           if ((rc = build_gs_csr(h.get(), &T, D.A, l, p.spmv_lanes, &D, err))) return rc;
         }
@@ -8467,6 +8730,11 @@ int dev_rank_ops(DistHandle* h, const GHier& G, const DevMat& A0d, const DistPla
 int dist_check(const mamg_params& p, std::string* err) {
   if (p.maxit != 1) {
     *err = "multi-GPU apply supports maxit 1 (one cycle per application, src/amg_parameters.py:71)";
+    return MAMG_ERR_UNSUPPORTED;
+  }
+  if (rings_csr(p)) {
+    *err = "multi-GPU apply has no seed-ring Schwarz on scalar (CSR) hierarchies: SCHWARZ_RINGS runs on N GPUs "
+           "on nodal systems with node-block smoothers (num_functions 2, node_block_smoother 1)";
     return MAMG_ERR_UNSUPPORTED;
   }
   if (point_gs(p)) {

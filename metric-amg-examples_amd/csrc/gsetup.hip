@@ -2846,6 +2846,16 @@ int gpu_setup(const DevMat& A0, const int32_t* idofs, int64_t n_idofs, const mam
   int rc = check_params(p, err);
   if (rc) return rc;
   if ((rc = check_point_gs_seeds(p, idofs, n_idofs, err))) return rc;
+  if (rings_csr(p) && idofs && n_idofs > 0) {   // as host_setup: the Schwarz_levels 0 hierarchy, the seeds kept
+    if ((rc = check_ring_seeds(p, idofs, n_idofs, A0.n, err))) return rc;
+    mamg_params p0 = p;
+    p0.Schwarz_levels = 0;
+    rc = gpu_setup(A0, nullptr, 0, p0, G, err);
+    G->params = p;
+    if (point_gs(p)) G->params.node_block_smoother = 0;
+    if (rc == MAMG_OK) G->seeds.assign(idofs, idofs + n_idofs);
+    return rc;
+  }
   if (point_gs(p)) {   // as host_setup: the hierarchy of the point JACOBI_RHO smoother
     mamg_params pj = p;
     pj.smoother = MAMG_SMOOTHER_JACOBI_RHO;

@@ -75,6 +75,14 @@ int check_params(const mamg_params& p, std::string* err);
 inline bool point_gs(const mamg_params& p) {
   return p.smoother == MAMG_SMOOTHER_GS_POINT || p.smoother == MAMG_SMOOTHER_SGS_POINT;
 }
+// SCHWARZ_RINGS on a hierarchy that uploads in the CSR layout (a scalar
+// system, or a nodal one with point smoothers): the seed-ring blocks with
+// point-wise GS on the rest (device.hip build_rings_csr); the hierarchy is the
+// Schwarz_levels 0 one
+inline bool rings_csr(const mamg_params& p) {
+  return p.Schwarz_levels >= 1 && p.Schwarz_type == MAMG_SCHWARZ_RINGS &&
+         (p.num_functions != 2 || !p.node_block_smoother || point_gs(p));
+}
 int check_point_gs_seeds(const mamg_params& p, const int32_t* idofs, int64_t n_idofs, std::string* err);
 int check_patch_seeds(const mamg_params& p, const int32_t* idofs, int64_t n_idofs, int64_t n, std::string* err);
 int check_ring_seeds(const mamg_params& p, const int32_t* idofs, int64_t n_idofs, int64_t n, std::string* err);

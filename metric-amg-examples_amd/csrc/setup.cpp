@@ -1039,6 +1039,10 @@ mamg_params resolve_params(const mamg_params& in, const int32_t* idofs, int64_t 
   mamg_params p = in;
   if (point_gs(p)) p.node_block_smoother = 0;   // point sweeps on the CSR layout (nodal aggregation stays)
   if (p.Schwarz_levels < 1) return p;
+  if (rings_csr(p) && p.num_functions <= 2 && (!idofs || n_idofs <= 0)) {
+    p.Schwarz_levels = 0;   // seed rings without seeds: the level smoother everywhere (as the nodal form)
+    return p;
+  }
   if (p.Schwarz_type == MAMG_SCHWARZ_SYMMETRIC && p.Schwarz_maxlvl >= 1 && p.num_functions == 2 &&
       p.node_block_smoother) {
     if (!idofs || n_idofs <= 0) {
@@ -1067,6 +1071,7 @@ mamg_params resolve_like(const mamg_params& in, const mamg_params& built) {
     p.Schwarz_type = built.Schwarz_type;
     p.Schwarz_levels = built.Schwarz_levels;
   }
+  if (rings_csr(p) && built.Schwarz_levels < 1) p.Schwarz_levels = 0;   // built without seeds
   return p;
 }
 
@@ -1117,9 +1122,11 @@ int check_params(const mamg_params& p, std::string* err) {
         return MAMG_ERR_UNSUPPORTED;
       }
     } else if (t == MAMG_SCHWARZ_RINGS) {
-      if (p.num_functions != 2 || !p.node_block_smoother || p.Schwarz_maxlvl < 1) {
-        *err = "SCHWARZ_RINGS (multiplicative seed-ring Schwarz) needs num_functions 2, node_block_smoother 1 "
-               "and Schwarz_maxlvl >= 1";
+      // num_functions 2 with node-block smoothers: the BSR2 form (node-block GS
+      // on the rest); num_functions 1, or 2 with point smoothers: the CSR form
+      // (point-wise GS on the rest, any level smoother below)
+      if (p.num_functions > 2 || p.Schwarz_maxlvl < 1) {
+        *err = "SCHWARZ_RINGS (multiplicative seed-ring Schwarz) needs num_functions 1 or 2 and Schwarz_maxlvl >= 1";
         return MAMG_ERR_UNSUPPORTED;
       }
       if (p.Schwarz_mmsize > RING_MAX_DOFS) {
@@ -1132,8 +1139,9 @@ int check_params(const mamg_params& p, std::string* err) {
         *err = std::string("Schwarz_type ") + (t == MAMG_SCHWARZ_SYMMETRIC ? "SYMMETRIC" : t == MAMG_SCHWARZ_FORWARD ? "FORWARD" : "BACKWARD") +
                " with Schwarz_maxlvl " + std::to_string(p.Schwarz_maxlvl) +
                " is multiplicative Schwarz on overlapping seed + ring blocks; implemented as SYMMETRIC on nodal "
-               "systems (num_functions 2, node_block_smoother 1: SCHWARZ_PATCHES / SCHWARZ_RINGS). "
-               "Alternatives: SCHWARZ_ADDITIVE (the same overlapping blocks, additive) or SCHWARZ_SEED_BLOCKS "
+               "systems (num_functions 2, node_block_smoother 1: SCHWARZ_PATCHES / SCHWARZ_RINGS) and, named "
+               "explicitly, as SCHWARZ_RINGS on scalar systems (the symmetric seed-ring sweep with point-wise GS "
+               "on the rest). Alternatives: SCHWARZ_ADDITIVE (the same overlapping blocks, additive) or SCHWARZ_SEED_BLOCKS "
                "(non-overlapping blocks, the level smoother)";
         return MAMG_ERR_UNSUPPORTED;
       }
@@ -1214,7 +1222,9 @@ int check_ring_seeds(const mamg_params& p, const int32_t* idofs, int64_t n_idofs
 // seed blocks are refused
 int check_point_gs_seeds(const mamg_params& p, const int32_t* idofs, int64_t n_idofs, std::string* err) {
   if (!point_gs(p) || p.Schwarz_levels < 1 || !idofs || n_idofs <= 0) return MAMG_OK;
-  *err = "point-wise multicolour GS/SGS (SMOOTHER_GS_POINT / SGS_POINT) has no level-0 seed blocks. Alternatives: "
+  if (p.Schwarz_type == MAMG_SCHWARZ_RINGS) return MAMG_OK;   // the seed rings, point sweeps on the rest and below
+  *err = "point-wise multicolour GS/SGS (SMOOTHER_GS_POINT / SGS_POINT) has no level-0 seed blocks but the seed "
+         "rings' (SCHWARZ_RINGS). Alternatives: "
          "Schwarz_levels 0 (the point sweeps everywhere), the node-block SMOOTHER_GS / SGS with "
          "SCHWARZ_SEED_BLOCKS or SCHWARZ_SYMMETRIC (num_functions 2), or a Jacobi-family smoother with "
          "SCHWARZ_BLOCK_JACOBI / SCHWARZ_ADDITIVE";
@@ -1226,6 +1236,19 @@ int host_setup(const CsrView& A0, const int32_t* idofs, int64_t n_idofs,
   int rc = check_params(p, err);
   if (rc) return rc;
   if ((rc = check_point_gs_seeds(p, idofs, n_idofs, err))) return rc;
+  if (rings_csr(p) && idofs && n_idofs > 0) {
+    // seed rings on the CSR layout: the Schwarz_levels 0 hierarchy (no level-0
+    // WB); the blocks and the rest's sweeps are built with the apply layout
+    // (device.hip build_rings_csr) from the seeds kept here
+    if ((rc = check_ring_seeds(p, idofs, n_idofs, A0.n, err))) return rc;
+    mamg_params p0 = p;
+    p0.Schwarz_levels = 0;
+    rc = host_setup(A0, nullptr, 0, p0, H, err);
+    H->params = p;
+    if (point_gs(p)) H->params.node_block_smoother = 0;
+    if (rc == MAMG_OK) H->seeds.assign(idofs, idofs + n_idofs);
+    return rc;
+  }
   if (point_gs(p)) {   // the hierarchy of the point JACOBI_RHO smoother; the sweeps are built with the apply layout
     mamg_params pj = p;
     pj.smoother = MAMG_SMOOTHER_JACOBI_RHO;

@@ -5,6 +5,7 @@
     python -m metric_amg_examples_amd.drivers emi_3d1d -gamma 1e4 -radius 1.0 -dump 1 -outdir D/
     python -m metric_amg_examples_amd.drivers run_solver_3d1d -infile input_metric.dat -indir D/ -outdir O/
     torchrun --nproc-per-node 8 -m metric_amg_examples_amd.drivers emi_3d1d_sweep -n 48
+    python -m metric_amg_examples_amd.drivers emi_3d1d -gamma 1e4 -radius 1.0 -schwarz rings
 
 Each mirrors a reference script's CLI and output:
   bidomain_2d / bidomain_3d   src/bidomain_2d.py:105-278, src/bidomain_3d.py:52-220
@@ -35,6 +36,11 @@ Differences (stated, not hidden): the matrices come from the in-library
 generators (problems.py; FEniCS is absent); the EMI drivers' manufactured
 solutions are restated in mms.py (src/emi_2d.py:8-128); the 3D-1D neuron mesh
 is the synthetic ``problems.neuron_curve``.
+The 3D-1D drivers take ``-schwarz additive`` (default: the additive
+overlapping Schwarz on the 1-D seeds' 2-rings, parameters_metric_3d1d) or
+``-schwarz rings`` (the reference's symmetric multiplicative Schwarz on the
+same blocks, SCHWARZ_RINGS with point-wise GS on the rest; DESIGN.md section
+2.12.1).
 """
 from __future__ import annotations
 
@@ -45,7 +51,7 @@ import time
 
 import numpy as np
 
-from . import fileio, mms, parameters as P, problems
+from . import _lib, fileio, mms, parameters as P, problems
 from .amg import MetricAMG
 from .krylov import ConjGrad
 from .precond import (get_block_diag_precond, get_hazmath_amg_precond, get_hazmath_metric_precond,
@@ -252,14 +258,48 @@ def emi(argv, dim):
     return rows
 
 
-def emi_3d1d(argv):
+SCHWARZ_3D1D = ('additive', 'rings')
+_rings_fallback_printed = False
+
+
+def _params_3d1d(schwarz: str) -> dict:
+    return P.parameters_metric_3d1d_rings if schwarz == 'rings' else P.parameters_metric_3d1d
+
+
+def _metric_amg_3d1d(A, W, idofs, params, **kw):
+    """MetricAMG for the 3D-1D drivers.  Under the seed rings a point-GS level
+    smoother can meet a coarse level that needs more than 64 colours
+    (MAMG_ERR_UNSUPPORTED): the coarse levels then run Jacobi-rho under the
+    same rings, and the substitution is printed once."""
+    global _rings_fallback_printed
+    try:
+        return MetricAMG(A, W, idofs=idofs, parameters=params, **kw)
+    except _lib.MamgError as e:
+        if e.code != -4 or params.get('Schwarz_type') != P.SCHWARZ_RINGS or \
+                params.get('smoother') not in (P.SMOOTHER_GS_POINT, P.SMOOTHER_SGS_POINT):
+            raise
+        if not _rings_fallback_printed:
+            print('[mamg] parameter substitution: point-wise GS/SGS below the seed rings refused (%s) -> '
+                  'SMOOTHER_JACOBI_RHO (relaxation 4/3) on the coarse levels, the rings unchanged' % e, flush=True)
+            _rings_fallback_printed = True
+        return MetricAMG(A, W, idofs=idofs,
+                         parameters=dict(params, smoother=P.SMOOTHER_JACOBI_RHO, relaxation=4.0 / 3.0), **kw)
+
+
+def emi_3d1d_parser():
     ap = argparse.ArgumentParser(prog='emi_3d1d')
     ap.add_argument('-gamma', type=float, default=1)
     ap.add_argument('-dump', type=int, default=0, choices=(0, 1))
     ap.add_argument('-radius', type=float, default=1)
     ap.add_argument('-n', type=int, default=32, help='cells per direction of the tissue cube')
     ap.add_argument('-outdir', type=str, default='./data/emi_3d1d/')
-    args, _ = ap.parse_known_args(argv)
+    ap.add_argument('-schwarz', type=str, default='additive', choices=SCHWARZ_3D1D,
+                    help='level-0 Schwarz on the 1-D seeds\' 2-rings: additive, or the symmetric multiplicative rings')
+    return ap
+
+
+def emi_3d1d(argv):
+    args, _ = emi_3d1d_parser().parse_known_args(argv)
     t0 = time.time()
     s = problems.emi_3d1d(args.n, args.gamma, args.radius)
     print('System setup and assembly time: %.3f' % (time.time() - t0), flush=True)
@@ -269,26 +309,29 @@ def emi_3d1d(argv):
         fileio.dump_system(A, b, s.W, args.outdir)
         return None
     # alternative solver: the file-free path of solve_haznics (src/utils.py:95-127)
-    B = MetricAMG(A, s.W, idofs=s.idofs, parameters=P.parameters_metric_3d1d)
+    B = _metric_amg_3d1d(A, s.W, s.idofs, _params_3d1d(args.schwarz))
     solver = ConjGrad(A, precond=B, tolerance=1e-6, maxiter=1000, stop_type=1)
     solver * b
     print('niters %d' % (len(solver.residuals) - 1))
     return len(solver.residuals) - 1
 
 
-def fenics_metric_solver_xd_1d(sfile: str, mdir: str, odir: str, quiet: bool = False) -> int:
+def fenics_metric_solver_xd_1d(sfile: str, mdir: str, odir: str, quiet: bool = False,
+                               schwarz: str = 'additive') -> int:
     """HAZmath's file-based 3D-1D solve (haznics.fenics_metric_solver_xd_1d,
     called at src/run_solver_3d1d.py:38): parameters from the .dat file,
     A / b / idofs from mdir (utils.dump_system format), CG with the file's
     stopping rule, metric AMG seeded at the 1D dofs; writes odir/solution.txt.
+    schwarz 'rings': the file's multiplicative Schwarz and GS as the seed rings
+    and the point-wise GS (fileio.dat_to_parameters(multiplicative=True)).
     Returns the iteration count."""
     d = fileio.read_dat(sfile)
-    params, solver_prm, notes = fileio.dat_to_parameters(d)
+    params, solver_prm, notes = fileio.dat_to_parameters(d, multiplicative=schwarz == 'rings')
     A, b, idofs, idofs3d = fileio.load_system(mdir)
     N = A.shape[0]
     W = [N - len(idofs), len(idofs)] if idofs is not None else [N]
     t0 = time.time()
-    B = MetricAMG(A, W, idofs=idofs, parameters=params)
+    B = _metric_amg_3d1d(A, W, idofs, params)
     t1 = time.time()
     st = solver_prm['stop_type']
     cg = ConjGrad(A, precond=B, tolerance=solver_prm['tol'], maxiter=solver_prm['maxit'],
@@ -308,16 +351,21 @@ def fenics_metric_solver_xd_1d(sfile: str, mdir: str, odir: str, quiet: bool = F
     return niters
 
 
-def run_solver_3d1d(argv):
+def run_solver_3d1d_parser():
     ap = argparse.ArgumentParser(prog='run_solver_3d1d')
     ap.add_argument('-infile', type=str, default='./src/input_metric.dat')
     ap.add_argument('-indir', type=str, default='./data/emi_3d1d/')
     ap.add_argument('-outdir', type=str, default='./results/emi_3d1d/')
-    args, _ = ap.parse_known_args(argv)
+    ap.add_argument('-schwarz', type=str, default='additive', choices=SCHWARZ_3D1D)
+    return ap
+
+
+def run_solver_3d1d(argv):
+    args, _ = run_solver_3d1d_parser().parse_known_args(argv)
     if not os.path.exists(args.infile) or not os.path.exists(args.indir):
         raise SystemExit('input file or matrix directory missing')
     return fenics_metric_solver_xd_1d(os.path.abspath(args.infile), os.path.abspath(args.indir) + '/',
-                                      os.path.abspath(args.outdir) + '/')
+                                      os.path.abspath(args.outdir) + '/', schwarz=args.schwarz)
 
 
 # ---- the 3D-1D sweep (BASELINE config 5) on N GPUs --------------------------
@@ -355,7 +403,7 @@ def solve_3d1d_unit(n: int, radius: float, gamma: float, params=None, device=Non
     b = problems.seeded_rhs(s.N)
     t0 = time.time()
     kw = {} if device is None else dict(device=device)
-    B = MetricAMG(A, s.W, idofs=s.idofs, parameters=params or P.parameters_metric_3d1d, **kw)
+    B = _metric_amg_3d1d(A, s.W, s.idofs, params or P.parameters_metric_3d1d, **kw)
     cg = ConjGrad(A, precond=B, tolerance=tol, maxiter=maxiter, stop_type=1)
     x = cg * b
     dt = time.time() - t0
@@ -386,13 +434,18 @@ def run_sweep(units, solve, rank: int = 0, world: int = 1, gather=None):
     return [r for _, r in rows], wall, max(w for _, w in parts)
 
 
-def emi_3d1d_sweep(argv):
+def emi_3d1d_sweep_parser():
     ap = argparse.ArgumentParser(prog='emi_3d1d_sweep')
     ap.add_argument('-n', type=int, default=48, help='cells per direction of the tissue cube')
     ap.add_argument('-radii', type=str, default=','.join(map(str, SWEEP_RADII)))
     ap.add_argument('-gammas', type=str, default=','.join('%g' % g for g in SWEEP_GAMMAS))
     ap.add_argument('-results', type=str, default='./results')
-    args, _ = ap.parse_known_args(argv)
+    ap.add_argument('-schwarz', type=str, default='additive', choices=SCHWARZ_3D1D)
+    return ap
+
+
+def emi_3d1d_sweep(argv):
+    args, _ = emi_3d1d_sweep_parser().parse_known_args(argv)
     import json
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -412,12 +465,13 @@ def emi_3d1d_sweep(argv):
             dist.all_gather_object(out, obj)
             return out
     units = sweep_units([float(v) for v in args.radii.split(',')], [float(v) for v in args.gammas.split(',')])
-    rows, _, wall = run_sweep(units, lambda u: solve_3d1d_unit(args.n, u[0], u[1], device=device),
+    rows, _, wall = run_sweep(units, lambda u: solve_3d1d_unit(args.n, u[0], u[1], params=_params_3d1d(args.schwarz),
+                                                               device=device),
                               rank, world, gather)
     if rank == 0:
         rdir = os.path.join(args.results, 'emi_3d1d')
         os.makedirs(rdir, exist_ok=True)
-        path = os.path.join(rdir, 'iters_sweep_n%d.txt' % args.n)
+        path = os.path.join(rdir, 'iters_sweep_n%d%s.txt' % (args.n, '' if args.schwarz == 'additive' else '_rings'))
         for k, r in enumerate(rows):
             _append(path, [r[h] for h in HEADERS_SWEEP], k == 0, HEADERS_SWEEP)
             print('emi_3d1d radius=%g gamma=%g ndofs=%d niters=%d timeKSP=%.3fs relres=%.2e (rank %d)'

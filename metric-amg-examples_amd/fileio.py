@@ -95,10 +95,16 @@ _SMOOTHER = {'JACOBI': P.SMOOTHER_JACOBI, 'L1DIAG': P.SMOOTHER_L1DIAG, 'GS': P.S
 _AGG = {1: P.VMB, 2: P.MIS, 3: P.MWM, 4: P.HEC, 5: P.HEM}
 
 
-def dat_to_parameters(d: dict):
+def dat_to_parameters(d: dict, multiplicative: bool = False):
     """HAZmath .dat keys -> (parameter dict with src/amg_parameters.py key
     names, solver dict, substitution notes).  The solver dict carries
-    linear_itsolver_type / _maxit / _tol / linear_stop_type / precond type."""
+    linear_itsolver_type / _maxit / _tol / linear_stop_type / precond type.
+
+    multiplicative=False (default): the file's multiplicative Schwarz runs as
+    SCHWARZ_ADDITIVE on the same blocks and GS / SGS as SMOOTHER_JACOBI_RHO.
+    multiplicative=True: the file's symmetric multiplicative Schwarz runs as
+    SCHWARZ_RINGS on the same blocks (point-wise GS on the dofs in no block)
+    and GS / SGS as SMOOTHER_GS_POINT / SGS_POINT; relaxation does not enter."""
     notes = []
     prm = {}
     word = lambda k, table, default: table[str(d.get(k, default)).upper()] \
@@ -135,6 +141,52 @@ def dat_to_parameters(d: dict):
     if 'AMG_aggregation_type' in d:
         prm['aggregation_type'] = _AGG.get(int(d['AMG_aggregation_type']), P.VMB)
     maxlvl = prm.get('Schwarz_maxlvl', 1)
+    if multiplicative:
+        mapped, n2 = _multiplicative_profile(prm, maxlvl, notes)
+    else:
+        mapped, n2 = _additive_profile(prm, maxlvl, notes)
+    solver = {'type': int(d.get('linear_itsolver_type', 1)),
+              'maxit': int(d.get('linear_itsolver_maxit', 500)),
+              'tol': float(d.get('linear_itsolver_tol', 1e-6)),
+              'stop_type': int(d.get('linear_stop_type', 1)),
+              'precond_type': int(d.get('linear_precond_type', 16))}
+    if solver['type'] != 1:
+        raise ValueError('linear_itsolver_type %d: only 1 (CG) is implemented' % solver['type'])
+    if solver['stop_type'] not in (1, 2):
+        raise ValueError('linear_stop_type %d: only 1 (||r||/||b||) and 2 (||r||_B/||b||_B)'
+                         % solver['stop_type'])
+    return mapped, solver, notes + n2
+
+
+def _multiplicative_profile(prm: dict, maxlvl: int, notes: list):
+    """the file's own smoothers: the seed rings (SCHWARZ_RINGS on the CSR
+    layout) and the point-wise multicolour GS / SGS"""
+    prm = dict(prm)
+    point = {P.SMOOTHER_GS: P.SMOOTHER_GS_POINT, P.SMOOTHER_SGS: P.SMOOTHER_SGS_POINT}
+    if prm.get('smoother') in point:
+        notes.append('smoother GS/SGS -> SMOOTHER_GS_POINT / SGS_POINT (point-wise sweeps in a multicolour order '
+                     "instead of HAZmath's sequential dof order; relaxation does not enter)")
+        prm['smoother'] = point[prm['smoother']]
+    st = prm.get('Schwarz_type')
+    seeds = prm.get('Schwarz_levels', 0) >= 1 and maxlvl >= 1
+    if seeds and st in (P.SCHWARZ_FORWARD, P.SCHWARZ_BACKWARD):
+        raise ValueError('Schwarz_type %r: forward-only / backward-only multiplicative Schwarz is not implemented '
+                         '(multiplicative=False maps it to SCHWARZ_ADDITIVE)' % st)
+    mapped, n2 = P.to_gpu_profile(prm)
+    if seeds:
+        n2 = [m for m in n2 if not m.startswith('Schwarz_maxlvl') and not m.startswith('Schwarz_type')]
+        notes.append('Schwarz_type %r (symmetric multiplicative) -> SCHWARZ_RINGS on the same seed + %d-ring '
+                     "blocks: colour order instead of HAZmath's sequential seed and dof order, point-wise GS on "
+                     'the dofs in no block' % (st, maxlvl))
+        mapped['Schwarz_levels'] = 1
+        mapped['Schwarz_maxlvl'] = maxlvl
+        mapped['Schwarz_type'] = P.SCHWARZ_RINGS
+    if prm.get('num_functions') is None:
+        mapped.pop('num_functions', None)
+    return mapped, n2
+
+
+def _additive_profile(prm: dict, maxlvl: int, notes: list):
     mapped, n2 = P.to_gpu_profile(prm)
     # the file-based 3D-1D solve seeds the sparse 1-D dofs: HAZmath's
     # multiplicative Schwarz on their maxlvl-rings becomes the additive
@@ -161,17 +213,7 @@ def dat_to_parameters(d: dict):
         mapped['relaxation'] = 4.0 / 3.0
         notes.append('relaxation %s -> 4/3 (weight of the relaxation/rho Jacobi smoother)'
                      % prm.get('relaxation', 1.0))
-    solver = {'type': int(d.get('linear_itsolver_type', 1)),
-              'maxit': int(d.get('linear_itsolver_maxit', 500)),
-              'tol': float(d.get('linear_itsolver_tol', 1e-6)),
-              'stop_type': int(d.get('linear_stop_type', 1)),
-              'precond_type': int(d.get('linear_precond_type', 16))}
-    if solver['type'] != 1:
-        raise ValueError('linear_itsolver_type %d: only 1 (CG) is implemented' % solver['type'])
-    if solver['stop_type'] not in (1, 2):
-        raise ValueError('linear_stop_type %d: only 1 (||r||/||b||) and 2 (||r||_B/||b||_B)'
-                         % solver['stop_type'])
-    return mapped, solver, notes + n2
+    return mapped, n2
 
 
 def write_solution(path: str, x: np.ndarray) -> None:

@@ -70,7 +70,9 @@ SCHWARZ_PATCHES = 6           # the reference's overlapping seed + 1-ring blocks
 SCHWARZ_SEED_BLOCKS = 7       # the level smoother on non-overlapping seed blocks (seed + joined non-seeds)
 SCHWARZ_RINGS = 8             # the reference's overlapping seed + Schwarz_maxlvl-ring blocks, symmetric
                               # multiplicative (one block per seed, greedy conflict colours) + node-block GS
-                              # on the dofs in no block (level 0, nodal; sparse seed sets such as EMI's)
+                              # on the dofs in no block (level 0, nodal; sparse seed sets such as EMI's);
+                              # named explicitly on a scalar system (or with point smoothers): point-wise GS
+                              # on the rest, the level smoother below (the 3D-1D system)
 OFF, ON = 0, 1
 STRENGTH_DIAG, STRENGTH_ROWMAX = 0, 1   # strength_measure: classical theta sqrt(|a_ii a_jj|) | row maximum (default)
 SOLVER_UMFPACK = 32          # coarse_solver / Schwarz_blksolver: dense direct here
@@ -124,6 +126,12 @@ parameters_metric_mi355x_poly = dict(
 parameters_metric_3d1d = dict(
     parameters_metric_mi355x, num_functions=1, Schwarz_type=SCHWARZ_ADDITIVE, Schwarz_maxlvl=2,
     Schwarz_mmsize=200, coarse_dof=300, max_levels=30)
+
+# the same with the reference's own level-0 smoother there (src/utils.py:84):
+# symmetric multiplicative Schwarz on those blocks in a conflict-colour order
+# and point-wise GS on the dofs in no block (SCHWARZ_RINGS on the CSR layout;
+# drivers: -schwarz rings)
+parameters_metric_3d1d_rings = dict(parameters_metric_3d1d, Schwarz_type=SCHWARZ_RINGS)
 
 # the reference's smoothers on the GPU: multicolour
 # node-block SGS (level 0: the same SGS order on the non-overlapping seed
