@@ -55,16 +55,9 @@ def eq_csr(e, M):
             and np.array_equal(e[2], M.data))
 
 
-@pytest.mark.parametrize('dim,n,g,kw', CASES)
-def test_bitwise_hierarchy(lib_built, dim, n, g, kw):
-    import metric_amg_examples_amd as M
-    s = M.problems.bidomain(dim, n, g)
-    o = mo.bidomain_system(dim, n, g)
-    A = s.scipy()
-    assert np.array_equal(A.indptr, o['A'].indptr) and np.array_equal(A.indices, o['A'].indices)
-    assert np.array_equal(A.data, o['A'].data)                 # generator bitwise
-    H = M.HostHierarchy(s, idofs=s.idofs, **to_c(kw))
-    h = mo.setup(o['A'], mo.Params(**kw), idofs=o['idofs'])
+def assert_equals_oracle(H, h):
+    """HostHierarchy H against the oracle's Hierarchy h, bit for bit, level by
+    level (shared with tests/test_irregular_host.py)."""
     assert H.num_levels == len(h.levels)
     for l, lv in enumerate(h.levels):
         ex = H.level(l)
@@ -79,6 +72,19 @@ def test_bitwise_hierarchy(lib_built, dim, n, g, kw):
             assert eq_csr(ex['WB'], lv.WB), 'WB level %d' % l
         else:
             assert np.array_equal(ex['winv'], lv.winv), 'winv level %d' % l
+
+
+@pytest.mark.parametrize('dim,n,g,kw', CASES)
+def test_bitwise_hierarchy(lib_built, dim, n, g, kw):
+    import metric_amg_examples_amd as M
+    s = M.problems.bidomain(dim, n, g)
+    o = mo.bidomain_system(dim, n, g)
+    A = s.scipy()
+    assert np.array_equal(A.indptr, o['A'].indptr) and np.array_equal(A.indices, o['A'].indices)
+    assert np.array_equal(A.data, o['A'].data)                 # generator bitwise
+    H = M.HostHierarchy(s, idofs=s.idofs, **to_c(kw))
+    h = mo.setup(o['A'], mo.Params(**kw), idofs=o['idofs'])
+    assert_equals_oracle(H, h)
 
 
 def test_no_idofs_and_scipy_input(lib_built):
