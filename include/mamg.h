@@ -275,8 +275,16 @@ int mamg_hier_level_export(const mamg_hier* h, int l,
 
 /* ---- multi-GPU partition plan (host only) --------- */
 /* Rank `rank` of `nranks`: contiguous node ranges per level, ghost lists,
- * send lists, rank-local BSR2 matrices.  Levels with <= rep_nodes nodes (and
- * all coarser ones) are replicated. */
+ * send lists, rank-local matrices.  Levels with <= rep_nodes nodes (and all
+ * coarser ones) are replicated.  A nodal hierarchy (num_functions 2,
+ * node-block smoothers) gives a BSR2 plan: a node is a pair of dofs, the
+ * matrices are 2x2-block.  A scalar hierarchy (num_functions 1) gives a CSR
+ * plan: a node is a dof, the matrices are CSR with
+ * columns numbered [owned | ghost] and every row sorted by local column, the
+ * smoother is the slice of winv or, on level 0 with seed blocks, the owned
+ * rows of WB (whose external columns are ghosts too).  num_functions > 2,
+ * num_functions 2 with node_block_smoother 0, point-wise GS / SGS and
+ * SCHWARZ_RINGS on CSR hierarchies return MAMG_ERR_UNSUPPORTED. */
 typedef struct mamg_plan mamg_plan;
 int mamg_hier_dist_plan(const mamg_hier* h, int rank, int nranks, int64_t rep_nodes,
                         mamg_plan** out);
@@ -287,12 +295,20 @@ int mamg_plan_num_levels(const mamg_plan* p);
 int mamg_plan_level_sizes(const mamg_plan* p, int l, int64_t* s);
 /* Export (any pointer may be NULL): ghosts[nghost], ghost_off[nranks+1],
  * send_idx[nsend], send_off[nranks+1], A/P/Rp as BSR2 (ptr, col, val[4 nb]),
- * W[4 nloc]. */
+ * W[4 nloc].  Scalar plan: nb counts entries, A/P/Rp are CSR (val[nb]) and
+ * W[nloc] = winv (untouched where the level smooths with WB). */
 int mamg_plan_level_export(const mamg_plan* p, int l, int64_t* ghosts, int64_t* ghost_off,
                            int64_t* send_idx, int64_t* send_off,
                            int64_t* Aptr, int32_t* Acol, double* Aval,
                            int64_t* Pptr, int32_t* Pcol, double* Pval,
                            int64_t* Rptr, int32_t* Rcol, double* Rval, double* W);
+/* dofs per node of the plan: 2 (BSR2 plan) or 1 (scalar CSR plan) */
+int mamg_plan_dofs_per_node(const mamg_plan* p);
+/* Scalar plan: the owned rows of the level's sparse block smoother WB, columns
+ * local [owned | ghost] (any pointer may be NULL).  sizes[3] = entries, rows,
+ * columns (zeros where the level smooths with winv); ptr[rows + 1],
+ * col[entries], val[entries]. */
+int mamg_plan_level_wb(const mamg_plan* p, int l, int64_t* sizes, int64_t* ptr, int32_t* col, double* val);
 
 /* ---- multi-GPU apply (one process per GPU, RCCL over xGMI) ------------- */
 typedef struct mamg_dhandle mamg_dhandle;
@@ -303,10 +319,20 @@ int mamg_comm_unique_id(void* id);
  * rank's GPU where the profile allows it, else on the host -- is replicated
  * and deterministic) and keeps only its node range of each level; levels
  * with <= rep_nodes nodes are replicated.  V and W cycles, coarse-grid
- * scaling, nu1 / nu2 >= 1; Jacobi-family, POLY and multicolour GS / SGS
- * smoothers on BSR2 (nodal) hierarchies.  SCHWARZ_PATCHES / SCHWARZ_RINGS,
- * CSR-layout hierarchies (SCHWARZ_RINGS on them included) and maxit > 1
- * return MAMG_ERR_UNSUPPORTED. */
+ * scaling, nu1 / nu2 >= 1.
+ *  - Nodal hierarchies (num_functions 2, node-block smoothers, BSR2 layout):
+ *    Jacobi-family, POLY and multicolour GS / SGS smoothers, SCHWARZ_PATCHES
+ *    and SCHWARZ_RINGS (the latter three with a GPU-setup profile).
+ *  - Scalar hierarchies (num_functions 1, CSR layout):
+ *    SMOOTHER_JACOBI / L1DIAG / JACOBI_RHO / POLY and the level-0 sparse block
+ *    smoother of the seeds (SCHWARZ_ADDITIVE / BLOCK_JACOBI / SEED_BLOCKS with
+ *    Schwarz_maxlvl >= 1), e.g. the 3D-1D preset.  Every rank runs the host
+ *    setup and plans the whole hierarchy on the host (O(global nnz) host work
+ *    per rank).  Local vectors are the plain slices r[o0:o1], z[o0:o1].
+ * MAMG_ERR_UNSUPPORTED, the message naming the alternative: point-wise GS /
+ * SGS, SCHWARZ_RINGS on CSR hierarchies, num_functions 2 with
+ * node_block_smoother 0 (a nodal hierarchy in the CSR layout), num_functions
+ * > 2, maxit > 1. */
 int mamg_setup_dist(const mamg_csr* A, const int32_t* idofs, int64_t n_idofs,
                     const mamg_params* params, int rank, int nranks, const void* comm_id,
                     int64_t rep_nodes, mamg_dhandle** out);
@@ -314,13 +340,23 @@ int mamg_setup_dist(const mamg_csr* A, const int32_t* idofs, int64_t n_idofs,
  * setup only), e.g. from mamg_gen_bidomain_device: no rank holds the global
  * matrix on the host.  Covers the GPU setup's node-block profiles (the rank's
  * operators are cut out of the hierarchy in HBM); profiles that plan on the
- * host return MAMG_ERR_UNSUPPORTED. */
+ * host (scalar hierarchies among them) return MAMG_ERR_UNSUPPORTED. */
 int mamg_setup_dist_device(const mamg_csr* dA, const int32_t* idofs, int64_t n_idofs,
                            const mamg_params* params, int rank, int nranks, const void* comm_id,
                            int64_t rep_nodes, mamg_dhandle** out);
-/* local node range [o0, o1) of level 0; local vectors are field-major
- * [u1(o0:o1); u2(o0:o1)] of length 2*(o1-o0) */
+/* local node range [o0, o1) of level 0 and the level's nodes nv; local vectors
+ * are field-major [u1(o0:o1); u2(o0:o1)] of length 2*(o1-o0) on a nodal
+ * handle, the plain slice v[o0:o1] on a scalar one (nv = rows) */
 int mamg_dist_range(const mamg_dhandle* h, int64_t* o0, int64_t* o1, int64_t* nv);
+/* dofs per node of the handle: 2 (nodal, BSR2) or 1 (scalar, CSR) */
+int mamg_dist_dofs_per_node(const mamg_dhandle* h);
+/* algorithmic bytes of one apply on this rank: the sum over its op list.
+ * Kernels as mamg_apply_bytes counts them on the rank-local operators (CSR:
+ * 12 nnz + 8 (rows + 1) + 8 columns + 8 rows, + 8 rows per extra vector of the
+ * epilogue).  Exchanges, with w = dofs per node, ns = send-list nodes, ng =
+ * ghosts: forward halo 8 ns (indices) + 2 * 8 w ns (pack) + 8 w ng (ghost
+ * writes); reverse-add 8 w ng + 3 * 8 w ns + 8 ns; all-reduce of a replicated
+ * right-hand side 2 * 8 w nv; of the scaling partials 16 * 256. */
 int mamg_dist_apply_bytes(const mamg_dhandle* h, double* bytes);
 /* what one mamg_dist_apply_device issues on this rank (counted from its op
  * list, nothing launched): counts[0] kernels, [1] RCCL send / receive groups,
@@ -342,8 +378,8 @@ int mamg_dist_apply_graph(mamg_dhandle* h, const double* d_r_local, double* d_z_
  * and agree on the outcome before any rank launches a graph whose RCCL calls
  * wait for its peers. */
 int mamg_dist_graph_prepare(mamg_dhandle* h, const double* d_r_local, double* d_z_local);
-/* y = A x on the rank's rows (the PCG operator; x, y local field-major
- * slices): forward halo of x, then the rank-local A.  Replaces the A * d
+/* y = A x on the rank's rows (the PCG operator; x, y local slices as for the
+ * apply): forward halo of x, then the rank-local A.  Replaces the A * d
  * product inside cbc.block ConjGrad (src/bidomain_3d.py:149) on N GPUs. */
 int mamg_dist_spmv_device(mamg_dhandle* h, const double* d_x_local, double* d_y_local, void* stream);
 /* mode 0: eager, events around the level-0 residual and K launches; 1:

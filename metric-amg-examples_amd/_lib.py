@@ -96,6 +96,9 @@ SIGNATURES = {
     'mamg_plan_level_sizes': (C.c_int, [VP, C.c_int, P_I64]),
     'mamg_plan_level_export': (C.c_int, [VP, C.c_int, P_I64, P_I64, P_I64, P_I64]
                                + [P_I64, P_I32, P_F64] * 3 + [P_F64]),
+    'mamg_plan_dofs_per_node': (C.c_int, [VP]),
+    'mamg_plan_level_wb': (C.c_int, [VP, C.c_int, P_I64, P_I64, P_I32, P_F64]),
+    'mamg_dist_dofs_per_node': (C.c_int, [VP]),
     'mamg_comm_id_bytes': (C.c_int, []),
     'mamg_comm_unique_id': (C.c_int, [C.c_char_p]),
     'mamg_setup_dist': (C.c_int, [C.POINTER(mamg_csr), P_I32, C.c_int64, C.POINTER(mamg_params),

@@ -433,7 +433,8 @@ class HostHierarchy:
 
 class DistPlan:
     """Rank-local partition plan of the multi-GPU V-cycle (``mamg_hier_dist_plan``):
-    node ranges, ghost / send lists and rank-local 2x2-block matrices per level."""
+    node ranges, ghost / send lists and rank-local matrices per level -- 2x2-block
+    (BSR2) for a nodal hierarchy, CSR for a scalar one (``dofs_per_node`` 2 / 1)."""
 
     def __init__(self, H: HostHierarchy, rank: int, nranks: int, rep_nodes: int = 32768):
         self._L = _lib.lib()
@@ -447,7 +448,16 @@ class DistPlan:
     def num_levels(self):
         return self._L.mamg_plan_num_levels(self._h)
 
+    @property
+    def dofs_per_node(self):
+        return self._L.mamg_plan_dofs_per_node(self._h)
+
     def level(self, l):
+        """dict of the level's ranges, lists and matrices.  BSR2 plan: A / P /
+        R = (ptr, col, val[nb, 2, 2], nr, nc), W[nloc, 2, 2].  Scalar plan: A /
+        P / R (and WB where the level smooths with the seed blocks) = (ptr,
+        col, val[nnz], nr, nc) with local columns [owned | ghost], else
+        winv[nloc]."""
         s = (C.c_int64 * 16)()
         _lib.check(self._L.mamg_plan_level_sizes(self._h, l, s))
         (nv, rep, coarsest, o0, o1, ng, ns, nbA, nrA, ncA, nbP, nrP, ncP, nbR, nrR, ncR) = list(s)
@@ -456,13 +466,19 @@ class DistPlan:
                    nloc=o1 - o0, ghosts=np.zeros(ng, np.int64), ghost_off=np.zeros(nr + 1, np.int64),
                    send_idx=np.zeros(ns, np.int64), send_off=np.zeros(nr + 1, np.int64))
 
+        scalar = self.dofs_per_node == 1
+        bw = 1 if scalar else 4
+
         def alloc(nb, nrows):
-            return (np.zeros(nrows + 1, np.int64), np.zeros(nb, np.int32), np.zeros(4 * nb))
+            return (np.zeros(nrows + 1, np.int64), np.zeros(nb, np.int32), np.zeros(bw * nb))
 
         A = alloc(nbA, nrA)
         P = alloc(nbP, nrP) if nrP else (None, None, None)
         R = alloc(nbR, nrR) if nrR else (None, None, None)
-        W = np.zeros(4 * (o1 - o0)) if not coarsest else None
+        wb = (C.c_int64 * 3)()
+        if scalar:
+            _lib.check(self._L.mamg_plan_level_wb(self._h, l, wb, None, None, None))
+        W = np.zeros(bw * (o1 - o0)) if not coarsest and not wb[1] else None
 
         def p(a, t):
             return None if a is None else _lib.ptr(a, t)
@@ -474,6 +490,19 @@ class DistPlan:
             self._h, l, p(out['ghosts'], C.c_int64), p(out['ghost_off'], C.c_int64),
             p(out['send_idx'], C.c_int64), p(out['send_off'], C.c_int64), *args,
             p(W, C.c_double)))
+        if scalar:
+            out['A'] = A + (nrA, ncA)
+            if nrP:
+                out['P'] = P + (nrP, ncP)
+                out['R'] = R + (nrR, ncR)
+            if wb[1]:
+                B = alloc(wb[0], wb[1])
+                _lib.check(self._L.mamg_plan_level_wb(self._h, l, None, p(B[0], C.c_int64), p(B[1], C.c_int32),
+                                                      p(B[2], C.c_double)))
+                out['WB'] = B + (wb[1], wb[2])
+            if W is not None:
+                out['winv'] = W
+            return out
         out['A'] = (A[0], A[1], A[2].reshape(-1, 2, 2), nrA, ncA)
         if nrP:
             out['P'] = (P[0], P[1], P[2].reshape(-1, 2, 2), nrP, ncP)
@@ -533,7 +562,10 @@ class DistMetricAMG:
     replicated) -- a host CSR, or a tuple of CUDA tensors already in HBM
     (``problems.bidomain_device``: no rank then holds the global matrix on the
     host, ``mamg_setup_dist_device``) -- and applies B to its local slice r_local = [u1(o0:o1);
-    u2(o0:o1)] (field-major, length 2*(o1-o0)).  comm_id: bytes from
+    u2(o0:o1)] (field-major, length 2*(o1-o0)).  A scalar profile (num_functions 1: CSR
+    hierarchy, Jacobi-family / POLY smoothers, the additive seed blocks; the 3D-1D preset)
+    partitions the rows themselves: ``dofs_per_node`` is 1, ``nv`` the row count and the local
+    slice the plain r[o0:o1]; it takes a host matrix only.  comm_id: bytes from
     ``DistMetricAMG.unique_id()`` on rank 0, broadcast to all ranks; None
     builds a virtual (single-GPU, no RCCL) rank for tests."""
 
@@ -571,6 +603,7 @@ class DistMetricAMG:
         o0, o1, nv = C.c_int64(), C.c_int64(), C.c_int64()
         _lib.check(self._L.mamg_dist_range(h, C.byref(o0), C.byref(o1), C.byref(nv)))
         self.o0, self.o1, self.nv = o0.value, o1.value, nv.value
+        self.dofs_per_node = self._L.mamg_dist_dofs_per_node(h)
 
     def set_exchange(self, exchange):
         """Host-staged transport (mamg_dist_set_exchange): 'gloo' = the
@@ -621,7 +654,14 @@ class DistMetricAMG:
     def nloc(self):
         return self.o1 - self.o0
 
+    @property
+    def local_size(self):
+        """length of this rank's local vectors"""
+        return self.dofs_per_node * (self.o1 - self.o0)
+
     def local_slice(self, v):
+        if self.dofs_per_node == 1:
+            return v[self.o0:self.o1]
         return np.concatenate([v[self.o0:self.o1], v[self.nv + self.o0:self.nv + self.o1]])
 
     @property

@@ -403,6 +403,14 @@ int mamg_plan_num_levels(const mamg_plan* p) { return p ? (int)p->P.levels.size(
 int mamg_plan_level_sizes(const mamg_plan* p, int l, int64_t* s) {
   if (!p || l < 0 || l >= (int)p->P.levels.size() || !s) { set_error("bad level"); return MAMG_ERR_ARG; }
   const mamg::DistLevel& D = p->P.levels[l];
+  if (p->P.dofs == 1) {   // scalar plan: entry counts
+    const int64_t v[16] = {D.nv, D.replicated, D.coarsest, D.o0, D.o1, (int64_t)D.ghosts.size(),
+                           (int64_t)D.send_idx.size(),
+                           D.cA.nnz(), D.cA.n, D.cA.m, D.cP.nnz(), D.cP.n, D.cP.m,
+                           D.cRp.nnz(), D.cRp.n, D.cRp.m};
+    std::memcpy(s, v, sizeof(v));
+    return MAMG_OK;
+  }
   const int64_t v[16] = {D.nv, D.replicated, D.coarsest, D.o0, D.o1, (int64_t)D.ghosts.size(),
                          (int64_t)D.send_idx.size(),
                          D.A.ptr.empty() ? 0 : D.A.ptr[D.A.nr], D.A.nr, D.A.nc,
@@ -425,10 +433,32 @@ int mamg_plan_level_export(const mamg_plan* p, int l, int64_t* ghosts, int64_t* 
   cpv(ghost_off, D.ghost_off);
   cpv(send_idx, D.send_idx);
   cpv(send_off, D.send_off);
+  if (p->P.dofs == 1) {
+    cpv(Aptr, D.cA.ptr); cpv(Acol, D.cA.col); cpv(Aval, D.cA.val);
+    cpv(Pptr, D.cP.ptr); cpv(Pcol, D.cP.col); cpv(Pval, D.cP.val);
+    cpv(Rptr, D.cRp.ptr); cpv(Rcol, D.cRp.col); cpv(Rval, D.cRp.val);
+    cpv(W, D.W);
+    return MAMG_OK;
+  }
   cpv(Aptr, D.A.ptr); cpv(Acol, D.A.col); cpv(Aval, D.A.val);
   cpv(Pptr, D.P.ptr); cpv(Pcol, D.P.col); cpv(Pval, D.P.val);
   cpv(Rptr, D.Rp.ptr); cpv(Rcol, D.Rp.col); cpv(Rval, D.Rp.val);
   cpv(W, D.W);
+  return MAMG_OK;
+}
+
+int mamg_plan_dofs_per_node(const mamg_plan* p) {
+  if (!p) { set_error("null plan"); return MAMG_ERR_ARG; }
+  return p->P.dofs;
+}
+
+int mamg_plan_level_wb(const mamg_plan* p, int l, int64_t* sizes, int64_t* ptr, int32_t* col, double* val) {
+  if (!p || l < 0 || l >= (int)p->P.levels.size()) { set_error("bad level"); return MAMG_ERR_ARG; }
+  const mamg::Csr& B = p->P.levels[l].cWB;
+  if (sizes) { sizes[0] = B.nnz(); sizes[1] = B.n; sizes[2] = B.m; }
+  if (ptr && !B.ptr.empty()) std::memcpy(ptr, B.ptr.data(), B.ptr.size() * sizeof(int64_t));
+  if (col && !B.col.empty()) std::memcpy(col, B.col.data(), B.col.size() * sizeof(int32_t));
+  if (val && !B.val.empty()) std::memcpy(val, B.val.data(), B.val.size() * sizeof(double));
   return MAMG_OK;
 }
 
@@ -521,6 +551,11 @@ int setup_dist_impl(const mamg::CsrView& v, const mamg::DevMat* devA, const int3
     lap(on_device ? "ghost lists" : "hierarchy download");
     if (rc && rc != MAMG_ERR_UNSUPPORTED) { mamg::dev_prereserve_release(); set_error(err); return rc; }
   }
+  if (rc == MAMG_ERR_UNSUPPORTED && devA && P.num_functions == 1) {
+    set_error("multi-GPU setup from a device A_0: scalar (num_functions 1, CSR layout) hierarchies plan on the "
+              "host from the host matrix; pass the host CSR (mamg_setup_dist)");
+    return MAMG_ERR_UNSUPPORTED;
+  }
   if (rc == MAMG_ERR_UNSUPPORTED && devA) {
     mamg::dev_prereserve_release();
     set_error("multi-GPU setup from a device A_0 needs the GPU setup's profiles (num_functions 2, node-block "
@@ -595,6 +630,11 @@ int mamg_dist_range(const mamg_dhandle* h, int64_t* o0, int64_t* o1, int64_t* nv
   if (!h || !o0 || !o1 || !nv) { set_error("null argument"); return MAMG_ERR_ARG; }
   mamg::dist_range(h->d, o0, o1, nv);
   return MAMG_OK;
+}
+
+int mamg_dist_dofs_per_node(const mamg_dhandle* h) {
+  if (!h) { set_error("null handle"); return MAMG_ERR_ARG; }
+  return mamg::dist_dofs(h->d);
 }
 
 int mamg_dist_apply_bytes(const mamg_dhandle* h, double* bytes) {

@@ -66,6 +66,8 @@ int dist_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, int
                 const GHier* G = nullptr, const DevMat* A0d = nullptr);
 void dist_destroy(DistHandle* h);
 void dist_range(const DistHandle* h, int64_t* o0, int64_t* o1, int64_t* nv);
+// dofs per node: 2 nodal (BSR2; local vectors field-major), 1 scalar (CSR; plain slices)
+int dist_dofs(const DistHandle* h);
 double dist_apply_bytes(const DistHandle* h);
 void dist_apply_launches(const DistHandle* h, int64_t c[5]);
 int dist_apply(DistHandle* h, const double* d_r, double* d_z, void* stream, std::string* err);

@@ -134,12 +134,14 @@ constexpr int SCALE_BLOCKS = 256;   // partial-sum blocks of the coarse-scaling 
 // ---------------------------------------------------------------------------
 template <int VL, int EPI, int TAG>
 __global__ __launch_bounds__(256) void csr_kernel(
-    int64_t n, const int64_t* __restrict__ ptr, const int32_t* __restrict__ col,
+    int64_t r0, int64_t n, const int64_t* __restrict__ ptr, const int32_t* __restrict__ col,
     const double* __restrict__ val, const double* __restrict__ x,
     const double* y, const double* __restrict__ b, const double* __restrict__ w,
     double* out) {
+  // rows [r0, n): r0 > 0 for the multi-GPU rank-local A's row ranges (interior
+  // rows during the halo); a row's sum does not depend on where the launch starts
   const int lane = threadIdx.x & (VL - 1);
-  const int64_t row = ((int64_t)blockIdx.x * 256 + threadIdx.x) / VL;
+  const int64_t row = r0 + ((int64_t)blockIdx.x * 256 + threadIdx.x) / VL;
   double s0 = 0.0, s1 = 0.0;
   if (row < n) {
     const int64_t p0 = ptr[row], p1 = ptr[row + 1];
@@ -2947,7 +2949,8 @@ enum OpKind { OP_CSR = 0, OP_SCALE = 1, OP_GEMV = 2, OP_AXPY = 3, OP_BSR = 4, OP
               OP_GS = 8, OP_ZERO = 9, OP_DOT2 = 10, OP_CSCALE = 11, OP_PATCH = 12, OP_TAIL = 13, OP_RING = 14,
               OP_CGS = 15,     // point-wise GS, one colour of a CSR level (csr_gs_kernel)
               OP_CGSF = 16,    // point-wise GS, a small level's whole smoothing call (csr_gs_small_kernel)
-              OP_CRING = 17 }; // one colour of a seed-ring sweep on the CSR layout (ring_csr_kernel)
+              OP_CRING = 17,   // one colour of a seed-ring sweep on the CSR layout (ring_csr_kernel)
+              OP_COPY = 18 };  // out = x (n doubles): a rank's plain slice into its [owned | ghost] buffer
 // kernel classes (kernel_ms / class_bytes slots)
 enum Cls {
   C_L0_RESID = 0,   // dominant: r = b - A0 x (once per apply)
@@ -5782,20 +5785,21 @@ Op a0_op(const DeviceHandle* h, int epi, const double* x, const double* b, doubl
 template <int VL, int TAG>
 void launch_csr_vl(const Op& o, hipStream_t s) {
   const DCsr& M = *o.M;
-  const unsigned g = nblocks(M.n * (int64_t)VL);
-  if (g == 0) return;
+  const int64_t r0 = o.r1 >= 0 ? o.r0 : 0, r1 = o.r1 >= 0 ? o.r1 : M.n;   // row range (multi-GPU), else all rows
+  if (r1 <= r0) return;
+  const unsigned g = nblocks((r1 - r0) * (int64_t)VL);
   switch (o.epi) {
     case EPI_Y:
-      csr_kernel<VL, EPI_Y, TAG><<<g, 256, 0, s>>>(M.n, M.ptr, M.col, M.val, o.x, o.y, o.b, o.w, o.out);
+      csr_kernel<VL, EPI_Y, TAG><<<g, 256, 0, s>>>(r0, r1, M.ptr, M.col, M.val, o.x, o.y, o.b, o.w, o.out);
       break;
     case EPI_YADD:
-      csr_kernel<VL, EPI_YADD, TAG><<<g, 256, 0, s>>>(M.n, M.ptr, M.col, M.val, o.x, o.y, o.b, o.w, o.out);
+      csr_kernel<VL, EPI_YADD, TAG><<<g, 256, 0, s>>>(r0, r1, M.ptr, M.col, M.val, o.x, o.y, o.b, o.w, o.out);
       break;
     case EPI_RESID:
-      csr_kernel<VL, EPI_RESID, TAG><<<g, 256, 0, s>>>(M.n, M.ptr, M.col, M.val, o.x, o.y, o.b, o.w, o.out);
+      csr_kernel<VL, EPI_RESID, TAG><<<g, 256, 0, s>>>(r0, r1, M.ptr, M.col, M.val, o.x, o.y, o.b, o.w, o.out);
       break;
     default:
-      csr_kernel<VL, EPI_JACOBI, TAG><<<g, 256, 0, s>>>(M.n, M.ptr, M.col, M.val, o.x, o.y, o.b, o.w, o.out);
+      csr_kernel<VL, EPI_JACOBI, TAG><<<g, 256, 0, s>>>(r0, r1, M.ptr, M.col, M.val, o.x, o.y, o.b, o.w, o.out);
       break;
   }
 }
@@ -6136,6 +6140,9 @@ void launch(const Op& o, hipStream_t s) {
       break;
     case OP_ZERO:
       if (o.n) (void)dev_memset(o.out, 0, o.n * sizeof(double), s);
+      break;
+    case OP_COPY:
+      if (o.n) (void)dev_copy(o.out, o.x, o.n * sizeof(double), s);
       break;
     case OP_DOT2:
       if (o.n) dot2_partial_kernel<<<SCALE_BLOCKS, 256, 0, s>>>(o.n, o.b, o.x, o.y, o.part);
@@ -7220,10 +7227,58 @@ __global__ __launch_bounds__(256) void addidx2_kernel(int64_t n, const int64_t* 
   }
 }
 
+// width 1 (scalar CSR hierarchies: a node is a dof).  The buffer side is
+// contiguous in k, the indexed side one 8-byte access per thread.
+__global__ __launch_bounds__(256) void pack1_kernel(int64_t n, const int64_t* __restrict__ idx,
+                                                    const double* __restrict__ x,
+                                                    double* __restrict__ buf) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k < n) buf[k] = x[idx[k]];
+}
+
+__global__ __launch_bounds__(256) void unpack1_kernel(int64_t n, const int64_t* __restrict__ idx, int64_t nloc,
+                                                      const double* __restrict__ buf, double* x) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k < n) x[nloc + idx[k]] = buf[k];
+}
+
+// idx holds distinct owned rows (one peer's send list): no two threads share a target
+__global__ __launch_bounds__(256) void addidx1_kernel(int64_t n, const int64_t* __restrict__ idx,
+                                                      const double* __restrict__ buf, double* x) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k < n) {
+    const int64_t i = idx[k];
+    x[i] = x[i] + buf[k];
+  }
+}
+
+// the exchange kernels of a handle with w dofs per node (2: the double2
+// kernels of the nodal path, 1: the scalar ones)
+inline void pack_w(int w, int64_t n, const int64_t* idx, const double* x, double* buf, hipStream_t s) {
+  if (w == 2) pack2_kernel<<<nblocks(n), 256, 0, s>>>(n, idx, x, buf);
+  else pack1_kernel<<<nblocks(n), 256, 0, s>>>(n, idx, x, buf);
+}
+inline void unpack_w(int w, int64_t n, const int64_t* idx, int64_t nloc, const double* buf, double* x, hipStream_t s) {
+  if (w == 2) unpack2_kernel<<<nblocks(n), 256, 0, s>>>(n, idx, nloc, buf, x);
+  else unpack1_kernel<<<nblocks(n), 256, 0, s>>>(n, idx, nloc, buf, x);
+}
+inline void addidx_w(int w, int64_t n, const int64_t* idx, const double* buf, double* x, hipStream_t s) {
+  if (w == 2) addidx2_kernel<<<nblocks(n), 256, 0, s>>>(n, idx, buf, x);
+  else addidx1_kernel<<<nblocks(n), 256, 0, s>>>(n, idx, buf, x);
+}
+
 struct DDLevel {
   int64_t nv = 0, nloc = 0, ng = 0;
   bool replicated = false, coarsest = false;
   DBsr A, P, R;
+  // scalar (CSR) level: A_loc, P_loc, Rp_loc, on level 0 with seed blocks the
+  // owned rows of WB (else the winv slice); POLY: the step smoothers w_k WB
+  // (sharing WB's pattern) or w_k winv; vectors hold nloc + ng doubles
+  DCsr cA, cP, cR, cWB;
+  std::vector<DCsr> cWBk;
+  double* winv = nullptr;
+  std::vector<double*> winvk;
+  double* gb = nullptr;    // level 0 with WB: b over [owned | ghost] (X = WB_loc b reads b's ghosts)
   DBsr PA;                 // post fusion: merged [P_loc | AP_loc]
   DBsr K;                  // post fusion: K_loc = P_loc - W (AP)_loc (default)
   dv4* W = nullptr;
@@ -7287,6 +7342,7 @@ struct DOp {
 struct DistHandle {
   mamg_params p;
   int rank = 0, nranks = 1, device = 0;
+  int w = 2;                           // dofs per node: 2 nodal (BSR2), 1 scalar (CSR)
   ncclComm_t comm = nullptr;
   std::vector<DDLevel> L;
   std::vector<void*> allocs;
@@ -7660,6 +7716,154 @@ void dcycle_rings(const DistHandle* h, const double* b, int64_t bs, double* xout
   ops->push_back(wrap(o));
 }
 
+// ---- scalar (CSR) hierarchies on N ranks: cycle_ops_csr restated with
+// exchanges.  Vectors are [owned | ghost] doubles;
+// every rank emits the same schedule whatever it owns.
+DOp halo_op1(int level, double* x, const DDLevel& D, int cls) {
+  DOp d;
+  d.dk = D_HALO; d.level = level; d.buf = x; d.cls = cls;
+  const int64_t ns = D.send_off.empty() ? 0 : D.send_off.back();
+  d.bytes = 8.0 * ns + 8.0 * ns * 2 + 8.0 * D.ng;   // idx, pack r/w, ghost writes
+  return d;
+}
+
+// forward halo of x, then the SpMV `op` on the rank-local operator.  With
+// `split` (the level-0 residual and the standalone SpMV) the longest run of
+// rows without ghost columns [ib0, ib1) (maybe empty) runs on the side stream
+// while the halo is in flight (one D_OVERLAP) and the rest after it; the same
+// kernel computes every row either way (same bits).
+void halo_csr(const DistHandle* h, int l, double* x, const Op& op, bool split, std::vector<DOp>* ops) {
+  const DDLevel& D = h->L[l];
+  if (D.replicated) { ops->push_back(wrap(op)); return; }
+  if (!(split && h->overlap)) {
+    ops->push_back(halo_op1(l, x, D, C_COMM));
+    ops->push_back(wrap(op));
+    return;
+  }
+  const double n = (double)std::max<int64_t>(D.nloc, 1);
+  DOp ov = halo_op1(l, x, D, op.cls);   // timed and counted with the SpMV's class
+  ov.dk = D_OVERLAP;
+  ov.op = op;
+  ov.op.r0 = D.ib0;
+  ov.op.r1 = D.ib1;
+  ov.op.bytes = op.bytes * (double)(D.ib1 - D.ib0) / n;
+  ov.bytes += ov.op.bytes;
+  ops->push_back(ov);
+  const int64_t lo[2] = {0, D.ib1}, hi[2] = {D.ib0, D.nloc};
+  for (int k = 0; k < 2; ++k) {   // both always emitted (possibly empty): one schedule on every rank
+    Op b = op;
+    b.r0 = lo[k];
+    b.r1 = hi[k];
+    b.bytes = op.bytes * (double)std::max<int64_t>(hi[k] - lo[k], 0) / n;
+    ops->push_back(wrap(b));
+  }
+}
+
+void dcycle_csr(const DistHandle* h, int l, const double* b, double* xout, std::vector<DOp>* ops);
+
+// as dscale_ops: the dots over the owned rows, the scale over [owned | ghost]
+void dscale_csr(const DistHandle* h, int lc, std::vector<DOp>* ops) {
+  const DDLevel& C = h->L[lc];
+  halo_csr(h, lc, C.x, csr_op(C.cA, EPI_Y, C_MISC, 1, C.x, nullptr, nullptr, nullptr, C.q), false, ops);
+  Op d;
+  d.kind = OP_DOT2; d.cls = C_MISC; d.n = C.nloc; d.b = C.b; d.x = C.x; d.y = C.q; d.part = C.part2;
+  d.bytes = 24.0 * d.n;
+  ops->push_back(wrap(d));
+  if (!C.replicated) {
+    DOp a;
+    a.dk = D_ALLREDUCE; a.cls = C_COMM; a.buf = C.part2; a.count = 2 * SCALE_BLOCKS; a.bytes = 16.0 * SCALE_BLOCKS;
+    ops->push_back(a);
+  }
+  Op sc;
+  sc.kind = OP_CSCALE; sc.cls = C_MISC; sc.n = C.nloc + C.ng; sc.part = C.part2; sc.out = C.x;
+  sc.bytes = 16.0 * sc.n;
+  ops->push_back(wrap(sc));
+}
+
+// one smoothing step of a scalar level from the iterate X (not the first from
+// x = 0): halo of X, then x + w_s winv (b - A X) in one pass, or with the
+// sparse block smoother r = b - A X, halo of r, x + w_s WB_loc r
+void dsmooth_csr(const DistHandle* h, int l, const double* b, double* X, double* out, int s, bool pre,
+                 std::vector<DOp>* ops) {
+  const DDLevel& D = h->L[l];
+  const bool l0 = l == 0;
+  const int tagA = l0 ? 0 : 1, clsS = l0 ? C_L0_SMOOTH : C_COARSE, clsW = l0 ? C_L0_WB : C_COARSE;
+  const int m = smoother_steps(h->p);
+  if (D.cWB.n > 0) {
+    const DCsr& wb = D.cWBk.empty() ? D.cWB : D.cWBk[step_index(m, s, pre)];
+    halo_csr(h, l, X, csr_op(D.cA, EPI_RESID, clsS, tagA, X, nullptr, b, nullptr, D.r), false, ops);
+    halo_csr(h, l, D.r, csr_op(wb, EPI_YADD, clsW, tagA, D.r, X, nullptr, nullptr, out), false, ops);
+  } else {
+    const double* wv = D.winvk.empty() ? D.winv : D.winvk[step_index(m, s, pre)];
+    halo_csr(h, l, X, csr_op(D.cA, EPI_JACOBI, clsS, tagA, X, X, b, wv, out), false, ops);
+  }
+}
+
+void dcycle_csr(const DistHandle* h, int l, const double* b, double* xout, std::vector<DOp>* ops) {
+  const DDLevel& D = h->L[l];
+  const mamg_params& p = h->p;
+  const bool l0 = l == 0;
+  if (D.coarsest) {
+    Op o;
+    o.kind = OP_GEMV; o.cls = C_DENSE; o.n = D.nv; o.x = b; o.w = D.Ainv; o.out = xout;
+    o.bytes = 8.0 * o.n * o.n + 16.0 * o.n;
+    ops->push_back(wrap(o));
+    return;
+  }
+  const DDLevel& C = h->L[l + 1];
+  const int tagA = l0 ? 0 : 1, clsW = l0 ? C_L0_WB : C_COARSE;
+  const int m = smoother_steps(p);
+  const int npre = p.presmooth_iter * m, npost = p.postsmooth_iter * m;
+  double* X = D.t;
+  double* X2 = D.t2;
+  if (D.cWB.n > 0) {   // X = WB_loc b: b's ghosts first (b copied into its [owned | ghost] buffer)
+    const DCsr& wb = D.cWBk.empty() ? D.cWB : D.cWBk[step_index(m, 0, true)];
+    Op c;
+    c.kind = OP_COPY; c.cls = clsW; c.n = D.nloc; c.x = b; c.out = D.gb; c.bytes = 16.0 * D.nloc;
+    ops->push_back(wrap(c));
+    halo_csr(h, l, D.gb, csr_op(wb, EPI_Y, clsW, tagA, D.gb, nullptr, nullptr, nullptr, X), false, ops);
+  } else {
+    Op o;
+    o.kind = OP_SCALE; o.cls = clsW; o.n = D.nloc; o.w = D.winvk.empty() ? D.winv : D.winvk[step_index(m, 0, true)];
+    o.x = b; o.out = X; o.bytes = 24.0 * D.nloc;
+    ops->push_back(wrap(o));
+  }
+  for (int s = 1; s < npre; ++s) {
+    dsmooth_csr(h, l, b, X, X2, s, true, ops);
+    std::swap(X, X2);
+  }
+  halo_csr(h, l, X, csr_op(D.cA, EPI_RESID, l0 ? C_L0_RESID : C_COARSE, tagA, X, nullptr, b, nullptr, D.r), l0, ops);
+  // partial restriction, then the ghost partials to their owners (added in
+  // rank order) or the sum over the ranks into a replicated level
+  ops->push_back(wrap(csr_op(D.cR, EPI_Y, l0 ? C_L0_R : C_COARSE, tagA, D.r, nullptr, nullptr, nullptr, C.b)));
+  if (!D.replicated) {
+    DOp d;
+    d.cls = C_COMM;
+    if (C.replicated) {
+      d.dk = D_ALLREDUCE; d.buf = C.b; d.count = C.nv; d.bytes = 16.0 * C.nv;
+    } else {
+      d.dk = D_REVERSE; d.level = l + 1; d.buf = C.b;
+      const int64_t ns = C.send_off.back();
+      d.bytes = 8.0 * C.ng + 8.0 * ns * 3 + 8.0 * ns;
+    }
+    ops->push_back(d);
+  }
+  dcycle_csr(h, l + 1, C.b, C.x, ops);
+  if (p.cycle_type == MAMG_W_CYCLE && !C.coarsest) {   // second visit on the updated residual
+    halo_csr(h, l + 1, C.x, csr_op(C.cA, EPI_RESID, C_MISC, 1, C.x, nullptr, C.b, nullptr, C.c), false, ops);
+    dcycle_csr(h, l + 1, C.c, C.e, ops);
+    ops->push_back(wrap(axpy_op(C.nloc, C.e, C.x)));
+  }
+  if (p.coarse_scaling) dscale_csr(h, l + 1, ops);      // ghosts of C.x scaled too
+  else if (!C.replicated) ops->push_back(halo_op1(l + 1, C.x, C, C_COMM));
+  ops->push_back(wrap(csr_op(D.cP, EPI_YADD, l0 ? C_L0_P : C_COARSE, tagA, C.x, X, nullptr, nullptr, X)));
+  for (int s = 0; s < npost; ++s) {
+    double* out = s == npost - 1 ? xout : X2;
+    dsmooth_csr(h, l, b, X, out, s, false, ops);
+    if (out == X2) std::swap(X, X2);
+  }
+}
+
 // multi-GPU cycle from x = 0 (V or W, nu1 / nu2 sweeps, optional coarse-grid
 // scaling): see dist.cpp / dist_ref.py
 void dcycle_ops(const DistHandle* h, int l, const double* b, int64_t bs, double* xout, int64_t os,
@@ -7739,7 +7943,7 @@ void dcycle_ops(const DistHandle* h, int l, const double* b, int64_t bs, double*
 // memory around the callback (stream synchronised first), the same pack /
 // unpack / rank-ordered reverse-add kernels as the RCCL branch of run_dop
 int run_dop_host(DistHandle* h, const DOp& d, hipStream_t s, std::string* err) {
-  const int P = h->nranks;
+  const int P = h->nranks, w = h->w;
   std::vector<double*> snd(P, nullptr), rcv(P, nullptr);
   std::vector<int64_t> sc(P, 0), rc(P, 0);
   if (d.dk == D_ALLREDUCE) {
@@ -7770,12 +7974,12 @@ int run_dop_host(DistHandle* h, const DOp& d, hipStream_t s, std::string* err) {
     const int64_t s0 = D.cs_off[b0], s1 = D.cs_off[b0 + P], g0 = D.cg_off[b0], g1 = D.cg_off[b0 + P];
     for (int q = 0; q < P; ++q) {
       if (q == h->rank) continue;
-      snd[q] = hs + 2 * D.cs_off[b0 + q]; sc[q] = 2 * (D.cs_off[b0 + q + 1] - D.cs_off[b0 + q]);
-      rcv[q] = hg + 2 * D.cg_off[b0 + q]; rc[q] = 2 * (D.cg_off[b0 + q + 1] - D.cg_off[b0 + q]);
+      snd[q] = hs + w * D.cs_off[b0 + q]; sc[q] = w * (D.cs_off[b0 + q + 1] - D.cs_off[b0 + q]);
+      rcv[q] = hg + w * D.cg_off[b0 + q]; rc[q] = w * (D.cg_off[b0 + q + 1] - D.cg_off[b0 + q]);
     }
     if (s1 > s0) {
-      pack2_kernel<<<nblocks(s1 - s0), 256, 0, s>>>(s1 - s0, D.csend_idx + s0, d.buf, D.sendbuf + 2 * s0);
-      HIPCHK(hipMemcpyAsync(hs + 2 * s0, D.sendbuf + 2 * s0, 2 * (s1 - s0) * sizeof(double), hipMemcpyDeviceToHost, s));
+      pack_w(w, s1 - s0, D.csend_idx + s0, d.buf, D.sendbuf + w * s0, s);
+      HIPCHK(hipMemcpyAsync(hs + w * s0, D.sendbuf + w * s0, w * (s1 - s0) * sizeof(double), hipMemcpyDeviceToHost, s));
     }
     HIPCHK(hipStreamSynchronize(s));
     if (h->ex.sendrecv(h->ex.ctx, P, snd.data(), sc.data(), rcv.data(), rc.data())) {
@@ -7783,8 +7987,8 @@ int run_dop_host(DistHandle* h, const DOp& d, hipStream_t s, std::string* err) {
       return MAMG_ERR_HIP;
     }
     if (g1 > g0) {
-      HIPCHK(hipMemcpyAsync(D.recvbuf + 2 * g0, hg + 2 * g0, 2 * (g1 - g0) * sizeof(double), hipMemcpyHostToDevice, s));
-      unpack2_kernel<<<nblocks(g1 - g0), 256, 0, s>>>(g1 - g0, D.cghost_idx + g0, D.nloc, D.recvbuf + 2 * g0, d.buf);
+      HIPCHK(hipMemcpyAsync(D.recvbuf + w * g0, hg + w * g0, w * (g1 - g0) * sizeof(double), hipMemcpyHostToDevice, s));
+      unpack_w(w, g1 - g0, D.cghost_idx + g0, D.nloc, D.recvbuf + w * g0, d.buf, s);
     }
     return MAMG_OK;
   }
@@ -7792,17 +7996,17 @@ int run_dop_host(DistHandle* h, const DOp& d, hipStream_t s, std::string* err) {
     if (q == h->rank) continue;
     const int64_t sq = D.send_off[q + 1] - D.send_off[q], gq = D.ghost_off[q + 1] - D.ghost_off[q];
     if (d.dk == D_HALO) {   // my owned values they ghost -> their ghosts of mine
-      snd[q] = hs + 2 * D.send_off[q]; sc[q] = 2 * sq;
-      rcv[q] = hg + 2 * D.ghost_off[q]; rc[q] = 2 * gq;
+      snd[q] = hs + w * D.send_off[q]; sc[q] = w * sq;
+      rcv[q] = hg + w * D.ghost_off[q]; rc[q] = w * gq;
     } else {                // D_REVERSE: my ghost partials -> their owned rows
-      snd[q] = hg + 2 * D.ghost_off[q]; sc[q] = 2 * gq;
-      rcv[q] = hr + 2 * D.send_off[q]; rc[q] = 2 * sq;
+      snd[q] = hg + w * D.ghost_off[q]; sc[q] = w * gq;
+      rcv[q] = hr + w * D.send_off[q]; rc[q] = w * sq;
     }
   }
   if (d.dk == D_HALO) {
     if (ns) {
-      pack2_kernel<<<nblocks(ns), 256, 0, s>>>(ns, D.send_idx, d.buf, D.sendbuf);
-      HIPCHK(hipMemcpyAsync(hs, D.sendbuf, 2 * ns * sizeof(double), hipMemcpyDeviceToHost, s));
+      pack_w(w, ns, D.send_idx, d.buf, D.sendbuf, s);
+      HIPCHK(hipMemcpyAsync(hs, D.sendbuf, w * ns * sizeof(double), hipMemcpyDeviceToHost, s));
     }
     HIPCHK(hipStreamSynchronize(s));
     if (h->ex.sendrecv(h->ex.ctx, P, snd.data(), sc.data(), rcv.data(), rc.data())) {
@@ -7810,21 +8014,21 @@ int run_dop_host(DistHandle* h, const DOp& d, hipStream_t s, std::string* err) {
       return MAMG_ERR_HIP;
     }
     if (D.ng)
-      HIPCHK(hipMemcpyAsync(d.buf + 2 * D.nloc, hg, 2 * D.ng * sizeof(double), hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(d.buf + w * D.nloc, hg, w * D.ng * sizeof(double), hipMemcpyHostToDevice, s));
     return MAMG_OK;
   }
   // D_REVERSE
-  if (D.ng) HIPCHK(hipMemcpyAsync(hg, d.buf + 2 * D.nloc, 2 * D.ng * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (D.ng) HIPCHK(hipMemcpyAsync(hg, d.buf + w * D.nloc, w * D.ng * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   if (h->ex.sendrecv(h->ex.ctx, P, snd.data(), sc.data(), rcv.data(), rc.data())) {
     *err = "exchange sendrecv callback failed";
     return MAMG_ERR_HIP;
   }
-  if (ns) HIPCHK(hipMemcpyAsync(D.recvbuf, hr, 2 * ns * sizeof(double), hipMemcpyHostToDevice, s));
+  if (ns) HIPCHK(hipMemcpyAsync(D.recvbuf, hr, w * ns * sizeof(double), hipMemcpyHostToDevice, s));
   for (int q = 0; q < P; ++q) {
     const int64_t sq = D.send_off[q + 1] - D.send_off[q];
     if (q == h->rank || !sq) continue;
-    addidx2_kernel<<<nblocks(sq), 256, 0, s>>>(sq, D.send_idx + D.send_off[q], D.recvbuf + 2 * D.send_off[q], d.buf);
+    addidx_w(w, sq, D.send_idx + D.send_off[q], D.recvbuf + w * D.send_off[q], d.buf, s);
   }
   return MAMG_OK;
 }
@@ -7834,6 +8038,7 @@ int run_dop(DistHandle* h, const DOp& d, hipStream_t s, std::string* err) {
     launch(d.op, s);
     return MAMG_OK;
   }
+  const int w = h->w;
   if (h->nranks == 1 && !h->comm) {     // no peers: halos empty, sums over one rank
     if (d.dk == D_OVERLAP) launch(d.op, s);
     return MAMG_OK;
@@ -7871,27 +8076,27 @@ int run_dop(DistHandle* h, const DOp& d, hipStream_t s, std::string* err) {
     const int P = h->nranks;
     const size_t b0 = (size_t)d.colour * (P + 1);
     const int64_t s0 = D.cs_off[b0], s1 = D.cs_off[b0 + P], g0 = D.cg_off[b0], g1 = D.cg_off[b0 + P];
-    if (s1 > s0) pack2_kernel<<<nblocks(s1 - s0), 256, 0, s>>>(s1 - s0, D.csend_idx + s0, d.buf, D.sendbuf + 2 * s0);
+    if (s1 > s0) pack_w(w, s1 - s0, D.csend_idx + s0, d.buf, D.sendbuf + w * s0, s);
     NCCLCHK(ncclGroupStart());
     for (int q = 0; q < P; ++q) {
       if (q == h->rank) continue;
       const int64_t sc = D.cs_off[b0 + q + 1] - D.cs_off[b0 + q], gc = D.cg_off[b0 + q + 1] - D.cg_off[b0 + q];
-      if (sc) NCCLCHK(ncclSend(D.sendbuf + 2 * D.cs_off[b0 + q], 2 * sc, ncclDouble, q, h->comm, s));
-      if (gc) NCCLCHK(ncclRecv(D.recvbuf + 2 * D.cg_off[b0 + q], 2 * gc, ncclDouble, q, h->comm, s));
+      if (sc) NCCLCHK(ncclSend(D.sendbuf + w * D.cs_off[b0 + q], w * sc, ncclDouble, q, h->comm, s));
+      if (gc) NCCLCHK(ncclRecv(D.recvbuf + w * D.cg_off[b0 + q], w * gc, ncclDouble, q, h->comm, s));
     }
     NCCLCHK(ncclGroupEnd());
-    if (g1 > g0) unpack2_kernel<<<nblocks(g1 - g0), 256, 0, s>>>(g1 - g0, D.cghost_idx + g0, D.nloc, D.recvbuf + 2 * g0, d.buf);
+    if (g1 > g0) unpack_w(w, g1 - g0, D.cghost_idx + g0, D.nloc, D.recvbuf + w * g0, d.buf, s);
     return MAMG_OK;
   }
   if (d.dk == D_HALO) {
-    if (ns) pack2_kernel<<<nblocks(ns), 256, 0, s>>>(ns, D.send_idx, d.buf, D.sendbuf);
+    if (ns) pack_w(w, ns, D.send_idx, d.buf, D.sendbuf, s);
     NCCLCHK(ncclGroupStart());
     for (int q = 0; q < h->nranks; ++q) {
       if (q == h->rank) continue;
       const int64_t sc = D.send_off[q + 1] - D.send_off[q];
       const int64_t gc = D.ghost_off[q + 1] - D.ghost_off[q];
-      if (sc) NCCLCHK(ncclSend(D.sendbuf + 2 * D.send_off[q], 2 * sc, ncclDouble, q, h->comm, s));
-      if (gc) NCCLCHK(ncclRecv(d.buf + 2 * (D.nloc + D.ghost_off[q]), 2 * gc, ncclDouble, q, h->comm, s));
+      if (sc) NCCLCHK(ncclSend(D.sendbuf + w * D.send_off[q], w * sc, ncclDouble, q, h->comm, s));
+      if (gc) NCCLCHK(ncclRecv(d.buf + w * (D.nloc + D.ghost_off[q]), w * gc, ncclDouble, q, h->comm, s));
     }
     NCCLCHK(ncclGroupEnd());
     return MAMG_OK;
@@ -7902,15 +8107,14 @@ int run_dop(DistHandle* h, const DOp& d, hipStream_t s, std::string* err) {
     if (q == h->rank) continue;
     const int64_t sc = D.send_off[q + 1] - D.send_off[q];
     const int64_t gc = D.ghost_off[q + 1] - D.ghost_off[q];
-    if (gc) NCCLCHK(ncclSend(d.buf + 2 * (D.nloc + D.ghost_off[q]), 2 * gc, ncclDouble, q, h->comm, s));
-    if (sc) NCCLCHK(ncclRecv(D.recvbuf + 2 * D.send_off[q], 2 * sc, ncclDouble, q, h->comm, s));
+    if (gc) NCCLCHK(ncclSend(d.buf + w * (D.nloc + D.ghost_off[q]), w * gc, ncclDouble, q, h->comm, s));
+    if (sc) NCCLCHK(ncclRecv(D.recvbuf + w * D.send_off[q], w * sc, ncclDouble, q, h->comm, s));
   }
   NCCLCHK(ncclGroupEnd());
   for (int q = 0; q < h->nranks; ++q) {
     const int64_t sc = D.send_off[q + 1] - D.send_off[q];
     if (q == h->rank || !sc) continue;
-    addidx2_kernel<<<nblocks(sc), 256, 0, s>>>(sc, D.send_idx + D.send_off[q],
-                                               D.recvbuf + 2 * D.send_off[q], d.buf);
+    addidx_w(w, sc, D.send_idx + D.send_off[q], D.recvbuf + w * D.send_off[q], d.buf, s);
   }
   return MAMG_OK;
 }
@@ -7918,6 +8122,7 @@ int run_dop(DistHandle* h, const DOp& d, hipStream_t s, std::string* err) {
 void dapply_ops(const DistHandle* h, const double* r, double* z, std::vector<DOp>* ops) {
   ops->clear();
   const int64_t nloc = h->L[0].nloc;
+  if (h->w == 1) { dcycle_csr(h, 0, r, z, ops); return; }   // scalar: the rank's plain slices
   dcycle_ops(h, 0, r, nloc, z, nloc, ops);
 }
 
@@ -7926,6 +8131,13 @@ void dapply_ops(const DistHandle* h, const double* r, double* z, std::vector<DOp
 void dspmv_ops(const DistHandle* h, const double* x, double* y, std::vector<DOp>* ops) {
   ops->clear();
   const DDLevel& D = h->L[0];
+  if (h->w == 1) {   // scalar: x copied into the [owned | ghost] buffer, halo, A_loc (interior rows meanwhile)
+    Op c;
+    c.kind = OP_COPY; c.cls = C_MISC; c.n = D.nloc; c.x = x; c.out = D.spx; c.bytes = 16.0 * D.nloc;
+    ops->push_back(wrap(c));
+    halo_csr(h, 0, D.spx, csr_op(D.cA, EPI_Y, C_L0_RESID, 0, D.spx, nullptr, nullptr, nullptr, y), true, ops);
+    return;
+  }
   Op o;
   o.kind = OP_ILV; o.cls = C_MISC; o.n = D.nloc; o.b = x; o.bs = D.nloc; o.out = D.spx;
   o.bytes = 32.0 * D.nloc;
@@ -8725,6 +8937,81 @@ int dev_rank_ops(DistHandle* h, const GHier& G, const DevMat& A0d, const DistPla
   return MAMG_OK;
 }
 
+int upload_dcsr(DistHandle* h, const Csr& M, DCsr* D, int lanes, std::string* err) {
+  D->n = M.n;
+  D->m = M.m;
+  D->nnz = M.nnz();
+  D->lanes = lanes > 0 ? lanes : pick_lanes(M.n, D->nnz);
+  int rc;
+  if ((rc = ddalloc(h, &D->ptr, M.n + 1, err))) return rc;
+  if ((rc = ddalloc(h, &D->col, std::max<int64_t>(D->nnz, 1), err))) return rc;
+  if ((rc = ddalloc(h, &D->val, std::max<int64_t>(D->nnz, 1), err))) return rc;
+  if (M.ptr.size() == (size_t)M.n + 1)
+    HIPCHK(hipMemcpy(D->ptr, M.ptr.data(), (M.n + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+  if (D->nnz) {
+    HIPCHK(hipMemcpy(D->col, M.col.data(), D->nnz * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(D->val, M.val.data(), D->nnz * sizeof(double), hipMemcpyHostToDevice));
+  }
+  return MAMG_OK;
+}
+
+// one level of a scalar (CSR) plan: A_loc / P_loc / Rp_loc, the WB rows or
+// the winv slice, POLY's step smoothers (values only, as poly_scaled), the
+// dense inverse in natural order, and the level-0 interior row run
+int upload_scalar_level(DistHandle* h, const HostLevel& hl, const DistLevel& P, int l, int pm, const double* pw,
+                        std::string* err) {
+  DDLevel& D = h->L[l];
+  int rc;
+  if ((rc = upload_dcsr(h, P.cA, &D.cA, l == 0 ? h->p.spmv_lanes : 0, err))) return rc;
+  if (D.coarsest) {
+    const int64_t n = hl.n;
+    if ((rc = ddalloc(h, &D.Ainv, n * n, err))) return rc;
+    HIPCHK(hipMemcpy(D.Ainv, hl.Ainv.data(), n * n * sizeof(double), hipMemcpyHostToDevice));
+    return MAMG_OK;
+  }
+  if ((rc = upload_dcsr(h, P.cP, &D.cP, 0, err))) return rc;
+  if ((rc = upload_dcsr(h, P.cRp, &D.cR, 0, err))) return rc;
+  const bool blk = P.cWB.n > 0;
+  if (blk) {
+    if ((rc = upload_dcsr(h, P.cWB, &D.cWB, 0, err))) return rc;
+  } else {
+    if ((int64_t)P.W.size() != D.nloc) { *err = "scalar plan: winv slice does not cover the owned rows"; return MAMG_ERR_ARG; }
+    if ((rc = ddalloc(h, &D.winv, D.nloc, err))) return rc;
+    if (D.nloc) HIPCHK(hipMemcpy(D.winv, P.W.data(), D.nloc * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (h->p.smoother == MAMG_SMOOTHER_POLY) {
+    const int64_t n = blk ? D.cWB.nnz : D.nloc;
+    const double* src = blk ? D.cWB.val : D.winv;
+    for (int k = 0; k < pm; ++k) {
+      double* q = nullptr;
+      if ((rc = ddalloc(h, &q, std::max<int64_t>(n, 1), err))) return rc;
+      if (n) wscale_kernel<<<nblocks(n), 256>>>(n, pw[k], src, q);
+      HIPCHK(hipGetLastError());
+      if (blk) {
+        DCsr c = D.cWB;
+        c.val = q;
+        D.cWBk.push_back(c);
+      } else {
+        D.winvk.push_back(q);
+      }
+    }
+  }
+  if (l == 0 && !P.replicated) {   // longest run of A_loc rows without ghost columns
+    int64_t best0 = 0, best1 = 0, run0 = 0;
+    for (int64_t i = 0; i <= P.cA.n; ++i) {
+      // rows are sorted by local column: the last entry tells
+      const bool ghost = i == P.cA.n || (P.cA.ptr[i + 1] > P.cA.ptr[i] && P.cA.col[P.cA.ptr[i + 1] - 1] >= P.nloc);
+      if (ghost) {
+        if (i - run0 > best1 - best0) { best0 = run0; best1 = i; }
+        run0 = i + 1;
+      }
+    }
+    D.ib0 = best0;
+    D.ib1 = best1;
+  }
+  return MAMG_OK;
+}
+
 }  // namespace
 
 int dist_check(const mamg_params& p, std::string* err) {
@@ -8732,16 +9019,7 @@ int dist_check(const mamg_params& p, std::string* err) {
     *err = "multi-GPU apply supports maxit 1 (one cycle per application, src/amg_parameters.py:71)";
     return MAMG_ERR_UNSUPPORTED;
   }
-  if (rings_csr(p)) {
-    *err = "multi-GPU apply has no seed-ring Schwarz on scalar (CSR) hierarchies: SCHWARZ_RINGS runs on N GPUs "
-           "on nodal systems with node-block smoothers (num_functions 2, node_block_smoother 1)";
-    return MAMG_ERR_UNSUPPORTED;
-  }
-  if (point_gs(p)) {
-    *err = "multi-GPU apply has no point-wise multicolour GS/SGS (SMOOTHER_GS_POINT / SGS_POINT run on one GPU; "
-           "the multi-GPU smoothers are the node-block ones)";
-    return MAMG_ERR_UNSUPPORTED;
-  }
+  if (int rc = dist_layout_check(p, err)) return rc;   // scalar (CSR) or nodal (BSR2) hierarchies (dist.cpp)
   return MAMG_OK;
 }
 
@@ -8783,6 +9061,7 @@ int dist_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, int
   h->p = p;
   h->rank = rank;
   h->nranks = nranks;
+  h->w = plan.dofs;
   h->device = p.device;
   adopt_prereserve(h.get());
   HIPCHK(hipSetDevice(p.device));
@@ -8812,7 +9091,9 @@ int dist_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, int
     D.coarsest = P.coarsest;
     D.send_off = P.send_off;
     D.ghost_off = P.ghost_off;
-    if (D.coarsest) {
+    if (h->w == 1) {   // scalar level: the plan's CSR operators as they are
+      if ((rc = upload_scalar_level(h.get(), H.levels[l], P, l, pm, pw, err))) return rc;
+    } else if (D.coarsest) {
       const HostLevel& hl = H.levels[l];
       const int64_t n = hl.n, nv = n / 2;
       std::vector<double> Ap(n * n);
@@ -8883,7 +9164,7 @@ int dist_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, int
       if ((rc = ddalloc(h.get(), &D.W, D.nloc, err))) return rc;
       HIPCHK(hipMemcpy(D.W, P.W.data(), 4 * D.nloc * sizeof(double), hipMemcpyHostToDevice));
     }
-    if (!D.coarsest) {
+    if (!D.coarsest && h->w == 2) {
       if (p.smoother == MAMG_SMOOTHER_POLY) {   // w_k W as on one GPU (poly_scaled)
         for (int k = 0; k < pm; ++k) {
           dv4* q = nullptr;
@@ -8897,19 +9178,21 @@ int dist_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, int
       }
     }
     const int64_t full = D.nloc + D.ng;
-    if ((rc = ddalloc(h.get(), &D.b, 2 * full, err))) return rc;
-    if ((rc = ddalloc(h.get(), &D.x, 2 * full, err))) return rc;
-    if ((rc = ddalloc(h.get(), &D.t, 2 * full, err))) return rc;
-    if ((rc = ddalloc(h.get(), &D.t2, 2 * full, err))) return rc;
-    if ((rc = ddalloc(h.get(), &D.r, 2 * full, err))) return rc;
-    if (l == 0 && !D.coarsest && (rc = ddalloc(h.get(), &D.spx, 2 * full, err))) return rc;
-    if ((D.patches || D.rings) && (rc = ddalloc(h.get(), &D.pb, 2 * full, err))) return rc;
+    const int w = h->w;
+    if ((rc = ddalloc(h.get(), &D.b, w * full, err))) return rc;
+    if ((rc = ddalloc(h.get(), &D.x, w * full, err))) return rc;
+    if ((rc = ddalloc(h.get(), &D.t, w * full, err))) return rc;
+    if ((rc = ddalloc(h.get(), &D.t2, w * full, err))) return rc;
+    if ((rc = ddalloc(h.get(), &D.r, w * full, err))) return rc;
+    if (l == 0 && !D.coarsest && (rc = ddalloc(h.get(), &D.spx, w * full, err))) return rc;
+    if ((D.patches || D.rings) && (rc = ddalloc(h.get(), &D.pb, w * full, err))) return rc;
+    if (D.cWB.n > 0 && (rc = ddalloc(h.get(), &D.gb, full, err))) return rc;
     if (l > 0 && p.cycle_type == MAMG_W_CYCLE) {
-      if ((rc = ddalloc(h.get(), &D.c, 2 * full, err))) return rc;
-      if ((rc = ddalloc(h.get(), &D.e, 2 * full, err))) return rc;
+      if ((rc = ddalloc(h.get(), &D.c, w * full, err))) return rc;
+      if ((rc = ddalloc(h.get(), &D.e, w * full, err))) return rc;
     }
     if (l > 0 && p.coarse_scaling) {
-      if ((rc = ddalloc(h.get(), &D.q, 2 * full, err))) return rc;
+      if ((rc = ddalloc(h.get(), &D.q, w * full, err))) return rc;
       if ((rc = ddalloc(h.get(), &D.part2, 2 * SCALE_BLOCKS, err))) return rc;
     }
     const int64_t ns = P.send_idx.size();
@@ -8920,9 +9203,9 @@ int dist_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, int
       if ((rc = ddalloc(h.get(), &D.send_idx, ns, err))) return rc;
       HIPCHK(hipMemcpy(D.send_idx, P.send_idx.data(), ns * sizeof(int64_t), hipMemcpyHostToDevice));
     }
-    if (std::max(ns, tcs) > 0 && (rc = ddalloc(h.get(), &D.sendbuf, 2 * std::max(ns, tcs), err))) return rc;
+    if (std::max(ns, tcs) > 0 && (rc = ddalloc(h.get(), &D.sendbuf, w * std::max(ns, tcs), err))) return rc;
     const int64_t nrcv = std::max(std::max(ns, D.ng), tcg);
-    if (nrcv > 0 && (rc = ddalloc(h.get(), &D.recvbuf, 2 * nrcv, err))) return rc;
+    if (nrcv > 0 && (rc = ddalloc(h.get(), &D.recvbuf, w * nrcv, err))) return rc;
   }
   h->nv0 = plan.levels[0].nv;
   h->o0 = plan.levels[0].o0;
@@ -8945,6 +9228,8 @@ void dist_destroy(DistHandle* h) {
   if (h->side) (void)hipStreamSynchronize(h->side);
   delete h;
 }
+
+int dist_dofs(const DistHandle* h) { return h->w; }
 
 void dist_range(const DistHandle* h, int64_t* o0, int64_t* o1, int64_t* nv) {
   *o0 = h->o0; *o1 = h->o1; *nv = h->nv0;
@@ -9189,7 +9474,9 @@ __global__ __launch_bounds__(256) void vsum_kernel(int64_t n, const double* __re
 // P ranks' op lists in lockstep on one stream
 int virtual_run(const std::vector<DistHandle*>& hs, const std::vector<std::vector<DOp>>& ops, hipStream_t s,
                 std::string* err, bool mark = true) {
-  const int P = (int)hs.size();
+  const int P = (int)hs.size(), w = hs[0]->w;
+  for (int p = 1; p < P; ++p)
+    if (hs[p]->w != w) { *err = "rank handles of different layouts"; return MAMG_ERR_ARG; }
   for (int p = 1; p < P; ++p)
     if (ops[p].size() != ops[0].size()) { *err = "rank schedules differ"; return MAMG_ERR_SETUP; }
   for (size_t k = 0; k < ops[0].size(); ++k) {
@@ -9202,7 +9489,7 @@ int virtual_run(const std::vector<DistHandle*>& hs, const std::vector<std::vecto
       for (int p = 0; p < P; ++p) {
         const DDLevel& D = hs[p]->L[ops[p][k].level];
         const int64_t ns = D.send_off.back();
-        if (ns) pack2_kernel<<<nblocks(ns), 256, 0, s>>>(ns, D.send_idx, ops[p][k].buf, D.sendbuf);
+        if (ns) pack_w(w, ns, D.send_idx, ops[p][k].buf, D.sendbuf, s);
       }
       for (int p = 0; p < P; ++p) {          // p receives from q
         const DDLevel& D = hs[p]->L[ops[p][k].level];
@@ -9213,7 +9500,7 @@ int virtual_run(const std::vector<DistHandle*>& hs, const std::vector<std::vecto
           const DDLevel& Q = hs[q]->L[ops[q][k].level];
           const int64_t sc = Q.send_off[p + 1] - Q.send_off[p];
           if (sc != gc) { *err = "halo count mismatch"; return MAMG_ERR_SETUP; }
-          HIPCHK(dev_copy(ops[p][k].buf + 2 * (D.nloc + D.ghost_off[q]), Q.sendbuf + 2 * Q.send_off[p], 2 * gc * sizeof(double), s));
+          HIPCHK(dev_copy(ops[p][k].buf + w * (D.nloc + D.ghost_off[q]), Q.sendbuf + w * Q.send_off[p], w * gc * sizeof(double), s));
         }
       }
     } else if (dk == D_CHALO) {
@@ -9223,7 +9510,7 @@ int virtual_run(const std::vector<DistHandle*>& hs, const std::vector<std::vecto
         const DDLevel& D = hs[p]->L[ops[p][k].level];
         const int64_t s0 = D.cs_off[b0], s1 = D.cs_off[b0 + P];
         if (s1 > s0)
-          pack2_kernel<<<nblocks(s1 - s0), 256, 0, s>>>(s1 - s0, D.csend_idx + s0, ops[p][k].buf, D.sendbuf + 2 * s0);
+          pack_w(w, s1 - s0, D.csend_idx + s0, ops[p][k].buf, D.sendbuf + w * s0, s);
       }
       for (int p = 0; p < P; ++p) {          // p receives colour c's ghosts from q
         const DDLevel& D = hs[p]->L[ops[p][k].level];
@@ -9234,15 +9521,14 @@ int virtual_run(const std::vector<DistHandle*>& hs, const std::vector<std::vecto
           const int64_t sc = Q.cs_off[b0 + p + 1] - Q.cs_off[b0 + p];
           if (sc != gc) { *err = "colour halo count mismatch"; return MAMG_ERR_SETUP; }
           if (!gc) continue;
-          HIPCHK(dev_copy(D.recvbuf + 2 * D.cg_off[b0 + q], Q.sendbuf + 2 * Q.cs_off[b0 + p], 2 * gc * sizeof(double), s));
+          HIPCHK(dev_copy(D.recvbuf + w * D.cg_off[b0 + q], Q.sendbuf + w * Q.cs_off[b0 + p], w * gc * sizeof(double), s));
         }
       }
       for (int p = 0; p < P; ++p) {
         const DDLevel& D = hs[p]->L[ops[p][k].level];
         const int64_t g0 = D.cg_off[b0], g1 = D.cg_off[b0 + P];
         if (g1 > g0)
-          unpack2_kernel<<<nblocks(g1 - g0), 256, 0, s>>>(g1 - g0, D.cghost_idx + g0, D.nloc, D.recvbuf + 2 * g0,
-                                                          ops[p][k].buf);
+          unpack_w(w, g1 - g0, D.cghost_idx + g0, D.nloc, D.recvbuf + w * g0, ops[p][k].buf, s);
       }
     } else if (dk == D_REVERSE) {
       for (int q = 0; q < P; ++q) {          // owner q receives partials from p
@@ -9254,7 +9540,7 @@ int virtual_run(const std::vector<DistHandle*>& hs, const std::vector<std::vecto
           const DDLevel& D = hs[p]->L[ops[p][k].level];
           const int64_t gc = D.ghost_off[q + 1] - D.ghost_off[q];
           if (sc != gc) { *err = "reverse count mismatch"; return MAMG_ERR_SETUP; }
-          HIPCHK(dev_copy(Q.recvbuf + 2 * Q.send_off[p], ops[p][k].buf + 2 * (D.nloc + D.ghost_off[q]), 2 * sc * sizeof(double), s));
+          HIPCHK(dev_copy(Q.recvbuf + w * Q.send_off[p], ops[p][k].buf + w * (D.nloc + D.ghost_off[q]), w * sc * sizeof(double), s));
         }
       }
       for (int q = 0; q < P; ++q) {
@@ -9262,8 +9548,7 @@ int virtual_run(const std::vector<DistHandle*>& hs, const std::vector<std::vecto
         for (int p = 0; p < P; ++p) {
           const int64_t sc = Q.send_off[p + 1] - Q.send_off[p];
           if (p == q || !sc) continue;
-          addidx2_kernel<<<nblocks(sc), 256, 0, s>>>(sc, Q.send_idx + Q.send_off[p],
-                                                     Q.recvbuf + 2 * Q.send_off[p], ops[q][k].buf);
+          addidx_w(w, sc, Q.send_idx + Q.send_off[p], Q.recvbuf + w * Q.send_off[p], ops[q][k].buf, s);
         }
       }
     } else {                                 // D_ALLREDUCE: sum in rank order
@@ -9297,6 +9582,7 @@ int dist_set_exchange(DistHandle* h, const mamg_exchange& ex, std::string* err) 
   };
   if (!h->host_ex) {
     int64_t red = 0;
+    const int w = h->w;
     const int nl = (int)h->L.size();
     h->hsend.assign(nl, nullptr);
     h->hghost.assign(nl, nullptr);
@@ -9306,10 +9592,10 @@ int dist_set_exchange(DistHandle* h, const mamg_exchange& ex, std::string* err) 
       const int64_t ns = D.send_off.empty() ? 0 : D.send_off.back();
       const int64_t tcs = D.cs_off.empty() ? 0 : D.cs_off.back(), tcg = D.cg_off.empty() ? 0 : D.cg_off.back();
       int rc;
-      if ((rc = pin(&h->hsend[l], 2 * std::max(ns, tcs))) || (rc = pin(&h->hghost[l], 2 * std::max(D.ng, tcg))) ||
-          (rc = pin(&h->hrecv[l], 2 * ns)))
+      if ((rc = pin(&h->hsend[l], w * std::max(ns, tcs))) || (rc = pin(&h->hghost[l], w * std::max(D.ng, tcg))) ||
+          (rc = pin(&h->hrecv[l], w * ns)))
         return rc;
-      red = std::max(red, 2 * D.nv);
+      red = std::max(red, w * D.nv);
     }
     red = std::max<int64_t>(red, 2 * SCALE_BLOCKS);   // coarse scaling partials
     int rc = pin(&h->hred, red);

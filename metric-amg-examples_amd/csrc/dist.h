@@ -22,11 +22,16 @@ struct DistLevel {
   HBsr Rp;                        // transpose of P (partial restriction)
   HBsr PA;                        // post fusion: merged [P_loc | AP_loc] (kpost == false)
   HBsr K;                         // post fusion: K_loc = P_loc - W (AP)_loc (kpost == true)
-  std::vector<double> W;          // 4 per owned node
+  std::vector<double> W;          // 4 per owned node (scalar plan: winv, 1 per owned row)
+  // scalar plan (dofs == 1, CSR layout): a node is a dof; the same operators
+  // as CSR, columns local [owned | ghost], each row sorted by local column
+  Csr cA, cP, cRp;
+  Csr cWB;                        // level 0 with seed blocks: the owned rows of WB (else W = winv)
 };
 
 struct DistPlan {
   int rank = 0, nranks = 1;
+  int dofs = 2;                      // dofs per node: 2 = BSR2 (nodal), 1 = CSR (scalar)
   bool fuse = false, kpost = true;   // post fusion taken; through K (else [P | AP])
   std::vector<DistLevel> levels;
 };
@@ -42,6 +47,16 @@ using GhostLists = std::vector<std::vector<std::vector<int64_t>>>;
 void dist_ranges(const std::vector<int64_t>& nv, const std::vector<char>& coarsest, int nranks,
                  int64_t rep_nodes, std::vector<std::vector<int64_t>>* own, std::vector<char>* rep);
 
+// which hierarchies the row partition takes (dist.cpp; also part of
+// device.hip dist_check): scalar ones (num_functions 1, CSR layout) with the
+// Jacobi-family / POLY smoothers and the additive seed blocks, and nodal ones
+// (num_functions 2, node-block smoothers, BSR2 layout); the message names the
+// alternative
+int dist_layout_check(const mamg_params& p, std::string* err);
+
+// num_functions 1: the scalar plan (DistPlan::dofs == 1; cA / cP / cRp / cWB,
+// W = winv), always from the whole host hierarchy (no pre / meta_only, no post
+// fusion).
 // fuse: prolongation fused into the post sweep (needs A P from the setup);
 // kpost: through K = P - kw W (A P) (one operator), else through [P | AP].
 // pre: ghost lists computed elsewhere (ghier_download_rank: then H holds only
