@@ -15,9 +15,20 @@ extern "C" {
  * or reset (NULL) one of the library's internal layout switches for the
  * process (names in mamg_option_names(); DESIGN.md section 4 gives the
  * measured defaults).  The product library reads no environment variables;
- * MAMG_ERR_ARG for an unknown name. */
+ * MAMG_ERR_ARG for an unknown name.
+ * Every setup call reads the switches once, at its entry: a call here
+ * affects the handles set up after it, and a handle keeps the switches it was
+ * built with for life (its layouts, its first apply and every later one). */
 int mamg_set_option(const char* name, const char* value);
 const char* mamg_option_names(void);   /* comma-separated */
+
+/* The switches a handle was built with, as "NAME=value" joined by commas in
+ * mamg_option_names() order.  Values are the resolved ones (defaults spelled
+ * out, clamps applied; "auto" / empty where an unset switch is a state of its
+ * own).  h == NULL: what a setup starting now would read (needs no GPU).
+ * MAMG_ERR_ARG when cap cannot hold the text and its terminator. */
+int mamg_handle_options(const mamg_handle* h, char* buf, int64_t cap);
+int mamg_dist_options(const mamg_dhandle* h, char* buf, int64_t cap);
 
 /* Verification of a row-sharded Galerkin product (the start of a
  * partition-local setup): on nranks

@@ -72,6 +72,8 @@ SIGNATURES = {
     'mamg_setup_cache_bytes': (C.c_int, [C.c_int, P_I64, P_I64]),
     'mamg_set_option': (C.c_int, [C.c_char_p, C.c_char_p]),
     'mamg_option_names': (C.c_char_p, []),
+    'mamg_handle_options': (C.c_int, [VP, C.c_char_p, C.c_int64]),
+    'mamg_dist_options': (C.c_int, [VP, C.c_char_p, C.c_int64]),
     'mamg_last_error': (C.c_char_p, []),
     'mamg_params_default': (None, [C.POINTER(mamg_params)]),
     'mamg_gen_bidomain_size': (C.c_int, [C.c_int, C.c_int64, P_I64, P_I64]),
@@ -186,6 +188,19 @@ def set_option(name, value):
 
 def option_names():
     return lib().mamg_option_names().decode().split(',')
+
+
+def options_of(fn, handle):
+    """mamg_handle_options / mamg_dist_options as a dict, name -> resolved
+    value (a string), in option_names() order."""
+    buf = C.create_string_buffer(4096)
+    check(fn(handle, buf, len(buf)))
+    return dict(kv.split('=', 1) for kv in buf.value.decode().split(','))
+
+
+def resolved_options():
+    """The switches a setup starting now would read (needs no GPU)."""
+    return options_of(lib().mamg_handle_options, None)
 
 
 def check(rc):

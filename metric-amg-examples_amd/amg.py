@@ -272,6 +272,11 @@ class MetricAMG:
         _lib.check(self._L.mamg_handle_params(self._h, C.byref(p)))
         return params_to_dict(p)
 
+    def options(self) -> dict:
+        """The internal layout switches the handle was built with
+        (mamg_handle_options): it keeps them whatever is set afterwards."""
+        return _lib.options_of(self._L.mamg_handle_options, self._h)
+
     @property
     def apply_bytes(self) -> float:
         b = C.c_double()
@@ -604,6 +609,10 @@ class DistMetricAMG:
         _lib.check(self._L.mamg_dist_range(h, C.byref(o0), C.byref(o1), C.byref(nv)))
         self.o0, self.o1, self.nv = o0.value, o1.value, nv.value
         self.dofs_per_node = self._L.mamg_dist_dofs_per_node(h)
+
+    def options(self) -> dict:
+        """The internal layout switches this rank was built with (mamg_dist_options)."""
+        return _lib.options_of(self._L.mamg_dist_options, self._h)
 
     def set_exchange(self, exchange):
         """Host-staged transport (mamg_dist_set_exchange): 'gloo' = the

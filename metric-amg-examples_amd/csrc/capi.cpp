@@ -203,6 +203,14 @@ struct Seeds {
     n = (int64_t)v.size();
   }
 };
+
+// mamg_handle_options / mamg_dist_options: the snapshot as "NAME=value,..."
+int write_options(const mamg::Switches& sw, char* buf, int64_t cap) {
+  const std::string s = mamg::format_switches(sw);
+  if (!buf || cap <= (int64_t)s.size()) { set_error("options: buffer too small"); return MAMG_ERR_ARG; }
+  std::memcpy(buf, s.c_str(), s.size() + 1);
+  return MAMG_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -482,6 +490,7 @@ int setup_dist_impl(const mamg::CsrView& v, const mamg::DevMat* devA, const int3
                     const mamg_params* params, int rank, int nranks, const void* comm_id, int64_t rep_nodes,
                     mamg_dhandle** out) {
   TmpTrim trim(false);
+  const mamg::Switches sw = mamg::read_switches();   // this setup's, whatever is set meanwhile
   int rc;
   const int64_t nnz0 = devA ? devA->nnz : v.nnz();
   const mamg_params P = mamg::resolve_params(*params, idofs, n_idofs, v.n);   // the reference's Schwarz names
@@ -508,13 +517,13 @@ int setup_dist_impl(const mamg::CsrView& v, const mamg::DevMat* devA, const int3
   // every rank builds the same hierarchy: on its own GPU when the profile is
   // the GPU setup's (bitwise equal to the host setup), else on the host
   rc = MAMG_ERR_UNSUPPORTED;
-  mamg::GHier G;
+  mamg::GHier G(sw);
   mamg::DevMat dA;
   bool on_device = false;   // rank-local operators built from G in HBM
   if (P.num_functions == 2 && P.node_block_smoother &&
       (P.AMG_type == MAMG_UA_AMG || P.sa_block_diag)) {
     G.device = P.device;
-    mamg::dev_prereserve(P.device, nnz0, nranks);   // rank-local layout memory first
+    mamg::dev_prereserve(P.device, nnz0, nranks, sw);   // rank-local layout memory first
     if (devA) { dA = *devA; rc = MAMG_OK; }
     else rc = mamg::upload_a0(v, &G, &dA, &err);
     lap("A0 upload");
@@ -524,9 +533,7 @@ int setup_dist_impl(const mamg::CsrView& v, const mamg::DevMat* devA, const int3
     // G in HBM.  MAMG_DIST_TEST=full: the whole hierarchy downloaded and
     // planned on the host; =rows: the rank's rows downloaded, planned on the
     // host (both bitwise the default; tests)
-    const char* e = mamg::opt("MAMG_DIST_TEST");
-    const std::string et = e ? e : "";
-    const int mode = et == "full" ? 1 : et == "rows" ? 2 : 0;
+    const int mode = sw.dist_test == "full" ? 1 : sw.dist_test == "rows" ? 2 : 0;
     if (rc) {
     } else if (devA && (mode != 0 || G.generic)) {
       err = "multi-GPU setup from a device A_0: this profile plans on the host from the host matrix "
@@ -565,7 +572,7 @@ int setup_dist_impl(const mamg::CsrView& v, const mamg::DevMat* devA, const int3
   if (rc == MAMG_ERR_UNSUPPORTED) rc = mamg::host_setup(v, S.ptr, S.n, P, &H, &err);
   if (rc) { mamg::dev_prereserve_release(); set_error(err); return rc; }
   mamg::DistHandle* d = nullptr;
-  rc = mamg::dist_upload(H, v, P, rank, nranks, comm_id, rep_nodes, &d, &err, pre ? &ghosts : nullptr,
+  rc = mamg::dist_upload(H, v, P, sw, rank, nranks, comm_id, rep_nodes, &d, &err, pre ? &ghosts : nullptr,
                          on_device ? &G : nullptr, on_device ? &dA : nullptr);
   lap("plan + rank-local upload");
   mamg::dev_prereserve_release();
@@ -745,7 +752,7 @@ int mamg_setup(const mamg_csr* A, const int32_t* idofs, int64_t n_idofs,
   rc = mamg::host_setup(v, S.ptr, S.n, P, &H, &err);
   if (rc) { set_error(err); return rc; }
   mamg::DeviceHandle* d = nullptr;
-  rc = mamg::dev_upload(H, v, P, &d, &err);
+  rc = mamg::dev_upload(H, v, P, mamg::read_switches(), &d, &err);
   if (rc) { set_error(err); return rc; }
   *out = new mamg_handle{d};
   return MAMG_OK;
@@ -761,7 +768,7 @@ int mamg_sharded_galerkin_check(const mamg_csr* A, const mamg_csr* P, const mamg
   int rc;
   if ((rc = to_view(A, &a)) || (rc = to_view(P, &p)) || (rc = to_view(Ac, &c))) return rc;
   std::string err;
-  if ((rc = mamg::sharded_galerkin_check(a, p, c, nranks, device, res6, &err))) set_error(err);
+  if ((rc = mamg::sharded_galerkin_check(a, p, c, nranks, device, mamg::read_switches(), res6, &err))) set_error(err);
   return rc;
   GUARD_END
 }
@@ -777,11 +784,11 @@ int mamg_setup_gpu(const mamg_csr* A, const int32_t* idofs, int64_t n_idofs,
   if (rc) return rc;
   const mamg_params P = mamg::resolve_params(*params, idofs, n_idofs, v.n);   // the reference's Schwarz names
   std::string err;
-  mamg::GHier G;
+  mamg::GHier G(mamg::read_switches());
   G.device = P.device;
   mamg::DevMat dA;
   Seeds S(idofs, n_idofs, v.n, &P);
-  mamg::dev_prereserve(P.device, v.nnz(), 1);   // layout memory before the setup churn
+  mamg::dev_prereserve(P.device, v.nnz(), 1, G.sw);   // layout memory before the setup churn
   if ((rc = mamg::upload_a0(v, &G, &dA, &err)) || (rc = mamg::gpu_setup(dA, S.ptr, S.n, P, &G, &err))) {
     mamg::dev_prereserve_release();
     set_error(err);
@@ -818,10 +825,10 @@ int mamg_setup_gpu_device(const mamg_csr* dA, const int32_t* idofs, int64_t n_id
   M.col = const_cast<int32_t*>(dA->colind);
   M.val = const_cast<double*>(dA->values);
   std::string err;
-  mamg::GHier G;
+  mamg::GHier G(mamg::read_switches());
   G.device = P.device;
   Seeds S(idofs, n_idofs, M.n, &P);
-  mamg::dev_prereserve(P.device, M.nnz, 1);   // layout memory before the setup churn
+  mamg::dev_prereserve(P.device, M.nnz, 1, G.sw);   // layout memory before the setup churn
   int rc = mamg::gpu_setup(M, S.ptr, S.n, P, &G, &err);
   if (rc) { mamg::dev_prereserve_release(); set_error(err); return rc; }
   mamg::DeviceHandle* d = nullptr;
@@ -844,7 +851,7 @@ int mamg_gpu_host_setup(const mamg_csr* A, const int32_t* idofs, int64_t n_idofs
   if (rc) return rc;
   const mamg_params P = mamg::resolve_params(*params, idofs, n_idofs, v.n);   // the reference's Schwarz names
   std::string err;
-  mamg::GHier G;
+  mamg::GHier G(mamg::read_switches());
   G.device = P.device;
   mamg::DevMat dA;
   Seeds S(idofs, n_idofs, v.n, &P);
@@ -890,7 +897,7 @@ int mamg_upload(const mamg_hier* h, const mamg_csr* A, const mamg_params* params
   }
   std::string err;
   mamg::DeviceHandle* d = nullptr;
-  int rc = mamg::dev_upload(h->H, v, P, &d, &err);
+  int rc = mamg::dev_upload(h->H, v, P, mamg::read_switches(), &d, &err);
   if (rc) { set_error(err); return rc; }
   *out = new mamg_handle{d};
   return MAMG_OK;
@@ -912,6 +919,18 @@ int mamg_level_format(const mamg_handle* h, int level) {
     return MAMG_ERR_ARG;
   }
   return mamg::dev_level_format(h->d, level);
+}
+
+int mamg_handle_options(const mamg_handle* h, char* buf, int64_t cap) {
+  GUARD_BEGIN
+  return write_options(h ? mamg::dev_switches(h->d) : mamg::read_switches(), buf, cap);
+  GUARD_END
+}
+
+int mamg_dist_options(const mamg_dhandle* h, char* buf, int64_t cap) {
+  GUARD_BEGIN
+  return write_options(h ? mamg::dist_switches(h->d) : mamg::read_switches(), buf, cap);
+  GUARD_END
 }
 
 int mamg_handle_params(const mamg_handle* h, mamg_params* out) {

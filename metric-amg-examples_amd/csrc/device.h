@@ -10,11 +10,12 @@ namespace mamg {
 
 struct DeviceHandle;
 
-int dev_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, DeviceHandle** out,
-               std::string* err);
+// sw: the setup's snapshot of the switch table (opts.h); the handle keeps it
+int dev_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, const Switches& sw,
+               DeviceHandle** out, std::string* err);
 // apply handle from a GPU-setup hierarchy (everything stays in HBM); G's
 // buffers are released level by level as the apply layouts are built
-void dev_prereserve(int device, int64_t nnz, int nranks);
+void dev_prereserve(int device, int64_t nnz, int nranks, const Switches& sw);
 void dev_prereserve_release();
 int dev_from_ghier(GHier* G, const DevMat& A0, const mamg_params& p, DeviceHandle** out,
                    std::string* err);
@@ -39,6 +40,8 @@ int dev_num_levels(const DeviceHandle* h);
 int dev_layout(const DeviceHandle* h);
 int dev_level_format(const DeviceHandle* h, int level);
 mamg_params dev_params(const DeviceHandle* h);
+// the switches the handle was built with (dev_upload's sw, dev_from_ghier's G->sw)
+const Switches& dev_switches(const DeviceHandle* h);
 void dev_kregion(const DeviceHandle* h, std::vector<double>* ms, int* kept);
 double dev_apply_bytes(const DeviceHandle* h);
 int dev_apply(DeviceHandle* h, const double* d_r, double* d_z, void* stream, std::string* err);
@@ -60,11 +63,12 @@ int dist_get_unique_id(void* id, std::string* err);
 // the multi-GPU path's parameter limits (maxit 1, no SCHWARZ_PATCHES /
 // SCHWARZ_RINGS), checked before a rank touches its GPU
 int dist_check(const mamg_params& p, std::string* err);
-int dist_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, int rank, int nranks,
-                const void* comm_id, int64_t rep_nodes, DistHandle** out, std::string* err,
+int dist_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, const Switches& sw, int rank,
+                int nranks, const void* comm_id, int64_t rep_nodes, DistHandle** out, std::string* err,
                 const std::vector<std::vector<std::vector<int64_t>>>* ghosts = nullptr,
                 const GHier* G = nullptr, const DevMat* A0d = nullptr);
 void dist_destroy(DistHandle* h);
+const Switches& dist_switches(const DistHandle* h);
 void dist_range(const DistHandle* h, int64_t* o0, int64_t* o1, int64_t* nv);
 // dofs per node: 2 nodal (BSR2; local vectors field-major), 1 scalar (CSR; plain slices)
 int dist_dofs(const DistHandle* h);

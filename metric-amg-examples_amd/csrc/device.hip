@@ -2329,21 +2329,12 @@ __global__ __launch_bounds__(256, 4) void patch_inv3_kernel(int64_t np, const in
   if (live && ok) patch_store(S, lane, 64, d, -1.0, U + i * ustride);
 }
 
-// MAMG_PATCH_INV: 1 the round-5 kernel (one patch per wave), 2 two patches
-// per wave (bitwise the same), default 3 the matrix-core block sweep
-int patch_inv_version() {
-  const char* e = opt("MAMG_PATCH_INV");
-  const int v = e ? std::atoi(e) : 3;
-#if MAMG_DIAG
-  if (v == 4 || v == 5) return v;
-#endif
-  return v == 1 || v == 2 ? v : 3;
-}
-
-void launch_patch_inv(int64_t np, const int32_t* perm, const int64_t* ptr, const int32_t* col, const int32_t* gcol,
-                      const dv4* val, int64_t ustride, double* U, int* bad) {
+// version (MAMG_PATCH_INV): 1 the round-5 kernel (one patch per wave), 2 two
+// patches per wave (bitwise the same), default 3 the matrix-core block sweep
+void launch_patch_inv(int version, int64_t np, const int32_t* perm, const int64_t* ptr, const int32_t* col,
+                      const int32_t* gcol, const dv4* val, int64_t ustride, double* U, int* bad) {
   if (np <= 0) return;
-  switch (patch_inv_version()) {
+  switch (version) {
     case 1: patch_inv_kernel<<<(unsigned)((np + 3) / 4), 256>>>(np, perm, ptr, col, gcol, val, ustride, U, bad); break;
     case 2: patch_inv2_kernel<<<(unsigned)((np + 7) / 8), 256>>>(np, perm, ptr, col, gcol, val, ustride, U, bad); break;
 #if MAMG_DIAG
@@ -2714,83 +2705,15 @@ __global__ __launch_bounds__(256) void cscale_kernel(int64_t n, int nb, const do
 
 inline unsigned nblocks(int64_t work) { return (unsigned)((work + 255) / 256); }
 
-// Tuning knobs (environment, read at upload), kept
-// because a test or an A/B needs them:
-//   MAMG_SELL_MIN_ROWS  node rows from which a level-0-class operator is stored
-//                       SELL-64 / half-symmetric (default 2^20; tests lower it
-//                       to exercise those formats on small problems)
-//   MAMG_MSELL_MIN_ROWS node rows from which a coarse level's A and K are stored
-//                       SELL-64 with several lanes per row (msell_kernel; off by
-//                       default: slower than the lane-group BSR kernels there)
-//   MAMG_HALF           0: SELL-64 instead of the half-symmetric ELL-64 A0 (1)
-//   MAMG_HALF_BANDS     band schedule of the half-symmetric kernel: sub-bands per
-//                       XCD (1; 0 = row order)
-//   MAMG_R_BANDS        plane-band schedule of the level-0 restriction: sub-bands
-//                       per XCD (1; 0 = XCD-contiguous rows)
-//   MAMG_K_SORT         level-0 K's rows sorted by length inside each SELL slice
-//                       (1; 0 = row order; sort_sell_slices)
-//   MAMG_POST_K         0: fused post sweep over [P | AP] instead of K = P - W A P (1)
-//   multi-GPU (mamg_setup_dist): MAMG_OVERLAP 0 = no interior-row launch during
-//   the forward halo (1); MAMG_DIST_TEST=dry: a virtual rank skips its exchanges
-//   (compute-only timing; results meaningless); setup: MAMG_PRERESERVE_B_PER_NNZ
 // Fixed by measurement (round 1 A/Bs; the variants
 // measured slower were removed in round 2): XCD-contiguous restriction rows,
 // SELL chunks of 8 blocks (K: 6), half-symmetric chunks of 4 with
 // XCD-contiguous rows, symmetric-block packing, lane counts from the mean row
-// length.
-constexpr int g_sell_u = 8;
-constexpr int g_post_u = 6;
-constexpr int64_t g_sell_max_len = 40;
-int g_half = 1;
-int g_half_bands = 1;
-int g_r_bands = 1;
-int g_k_sort = 1;
-int g_post_k = 1;
-int g_kvar = 0;
-int g_k_c16 = 1;   // MAMG_K_COL16: level-0 K's columns as 16-bit offsets from a per-slice base
+// length.  What stays selectable is a switch (opts.h), read from the handle.
+constexpr int sell_u = 8;
+constexpr int post_u = 6;
+constexpr int64_t sell_max_len = 40;
 __global__ void warm_kernel() {}
-
-// MAMG_FUSE_RBD: which restrictions write the next level's first sweep
-// (EPI_YBD): 2 those below level 0 (default), 1 all, 0 none.  A/B at
-// nrefs=6 (profiles/r05_fuse_rbd_ab.txt, 3 x 3 alternating runs): coarse
-// levels 0.400 -> 0.386 ms with 2; with 1 also level 0's restriction,
-// 0.461 -> 0.490 ms, a net loss
-int g_fuse_rbd = 2;
-int64_t g_sell_min_rows = 1 << 20;
-int64_t g_msell_min_rows = (int64_t)1 << 40;
-int64_t g_tail_nodes = 0;
-bool g_tail_set = false;   // MAMG_TAIL_NODES given: applies to every smoother (tests)   // off: coarse levels 0.41 -> 0.50 ms
-int g_tail_vl = 4;           // lanes per row cap inside the coarse tail (MAMG_TAIL_VL; 1/2/4/8/64 measured)
-void read_knobs() {
-  const char* e = nullptr;
-#if MAMG_DIAG
-  e = std::getenv("MAMG_K_VARIANT");   // the level-0 K kernel (diagnosis build: tests, A/Bs; read at upload)
-  g_kvar = e ? std::atoi(e) : 0;
-#endif
-  e = opt("MAMG_POST_K");
-  g_post_k = e ? std::atoi(e) : 1;   // 0: [P | AP]; 1: K (one block per slot); 2: K, split layout forced
-  e = opt("MAMG_SELL_MIN_ROWS");
-  g_sell_min_rows = e ? std::atoll(e) : (1 << 20);
-  e = opt("MAMG_TAIL_NODES");
-  g_tail_nodes = e ? std::atoll(e) : 0;
-  g_tail_set = e != nullptr;
-  e = opt("MAMG_TAIL_VL");
-  g_tail_vl = e ? std::max(1, std::min(64, std::atoi(e))) : 4;
-  e = opt("MAMG_MSELL_MIN_ROWS");
-  g_msell_min_rows = e ? std::atoll(e) : ((int64_t)1 << 40);
-  e = opt("MAMG_HALF");
-  g_half = e ? std::atoi(e) != 0 : 1;
-  e = opt("MAMG_HALF_BANDS");
-  g_half_bands = e ? std::atoi(e) : 1;
-  e = opt("MAMG_R_BANDS");
-  g_r_bands = e ? std::atoi(e) : 1;
-  e = opt("MAMG_K_SORT");
-  g_k_sort = e ? std::atoi(e) : 1;
-  e = opt("MAMG_FUSE_RBD");
-  g_fuse_rbd = e ? std::atoi(e) : 2;
-  e = opt("MAMG_K_COL16");
-  g_k_c16 = e ? std::atoi(e) : 1;
-}
 
 // every block symmetric (bitwise): then 3 doubles per block carry it exactly
 bool blocks_symmetric(const HBsr& B) {
@@ -2845,6 +2768,7 @@ struct DBsr {              // 2x2 blocks, node-major
   // col16 + cbase
   uint16_t* col16 = nullptr;
   int32_t* cbase = nullptr;
+  int kvar = 0;             // a K's kernel variant (launch_kvariant; 0 in the product build)
   // half-symmetric ELL-64 (half == true, A symmetric bitwise): col / val hold
   // the upper part I <= J < nr, hwu slots per row; lptr holds,
   // per lower entry J < I, the slot of the mirror block (J, I) in the upper
@@ -3016,6 +2940,8 @@ struct PcgGraph {
 
 struct DeviceHandle {
   mamg_params p;
+  const Switches sw;               // the switches the handle was built with (opts.h)
+  explicit DeviceHandle(const Switches& s) : sw(s) {}
   int device = 0;
   bool bsr = false;
   std::vector<DLevel> L;
@@ -3070,10 +2996,9 @@ enum { LT_BUILD = 0, LT_KREGION = 1, LT_REHOME = 2, LT_FINISH = 3 };
 // read of a value nothing wrote shows in the result (index arrays are left
 // alone: a poisoned index would fault instead of showing)
 template <class T>
-void poison_doubles(T* p, size_t bytes) {
+void poison_doubles(const Switches& sw, T* p, size_t bytes) {
   if constexpr (std::is_same<T, double>::value) {
-    const char* e = opt("MAMG_POISON");
-    if (e && std::atoi(e) != 0) (void)dev_memset(p, 0xff, bytes);
+    if (sw.poison) (void)dev_memset(p, 0xff, bytes);
   }
 }
 
@@ -3094,7 +3019,7 @@ int dalloc(HT* h, T** p, int64_t count, std::string* err) {
     *p = (T*)h->arena;
     h->arena += bytes;
     h->arena_left -= bytes;
-    poison_doubles(*p, bytes);
+    poison_doubles(h->sw, *p, bytes);
     return MAMG_OK;
   }
   void* q = nullptr;
@@ -3106,7 +3031,7 @@ int dalloc(HT* h, T** p, int64_t count, std::string* err) {
   HIPCHK(dev_malloc(&q, (size_t)count * sizeof(T)));
   h->allocs.push_back(q);
   *p = (T*)q;
-  poison_doubles(*p, (size_t)count * sizeof(T));
+  poison_doubles(h->sw, *p, (size_t)count * sizeof(T));
   return MAMG_OK;
 }
 
@@ -3205,7 +3130,7 @@ int upload_bsr(HT* h, const HBsr& B, DBsr* D, int lanes, std::string* err,
   int rc;
   // SELL-64 for many short rows (one lane per row needs >> 256 CUs x 64 rows)
   const bool merged_rows = np == 2 * B.nr + 1;
-  if (B.nr >= g_sell_min_rows && D->nb <= g_sell_max_len * B.nr && !merged_rows) {
+  if (B.nr >= h->sw.sell_min_rows && D->nb <= sell_max_len * B.nr && !merged_rows) {
     D->sym = sym && np == B.nr + 1 && blocks_symmetric(B);
     return upload_sell(h, B, D, err);
   }
@@ -3661,7 +3586,9 @@ struct TBsr {
 // the layout kernels that read them are queued on the null stream, and a
 // block handed out again is used only by work queued behind them
 struct TmpPool {
+  const Switches& sw;   // the owning handle's
   std::vector<void*> v;
+  explicit TmpPool(const Switches& s) : sw(s) {}
   ~TmpPool() {
     for (void* p : v) tmp_free(p);
   }
@@ -3671,7 +3598,7 @@ struct TmpPool {
     HIPCHK(tmp_malloc(&q, (size_t)std::max<int64_t>(count, 1) * sizeof(T)));
     v.push_back(q);
     *p = (T*)q;
-    poison_doubles(*p, (size_t)std::max<int64_t>(count, 1) * sizeof(T));
+    poison_doubles(sw, *p, (size_t)std::max<int64_t>(count, 1) * sizeof(T));
     return MAMG_OK;
   }
   void release(void* p) {
@@ -3701,8 +3628,7 @@ int dev_csr_to_bsr(TmpPool* T, const DevMat& M, int64_t nr, int64_t nc, TBsr* B,
   if ((rc = T->alloc(&B->col, B->nb, err))) return rc;
   if ((rc = T->alloc(&B->val, B->nb, err))) return rc;
   // MAMG_CSR2BSR_FILL=0: the column + value staged fill (csr2bsr_kernel<true>; tests, A/B)
-  const char* fe = opt("MAMG_CSR2BSR_FILL");
-  const bool f2 = fe ? std::atoi(fe) != 0 : true;
+  const bool f2 = T->sw.csr2bsr_fill;
   if (nr && f2 && lng)
     csr2bsr_fill_kernel<RS_CAP_LONG><<<g, RS_NODES>>>(nr, nc, M.ptr, M.col, M.val, B->ptr, B->col, B->val);
   else if (nr && f2)
@@ -3806,7 +3732,7 @@ int upload_sched(HT* h, const std::vector<int32_t>& sched, int32_t** d, int64_t*
 template <class HT>
 int build_band_sched(HT* h, const TBsr& B, DBsr* D, std::string* err) {
   const int64_t nr = B.nr, G = (nr + 255) / 256;
-  if (g_half_bands <= 0 || G < 64) return MAMG_OK;
+  if (h->sw.half_bands <= 0 || G < 64) return MAMG_OK;
   const int ns = 257;
   std::vector<int64_t> off;
   for (int i = 0; i < ns; ++i) {
@@ -3819,7 +3745,7 @@ int build_band_sched(HT* h, const TBsr& B, DBsr* D, std::string* err) {
   }
   if (off.size() < ns / 2) return MAMG_OK;
   std::nth_element(off.begin(), off.begin() + off.size() / 2, off.end());
-  const std::vector<int32_t> sched = band_sched(G, off[off.size() / 2], g_half_bands);
+  const std::vector<int32_t> sched = band_sched(G, off[off.size() / 2], h->sw.half_bands);
   if (sched.empty()) return MAMG_OK;
   D->band_stride = off[off.size() / 2];
   return upload_sched(h, sched, &D->sched, &D->nsched, err);
@@ -3830,7 +3756,7 @@ int build_band_sched(HT* h, const TBsr& B, DBsr* D, std::string* err) {
 template <class HT>
 int build_band_sched_range(HT* h, DBsr* D, int64_t r0, int64_t r1, std::string* err) {
   if (!D->half || D->band_stride <= 0 || r1 <= r0) return MAMG_OK;
-  const std::vector<int32_t> sched = band_sched((r1 - r0 + 255) / 256, D->band_stride, g_half_bands);
+  const std::vector<int32_t> sched = band_sched((r1 - r0 + 255) / 256, D->band_stride, h->sw.half_bands);
   if (sched.empty()) return MAMG_OK;
   D->sr0 = r0;
   D->sr1 = r1;
@@ -3895,10 +3821,10 @@ std::vector<int32_t> rest_band_sched(const std::vector<int32_t>& c0, int64_t Sf,
 // plane stride Sf of its columns
 template <class HT>
 int build_rest_sched(HT* h, TmpPool* T, DBsr* D, int64_t Sf, std::string* err) {
-  if (g_r_bands <= 0 || Sf <= 0 || D->sell || D->half || !D->ptr || D->lanes <= 0) return MAMG_OK;
+  if (h->sw.r_bands <= 0 || Sf <= 0 || D->sell || D->half || !D->ptr || D->lanes <= 0) return MAMG_OK;
   const int rpw = 256 / D->lanes;
   const int64_t G = (D->nr * (int64_t)D->lanes + 255) / 256;
-  if (G < 64 * 8 * (int64_t)g_r_bands || G >= ((int64_t)1 << 31)) return MAMG_OK;
+  if (G < 64 * 8 * (int64_t)h->sw.r_bands || G >= ((int64_t)1 << 31)) return MAMG_OK;
   int rc;
   int32_t* c0 = nullptr;
   if ((rc = T->alloc(&c0, G, err))) return rc;
@@ -3907,7 +3833,7 @@ int build_rest_sched(HT* h, TmpPool* T, DBsr* D, int64_t Sf, std::string* err) {
   std::vector<int32_t> hc(G);
   HIPCHK(hipMemcpy(hc.data(), c0, G * sizeof(int32_t), hipMemcpyDeviceToHost));
   T->release(c0);
-  const std::vector<int32_t> sched = rest_band_sched(hc, Sf, g_r_bands);
+  const std::vector<int32_t> sched = rest_band_sched(hc, Sf, h->sw.r_bands);
   if (sched.empty()) return MAMG_OK;
   if ((rc = upload_sched(h, sched, &D->rsched, &D->nrsched, err))) return rc;
   D->rsched_vl = D->lanes;
@@ -3990,9 +3916,9 @@ int try_half(HT* h, TmpPool* T, const TBsr& B, DBsr* D, std::string* err) {
 template <class HT>
 int upload_half_or_bsr(HT* h, const HBsr& B, DBsr* D, std::string* err) {
   const int64_t np = (int64_t)B.ptr.size();
-  if (g_half && B.nr >= g_sell_min_rows && np == B.nr + 1 && blocks_symmetric(B)) {
+  if (h->sw.half && B.nr >= h->sw.sell_min_rows && np == B.nr + 1 && blocks_symmetric(B)) {
     int rc;
-    TmpPool T;
+    TmpPool T(h->sw);
     TBsr tb;
     tb.nr = B.nr; tb.nc = B.nc; tb.nb = B.ptr[B.nr];
     if ((rc = T.alloc(&tb.ptr, np, err))) return rc;
@@ -4040,13 +3966,14 @@ int finalize_bsr(HT* h, TmpPool* T, TBsr& B, DBsr* D, int lanes, bool sym_ok, st
   const int per = sym ? 3 : 4;
   // multi-lane SELL (msell_kernel) for the coarse levels' A and K: lanes per
   // row from the mean row length, chunks of 5 blocks per lane
-  const bool msell = allow_sell && allow_msell && !B.merged && nr >= g_msell_min_rows && nr < g_sell_min_rows;
+  const bool msell = allow_sell && allow_msell && !B.merged && nr >= h->sw.msell_min_rows &&
+                     nr < h->sw.sell_min_rows;
   if (msell) {
     const double mean = nr ? (double)D->nb / (double)nr : 0.0;
     D->lpr = mean <= 10.0 ? 2 : mean <= 20.0 ? 4 : mean <= 40.0 ? 8 : 16;
   }
-  if (allow_sell && ((nr >= g_sell_min_rows && D->nb <= g_sell_max_len * nr) || msell) && !B.merged) {
-    if (allow_half && g_half && sym && nr == B.nc) {
+  if (allow_sell && ((nr >= h->sw.sell_min_rows && D->nb <= sell_max_len * nr) || msell) && !B.merged) {
+    if (allow_half && h->sw.half && sym && nr == B.nc) {
       if ((rc = try_half(h, T, B, D, err))) return rc;
       if (D->half) return MAMG_OK;
     }
@@ -4675,7 +4602,7 @@ int build_patches(DeviceHandle* h, TmpPool* T, const TBsr& B, DLevel* D, std::st
   const int64_t dmax = 2 * (int64_t)hf[3];
   D->pus = dmax * (dmax + 1) / 2;
   if ((rc = dalloc(h, &D->pu, nr * D->pus, err))) return rc;
-  launch_patch_inv(nr, D->pperm, D->Sptr, D->Scol, D->Scol, D->Sval, D->pus, D->pu, flags + 2);
+  launch_patch_inv(h->sw.patch_inv, nr, D->pperm, D->Sptr, D->Scol, D->Scol, D->Sval, D->pus, D->pu, flags + 2);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(hf, flags, 4 * sizeof(int), hipMemcpyDeviceToHost));
   if (hf[2]) { *err = "node patches: a patch matrix is not SPD (non-positive Gauss-Jordan pivot)"; return MAMG_ERR_SETUP; }
@@ -4823,7 +4750,7 @@ int build_bsr_level(DeviceHandle* h, int l, const LevelSrc& S, int64_t nvc, int 
   const mamg_params& p = h->p;
   const int64_t nv = D.n / 2;
   int rc;
-  TmpPool T;
+  TmpPool T(h->sw);
   if (D.coarsest) {
     if ((rc = dalloc(h, &D.Ainv, D.n * D.n, err))) return rc;
     permute_dense_kernel<<<nblocks(D.n * D.n), 256>>>(D.n, S.Ainv, D.Ainv);
@@ -4859,7 +4786,7 @@ int build_bsr_level(DeviceHandle* h, int l, const LevelSrc& S, int64_t nvc, int 
     TBsr Pb, Qb, M;
     if ((rc = dev_csr_to_bsr(&T, S.P, nv, nvc, &Pb, err))) return rc;
     if ((rc = dev_csr_to_bsr(&T, S.AP, nv, nvc, &Qb, err))) return rc;
-    if (g_post_k) {   // one operator K = P - W (A P) on AP's pattern,
+    if (h->sw.post_k) {   // one operator K = P - W (A P) on AP's pattern,
                       // W = the first post-smoothing step's smoother
       const double* Wpost = reinterpret_cast<const double*>(step_wd(D, 0, false));
       if ((rc = dev_kmerge(&T, Pb, Qb, Wpost, &M, err))) return rc;
@@ -4871,12 +4798,13 @@ int build_bsr_level(DeviceHandle* h, int l, const LevelSrc& S, int64_t nvc, int 
     // K: SELL-64 with 4-block chunks (K rows hold ~9 blocks at level 0; A/B in
     // DESIGN.md section 4), lane-group BSR if MAMG_POST_SELL=0; the merged
     // window is never SELL on this path
-    if ((rc = finalize_bsr(h, &T, M, g_post_k ? &D.KPb : &D.PAb, 0, false, err, g_post_k != 0, false,
-                           l > 0 && g_post_k != 0)))
+    if ((rc = finalize_bsr(h, &T, M, h->sw.post_k ? &D.KPb : &D.PAb, 0, false, err, h->sw.post_k != 0, false,
+                           l > 0 && h->sw.post_k != 0)))
       return rc;
-    if (l == 0 && g_post_k && g_k_sort && D.KPb.sell && D.KPb.lpr <= 1)
+    D.KPb.kvar = h->sw.k_variant;
+    if (l == 0 && h->sw.post_k && h->sw.k_sort && D.KPb.sell && D.KPb.lpr <= 1)
       if ((rc = sort_sell_slices(h, &T, &D.KPb, err))) return rc;
-    if (l == 0 && g_post_k && D.KPb.sell && g_k_c16)
+    if (l == 0 && h->sw.post_k && D.KPb.sell && h->sw.k_col16)
       if ((rc = compress_sell_cols(h, &T, &D.KPb, err))) return rc;
   } else {
     TBsr Pb;
@@ -5255,9 +5183,10 @@ void scale_ops(const DeviceHandle* h, int lc, std::vector<Op>* ops) {
 
 // ---- BSR2 layout.  b / xout of level 0 are the caller's field-major vectors
 // (stride nv0); all other vectors are node-interleaved (stride 0).
-// one op of the launch path as a coarse-tail op (tail_kernel); false if
-// the tail cannot express it (level-0 formats and strides, patches, CSR)
-bool to_tail(const Op& o, TOp* t) {
+// one op of the launch path as a coarse-tail op (tail_kernel; at most vl_cap
+// lanes per row, MAMG_TAIL_VL); false if the tail cannot express it (level-0
+// formats and strides, patches, CSR)
+bool to_tail(const Op& o, int vl_cap, TOp* t) {
   *t = TOp();
   switch (o.kind) {
     case OP_BSR:
@@ -5265,7 +5194,7 @@ bool to_tail(const Op& o, TOp* t) {
       const DBsr& M = *o.Mb;
       if (M.sell || M.half || M.split || o.xs || o.bs || o.os || o.xfm || M.lanes < 1 || M.lanes > 64) return false;
       t->kind = o.kind == OP_GS ? T_GS : T_BSR;
-      t->epi = o.epi; t->vl = std::min(M.lanes, g_tail_vl); t->sym = M.sym ? 1 : 0; t->n = M.nr; t->nb = M.nb;
+      t->epi = o.epi; t->vl = std::min(M.lanes, vl_cap); t->sym = M.sym ? 1 : 0; t->n = M.nr; t->nb = M.nb;
       t->ptr = M.ptr; t->col = M.col; t->val = M.val;
       t->x = o.kind == OP_GS ? o.out : o.x; t->y = o.y; t->b = o.b; t->W = o.W; t->out = o.out;
       t->r0 = o.r0; t->r1 = o.r1; t->perm = o.perm;
@@ -5296,8 +5225,7 @@ constexpr int64_t TAIL_LDS_MAX = 160 * 1024 - 1024;   // gfx950: 160 KB per work
 // written ones copied out last.  Returns the dynamic LDS bytes, or 0 (program
 // unchanged: global vectors) when the plan exceeds the LDS.
 int64_t tail_lds_plan(const DeviceHandle* h, int l, std::vector<TOp>* prog, int64_t reserve = 0) {
-  if (const char* e = opt("MAMG_TAIL_LDS"))
-    if (std::atoi(e) == 0) return 0;
+  if (!h->sw.tail_lds) return 0;
   struct Vec {
     double* base;
     int64_t n;
@@ -5405,8 +5333,7 @@ int64_t tail_lds_plan(const DeviceHandle* h, int l, std::vector<TOp>* prog, int6
 // nothing is resident.
 bool tail_res_plan(const DeviceHandle* h, int l, std::vector<TOp>* prog, std::vector<char>* img, int64_t* nov) {
   *nov = 0;
-  if (const char* e = opt("MAMG_TAIL_RES"))
-    if (std::atoi(e) == 0) return false;
+  if (!h->sw.tail_res) return false;
   constexpr int T = TAIL_THREADS;
   std::vector<dv4> iv((size_t)RES_RB * T, dv4{0.0, 0.0, 0.0, 0.0});
   std::vector<uint32_t> ic((size_t)RES_RB / 2 * T, 0u);
@@ -5543,7 +5470,7 @@ bool tail_ops(const DeviceHandle* h, int l, const double* b, double* xout, std::
     std::vector<TOp> prog(sub.size());
     double bytes = 0.0;
     for (size_t k = 0; k < sub.size(); ++k) {
-      if (!to_tail(sub[k], &prog[k])) return false;
+      if (!to_tail(sub[k], h->sw.tail_vl, &prog[k])) return false;
       bytes += sub[k].bytes;
     }
     std::vector<char> img;
@@ -5561,11 +5488,9 @@ bool tail_ops(const DeviceHandle* h, int l, const double* b, double* xout, std::
     // (TAIL_LDS_MAX); the dynamic LDS then covers both
     int prog_lds = -1;
     int64_t pbytes = (int64_t)(prog.size() * sizeof(TOp));
-    const char* pl_opt = opt("MAMG_TAIL_PROG_LDS");
     // default: scalar loads (s_load of a uniform descriptor: 795 vs 1262
     // cycles per empty op)
-    const bool prog_in_lds = pl_opt ? std::atoi(pl_opt) != 0 : false;
-    if (lds > 0 && prog_in_lds) {
+    if (lds > 0 && h->sw.tail_prog_lds) {
       const int64_t off = (lds + 15) / 16 * 16;
       if (off + pbytes <= TAIL_LDS_MAX) {
         prog_lds = (int)off;
@@ -5594,7 +5519,7 @@ bool tail_ops(const DeviceHandle* h, int l, const double* b, double* xout, std::
         lds = tail_lds_plan(h, l, &prog);
         prog_lds = -1;
         pbytes = (int64_t)(prog.size() * sizeof(TOp));
-        if (lds > 0 && prog_in_lds) {
+        if (lds > 0 && h->sw.tail_prog_lds) {
           const int64_t o2 = (lds + 15) / 16 * 16;
           if (o2 + pbytes <= TAIL_LDS_MAX) {
             prog_lds = (int)o2;
@@ -5695,7 +5620,7 @@ void cycle_ops_bsr(const DeviceHandle* h, int l, const double* b, int64_t bs, do
   ops->back().remap = 1;
   // the coarse level's first sweep in the restriction's epilogue (launch path,
   // bsr2_kernel layouts only; the tail programs keep their own T_BD)
-  const bool ybd = (g_fuse_rbd == 1 || (g_fuse_rbd == 2 && l > 0)) && tail_ok && starts_with_bd(h, l + 1) &&
+  const bool ybd = (h->sw.fuse_rbd == 1 || (h->sw.fuse_rbd == 2 && l > 0)) && tail_ok && starts_with_bd(h, l + 1) &&
                    !L.Rb.sell && !L.Rb.half && !L.Rb.sym && !L.Rb.split;
   if (ybd) {
     Op& r = ops->back();
@@ -5875,7 +5800,7 @@ void launch_msell(const Op& o, hipStream_t s) {
   const int64_t b0 = r0 / rows;
   const unsigned g = (unsigned)((r1 + rows - 1) / rows - b0);
 #define MSELL_ARGS r1, M.soff, M.meta, M.col, M.val, M.nbs, o.x, o.xs, o.y, o.b, o.bs, o.W, o.out, o.os, \
-    (TAG == 0 && g_kvar == 3) ? 1 : 0, M.lsort ? 1 : 0, b0, M.col16, M.cbase
+    (TAG == 0 && M.kvar == 3) ? 1 : 0, M.lsort ? 1 : 0, b0, M.col16, M.cbase
   switch (o.epi) {
     case EPI_Y: msell_kernel<LPR, U, EPI_Y, XFM, SYM, SPL, TAG, PROBE><<<g, 256, 0, s>>>(MSELL_ARGS); break;
     case EPI_YADD: msell_kernel<LPR, U, EPI_YADD, XFM, SYM, SPL, TAG, PROBE><<<g, 256, 0, s>>>(MSELL_ARGS); break;
@@ -5893,15 +5818,15 @@ void launch_msell(const Op& o, hipStream_t s) {
 #undef MSELL_ARGS
 }
 
-// the level-0 K kernel (MAMG_K_VARIANT for A/Bs, read at upload and by
-// mamg_time_apply): 0 two lanes per row, chunks of 5 (default); 1 one lane
+// the level-0 K kernel (DBsr::kvar, the diagnosis build's MAMG_K_VARIANT for
+// A/Bs): 0 two lanes per row, chunks of 5 (default); 1 one lane
 // per row, chunks of 6 (sell2_kernel, round 2); 2 four lanes per row, chunks
 // of 3; 4 / 5 the default with non-temporal loads of the columns and values /
 // the values only (the K stream kept from evicting the gathered e from L2);
 // 9 a probe without the e gathers (wrong results, timing only)
 template <int SPL>
 bool launch_kvariant(const Op& o, hipStream_t s) {
-  switch (g_kvar) {
+  switch (o.Mb->kvar) {
     case 4: launch_msell<2, 5, false, false, SPL, 0, 2>(o, s); return true;
     case 5: launch_msell<2, 5, false, false, SPL, 0, 3>(o, s); return true;
     case 1: return SPL == 2 ? (launch_msell<1, 6, false, false, SPL, 0>(o, s), true) : false;
@@ -5917,7 +5842,7 @@ bool launch_kvariant(const Op& o, hipStream_t s) {
 // the diagnosis build's MAMG_K_VARIANT=1 on a K not split in two streams,
 // does not): the distributed apply splits K around the coarse halo only then
 // 
-bool k_ranges_ok(const DBsr& K) { return !K.sell || !(g_kvar == 1 && K.split != 2); }
+bool k_ranges_ok(const DBsr& K) { return !K.sell || !(K.kvar == 1 && K.split != 2); }
 
 template <bool XFM, bool SYM, int TAG>
 void launch_sell_x(const Op& o, hipStream_t s) {
@@ -5940,10 +5865,10 @@ void launch_sell_x(const Op& o, hipStream_t s) {
       }
     }
   }
-  if (o.Mb->split && TAG == 0) launch_sell_u<XFM, SYM, g_post_u, true, TAG>(o, s);
-  else if (o.Mb->split) launch_sell_u<XFM, SYM, g_sell_u, true, TAG>(o, s);
-  else if (TAG == 0 && o.epi == EPI_KPOST) launch_sell_u<XFM, SYM, g_post_u, false, TAG>(o, s);
-  else launch_sell_u<XFM, SYM, g_sell_u, false, TAG>(o, s);
+  if (o.Mb->split && TAG == 0) launch_sell_u<XFM, SYM, post_u, true, TAG>(o, s);
+  else if (o.Mb->split) launch_sell_u<XFM, SYM, sell_u, true, TAG>(o, s);
+  else if (TAG == 0 && o.epi == EPI_KPOST) launch_sell_u<XFM, SYM, post_u, false, TAG>(o, s);
+  else launch_sell_u<XFM, SYM, sell_u, false, TAG>(o, s);
 }
 
 template <int TAG>
@@ -6277,10 +6202,8 @@ void select_k_region(DeviceHandle* h) {
   DLevel& L = h->L[0];
   DBsr& K = L.KPb;
   const size_t bytes = (size_t)K.nbs * 4 * sizeof(double);
-  const char* e = opt("MAMG_KREGION_TRIES");
-  const int tries = e ? std::atoi(e) : 4;
-  const char* eb = opt("MAMG_KREGION_BUDGET_MS");
-  const double budget = eb ? std::atof(eb) : 200.0;
+  const int tries = h->sw.kregion_tries;
+  const double budget = h->sw.kregion_budget_ms;
   if (tries <= 1 || K.sym || !L.r || !L.t || !L.Wd || !h->L[1].x) {
     rehome_array(h, (void**)&K.val, bytes);
     return;
@@ -6354,9 +6277,8 @@ void select_k_region(DeviceHandle* h) {
 }
 
 void rehome_operators(DeviceHandle* h) {
-  const char* e = opt("MAMG_REHOME");   // 0: keep the operators where the layout builder put them (tests)
-  if (e && std::atoi(e) == 0) return;
-  if (!h->bsr || h->L.size() < 2 || h->L[0].KPb.nr < g_sell_min_rows || !h->L[0].KPb.sell) return;
+  if (!h->sw.rehome) return;   // the operators stay where the layout builder put them (tests)
+  if (!h->bsr || h->L.size() < 2 || h->L[0].KPb.nr < h->sw.sell_min_rows || !h->L[0].KPb.sell) return;
   DLevel& L = h->L[0];
   auto lap = [t = std::chrono::steady_clock::now()]() mutable {
     const auto n = std::chrono::steady_clock::now();
@@ -6420,7 +6342,7 @@ void set_k_split(DBsr& K, int mode) {
 // 182.5 ms per apply with it (PCG graph replay).
 void set_tail_level(DeviceHandle* h) {
   h->tail_level = 0;
-  const int64_t nodes = g_tail_set ? g_tail_nodes : (gs_smoother(h->p) ? 1024 : 0);
+  const int64_t nodes = h->sw.tail_nodes.set ? h->sw.tail_nodes.v : (gs_smoother(h->p) ? 1024 : 0);
   if (!h->bsr || nodes <= 0) return;
   for (int l = 1; l < (int)h->L.size(); ++l) {
     if (h->L[l].coarsest) return;
@@ -6429,7 +6351,7 @@ void set_tail_level(DeviceHandle* h) {
 }
 
 void apply_k_layout_knob(DeviceHandle* h) {
-  if (!h->bsr || h->L.size() < 2 || g_post_k != 2) return;
+  if (!h->bsr || h->L.size() < 2 || h->sw.post_k != 2) return;
   for (DLevel& D : h->L)
     if (!D.coarsest) set_k_split(D.KPb, 1);
 }
@@ -6445,10 +6367,10 @@ std::string layout_error(const mamg_params& p) {
   return "multicolour GS/SGS smoothers need the BSR2 layout (num_functions 2, node-aligned smoother blocks)";
 }
 
-int dev_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, DeviceHandle** out,
-               std::string* err) {
+int dev_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, const Switches& sw,
+               DeviceHandle** out, std::string* err) {
   const auto t0 = std::chrono::steady_clock::now();
-  std::unique_ptr<DeviceHandle> h(new DeviceHandle());
+  std::unique_ptr<DeviceHandle> h(new DeviceHandle(sw));
   h->p = p;
   h->device = p.device;
   int ndev = 0;
@@ -6459,7 +6381,6 @@ int dev_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, Devi
   const int nl = (int)H.levels.size();
   h->L.resize(nl);
   h->bsr = !point_gs(p) && bsr_eligible(H, A0, p);   // point-wise GS: the CSR layout, nodal hierarchies too
-  read_knobs();
   if ((gs_smoother(p) || patch_schwarz(p) || (rings_schwarz(p) && !rings_csr(p))) && !h->bsr) {
     *err = layout_error(p);
     return MAMG_ERR_UNSUPPORTED;
@@ -6474,7 +6395,7 @@ int dev_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, Devi
     const int lanesA = l == 0 ? p.spmv_lanes : 0;
     if (h->bsr && !(l == 0 && D.coarsest)) {
       // copy the level's CSRs up once and build the apply layouts on the device
-      TmpPool T;
+      TmpPool T(h->sw);
       LevelSrc S;
       if ((rc = upload_tmp(&T, Al, &S.A, err))) return rc;
       if (D.coarsest) {
@@ -6513,10 +6434,10 @@ int dev_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, Devi
         HIPCHK(hipMemcpy(D.winv, hl.winv.data(), D.n * sizeof(double), hipMemcpyHostToDevice));
       }
       if (l == 0 && rings_schwarz(p) && !H.seeds.empty()) {   // seed rings + point GS on the rest
-        TmpPool T;
+        TmpPool T(h->sw);
         if ((rc = build_rings_csr(h.get(), &T, H.seeds, p.spmv_lanes, &D, err))) return rc;
       } else if (point_gs(p)) {
-        TmpPool T;
+        TmpPool T(h->sw);
         if ((rc = build_gs_csr(h.get(), &T, D.A, l, p.spmv_lanes, &D, err))) return rc;
       }
       if (p.smoother == MAMG_SMOOTHER_POLY) {   // step smoothers w_k W (values only)
@@ -6583,9 +6504,8 @@ int dev_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, Devi
 static thread_local void* g_pre = nullptr;
 static thread_local size_t g_pre_bytes = 0;
 static thread_local int g_pre_dev = -1;
-void dev_prereserve(int device, int64_t nnz, int nranks) {
-  const char* e = opt("MAMG_PRERESERVE_B_PER_NNZ");
-  double b = e ? std::atof(e) : 20.0;
+void dev_prereserve(int device, int64_t nnz, int nranks, const Switches& sw) {
+  double b = sw.prereserve_b_per_nnz;
   if (nranks > 1) b = 1.25 * b / nranks + 0.5;
   dev_prereserve_release();
   if (b <= 0 || nnz <= 0) return;
@@ -6624,13 +6544,12 @@ void adopt_prereserve(HT* h) {
 int dev_from_ghier(GHier* G, const DevMat& A0, const mamg_params& p, DeviceHandle** out,
                    std::string* err) {
   const auto t0 = std::chrono::steady_clock::now();
-  std::unique_ptr<DeviceHandle> h(new DeviceHandle());
+  std::unique_ptr<DeviceHandle> h(new DeviceHandle(G->sw));
   h->p = p;
   h->device = p.device;
   adopt_prereserve(h.get());
   HIPCHK(hipSetDevice(p.device));
   HIPCHK(hipStreamCreateWithFlags(&h->cap, hipStreamNonBlocking));
-  read_knobs();
   h->bsr = !G->generic && !point_gs(p);   // a general block or point smoother: the CSR layout (as dev_upload)
   if ((gs_smoother(p) || patch_schwarz(p) || (rings_schwarz(p) && !rings_csr(p))) && !h->bsr) {
     *err = layout_error(p);
@@ -6659,10 +6578,10 @@ int dev_from_ghier(GHier* G, const DevMat& A0, const mamg_params& p, DeviceHandl
           HIPCHK(dev_copy(D.winv, g.winv, D.n * sizeof(double)));
         }
         if (l == 0 && rings_schwarz(p) && !G->seeds.empty()) {   // seed rings + point GS on the rest
-          TmpPool T;
+          TmpPool T(h->sw);
           if ((rc = build_rings_csr(h.get(), &T, G->seeds, p.spmv_lanes, &D, err))) return rc;
         } else if (point_gs(p)) {
-          TmpPool T;
+          TmpPool T(h->sw);
           if ((rc = build_gs_csr(h.get(), &T, D.A, l, p.spmv_lanes, &D, err))) return rc;
         }
         if (p.smoother == MAMG_SMOOTHER_POLY) {   // step smoothers w_k W (values only)
@@ -6795,6 +6714,7 @@ int dev_level_format(const DeviceHandle* h, int level) {
 }
 
 mamg_params dev_params(const DeviceHandle* h) { return h->p; }
+const Switches& dev_switches(const DeviceHandle* h) { return h->sw; }
 void dev_kregion(const DeviceHandle* h, std::vector<double>* ms, int* kept) {
   *ms = h->kregion_ms;
   *kept = h->kregion_best;
@@ -7341,6 +7261,8 @@ struct DOp {
 
 struct DistHandle {
   mamg_params p;
+  const Switches sw;                   // the switches the handle was built with (opts.h)
+  explicit DistHandle(const Switches& s) : sw(s) {}
   int rank = 0, nranks = 1, device = 0;
   int w = 2;                           // dofs per node: 2 nodal (BSR2), 1 scalar (CSR)
   ncclComm_t comm = nullptr;
@@ -7350,7 +7272,6 @@ struct DistHandle {
   size_t arena_left = 0;
   double apply_bytes = 0.0;
   int64_t nv0 = 0, o0 = 0, o1 = 0;
-  bool overlap = true;                 // MAMG_OVERLAP: interior rows during the forward halo
   bool dry = false;                    // MAMG_DIST_TEST=dry: virtual rank skips its exchanges (timing only)
   hipStream_t side = nullptr;          // stream of the interior rows
   hipEvent_t ev_in = nullptr, ev_out = nullptr;
@@ -7431,7 +7352,7 @@ DOp halo_op(int level, double* x, const DDLevel& D, int cls) {
 // Every row is computed by the same kernel code either way (same bits).
 void halo_residual(const DistHandle* h, int l, double* x, const Op& op, std::vector<DOp>* ops) {
   const DDLevel& D = h->L[l];
-  if (!(h->overlap && D.A.half)) {
+  if (!(h->sw.overlap && D.A.half)) {
     ops->push_back(halo_op(l, x, D, C_COMM));
     ops->push_back(wrap(op));
     return;
@@ -7735,7 +7656,7 @@ DOp halo_op1(int level, double* x, const DDLevel& D, int cls) {
 void halo_csr(const DistHandle* h, int l, double* x, const Op& op, bool split, std::vector<DOp>* ops) {
   const DDLevel& D = h->L[l];
   if (D.replicated) { ops->push_back(wrap(op)); return; }
-  if (!(split && h->overlap)) {
+  if (!(split && h->sw.overlap)) {
     ops->push_back(halo_op1(l, x, D, C_COMM));
     ops->push_back(wrap(op));
     return;
@@ -7910,7 +7831,7 @@ void dcycle_ops(const DistHandle* h, int l, const double* b, int64_t bs, double*
   // K on its ghost-free rows while the coarse-e halo is in flight (level 0,
   // no coarse scaling); the schedule's shape is the same on every rank (the
   // overlap and both remainder launches are emitted, maybe empty)
-  const bool kov = l == 0 && h->overlap && D.K.nr > 0 && !C.replicated && !h->p.coarse_scaling && npost >= 1 &&
+  const bool kov = l == 0 && h->sw.overlap && D.K.nr > 0 && !C.replicated && !h->p.coarse_scaling && npost >= 1 &&
                    k_ranges_ok(D.K);
   dcoarse_ops(h, l, ops, kov);
   int s0 = 0;
@@ -8422,7 +8343,7 @@ __global__ __launch_bounds__(256) void cover_kernel(int64_t cnt, const int64_t* 
 // that the ghosts within 3 hops are current before the next colour.
 int dist_patches(DistHandle* h, const DevMat& A0d, const DistLevel& P, DDLevel* D, std::string* err) {
   int rc;
-  TmpPool T;
+  TmpPool T(h->sw);
   const int64_t nv = P.nv, nloc = P.nloc, ng = (int64_t)P.ghosts.size(), nl = nloc + ng;
   const int R = h->nranks;
   TBsr B;
@@ -8503,7 +8424,7 @@ int dist_patches(DistHandle* h, const DevMat& A0d, const DistLevel& P, DDLevel* 
   int* bad = nullptr;
   if ((rc = T.alloc(&bad, 1, err))) return rc;
   HIPCHK(dev_memset(bad, 0, sizeof(int)));
-  launch_patch_inv(np, L.pperm, L.Sptr, L.Scol, D->Sgcol, L.Sval, L.pus, L.pu, bad);
+  launch_patch_inv(h->sw.patch_inv, np, L.pperm, L.Sptr, L.Scol, D->Sgcol, L.Sval, L.pus, L.pu, bad);
   HIPCHK(hipGetLastError());
   int hb = 0;
   HIPCHK(hipMemcpy(&hb, bad, sizeof(int), hipMemcpyDeviceToHost));
@@ -8576,7 +8497,7 @@ int dist_patches(DistHandle* h, const DevMat& A0d, const DistLevel& P, DDLevel* 
 int dist_rings(DistHandle* h, const DevMat& A0d, const DistLevel& P, const std::vector<int32_t>& seeds,
                const int8_t* gcol, int ngc, DDLevel* D, uint8_t** cov_owned, std::string* err) {
   int rc;
-  TmpPool T;
+  TmpPool T(h->sw);
   const mamg_params& p = h->p;
   const int64_t nv = P.nv, nloc = P.nloc, ng = (int64_t)P.ghosts.size(), nl = nloc + ng, n = A0d.n;
   const int R = h->nranks, L = p.Schwarz_maxlvl;
@@ -8813,7 +8734,7 @@ int dev_rank_ops(DistHandle* h, const GHier& G, const DevMat& A0d, const DistPla
   const GLevel& g = G.levels[l];
   DDLevel& D = h->L[l];
   const int64_t nv = P.nv, nloc = P.nloc, nc = nloc + (int64_t)P.ghosts.size();
-  TmpPool T;
+  TmpPool T(h->sw);
   int32_t* map = nullptr;
   if (!P.replicated && (rc = dev_col_map(&T, P, &map, err))) return rc;
   // W (node blocks of the owned rows)
@@ -8834,7 +8755,7 @@ int dev_rank_ops(DistHandle* h, const GHier& G, const DevMat& A0d, const DistPla
     if (!P.replicated && (rc = ghost_free_run(&T, tA, nloc, &D.ib0, &D.ib1, err)))   // overlap window
       return rc;
     bool half = false;
-    if (l == 0 && g_half && tA.nr >= g_sell_min_rows && tA.nb > 0) {   // upload_half_or_bsr
+    if (l == 0 && h->sw.half && tA.nr >= h->sw.sell_min_rows && tA.nb > 0) {   // upload_half_or_bsr
       int* bad = nullptr;
       if ((rc = T.alloc(&bad, 1, err))) return rc;
       HIPCHK(dev_memset(bad, 0, sizeof(int)));
@@ -8897,7 +8818,8 @@ int dev_rank_ops(DistHandle* h, const GHier& G, const DevMat& A0d, const DistPla
       }
       if ((rc = dev_kmerge(&T, tP, tAP, Wk, &tK, err))) return rc;
       if ((rc = finalize_bsr(h, &T, tK, &D.K, 0, false, err))) return rc;
-      if (l == 0 && g_k_sort && D.K.sell && D.K.lpr <= 1)   // rows sorted inside slices (section 4.1)
+      D.K.kvar = h->sw.k_variant;
+      if (l == 0 && h->sw.k_sort && D.K.sell && D.K.lpr <= 1)   // rows sorted inside slices (section 4.1)
         if ((rc = sort_sell_slices(h, &T, &D.K, err))) return rc;
       // K's rows without coarse ghost columns, run while the coarse-e halo is
       // in flight (level 0's SELL K: launch_msell takes row ranges)
@@ -9023,8 +8945,8 @@ int dist_check(const mamg_params& p, std::string* err) {
   return MAMG_OK;
 }
 
-int dist_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, int rank, int nranks,
-                const void* comm_id, int64_t rep_nodes, DistHandle** out, std::string* err,
+int dist_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, const Switches& sw, int rank,
+                int nranks, const void* comm_id, int64_t rep_nodes, DistHandle** out, std::string* err,
                 const GhostLists* ghosts, const GHier* G, const DevMat* A0d) {
   if (int rc = dist_check(p, err)) return rc;
   const bool gs = gs_smoother(p);
@@ -9041,7 +8963,6 @@ int dist_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, int
            "with a GPU-setup profile)";
     return MAMG_ERR_UNSUPPORTED;
   }
-  read_knobs();
   double pw[MAMG_POLY_MAX];
   const int pm = poly_weights(p, pw);
   DistPlan plan;
@@ -9051,13 +8972,13 @@ int dist_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, int
   if (G)                   // operators from the GPU hierarchy: fusion needs its A P on every level
     for (size_t l = 0; l + 1 < G->levels.size() && fuse; ++l)
       if (!G->levels[l].coarsest && G->levels[l].AP.n != G->levels[l].n) fuse = false;
-  int rc = build_dist_plan(H, A0, rank, nranks, rep_nodes, fuse, &plan, err, g_post_k != 0, kw, ghosts,
+  int rc = build_dist_plan(H, A0, rank, nranks, rep_nodes, fuse, &plan, err, sw.post_k != 0, kw, ghosts,
                            G != nullptr);
   if (rc) return rc;
   if (p.print_level >= 2)
     std::fprintf(stderr, "[mamg] rank %d/%d setup:   of which host plan    %.3f s\n", rank, nranks,
                  std::chrono::duration<double>(std::chrono::steady_clock::now() - tp0).count());
-  std::unique_ptr<DistHandle> h(new DistHandle());
+  std::unique_ptr<DistHandle> h(new DistHandle(sw));
   h->p = p;
   h->rank = rank;
   h->nranks = nranks;
@@ -9070,12 +8991,7 @@ int dist_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, int
     std::memcpy(&uid, comm_id, sizeof(uid));
     NCCLCHK(ncclCommInitRank(&h->comm, nranks, uid, rank));
   }
-  {
-    const char* e = opt("MAMG_OVERLAP");
-    h->overlap = e ? std::atoi(e) != 0 : true;
-    e = opt("MAMG_DIST_TEST");
-    h->dry = !comm_id && e && std::string(e) == "dry";
-  }
+  h->dry = !comm_id && sw.dist_test == "dry";
   HIPCHK(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
   HIPCHK(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
   HIPCHK(hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming));
@@ -9105,7 +9021,7 @@ int dist_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, int
     } else if (G) {
       // multicolour GS: the level's global colouring (every rank computes the
       // same one, as the single-GPU build_gs), then each colour's halo lists
-      TmpPool TC;
+      TmpPool TC(h->sw);
       int8_t* gcol = nullptr;
       int ncol = 0;
       const bool rl0 = l == 0 && rings && !G->seeds.empty();   // level-0 seed rings + the rest's GS
@@ -9155,6 +9071,7 @@ int dist_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, int
       }
       if (P.K.nr > 0) {
         if ((rc = upload_bsr(h.get(), P.K, &D.K, 0, err))) return rc;
+        D.K.kvar = h->sw.k_variant;
       } else if (P.PA.nr > 0) {
         if ((rc = upload_bsr(h.get(), P.PA, &D.PA, 0, err))) return rc;
       } else {
@@ -9230,6 +9147,7 @@ void dist_destroy(DistHandle* h) {
 }
 
 int dist_dofs(const DistHandle* h) { return h->w; }
+const Switches& dist_switches(const DistHandle* h) { return h->sw; }
 
 void dist_range(const DistHandle* h, int64_t* o0, int64_t* o1, int64_t* nv) {
   *o0 = h->o0; *o1 = h->o1; *nv = h->nv0;

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "host.h"
+#include "opts.h"
 
 namespace mamg {
 
@@ -39,6 +40,8 @@ struct GLevel {
 };
 
 struct GHier {
+  const Switches sw;          // the setup's snapshot of the switch table (opts.h)
+  explicit GHier(const Switches& s) : sw(s) {}
   mamg_params params;
   int device = 0;
   bool generic = false;       // some level's smoother is WB or winv: CSR apply layout
@@ -60,7 +63,7 @@ int ghier_download(const GHier& G, const CsrView& A0, Hierarchy* H, std::string*
 // row-sharded Galerkin product on nranks virtual ranks, each row compared bit
 // for bit with the unsharded (A P) and with Ac (gsetup.hip; res[6])
 int sharded_galerkin_check(const CsrView& A, const CsrView& P, const CsrView& Ac, int nranks, int device,
-                           int64_t res[6], std::string* err);
+                           const Switches& sw, int64_t res[6], std::string* err);
 // multi-GPU: download only what rank `rank` of `nranks` reads (its node rows
 // of every distributed level, replicated levels whole, no R / aggregates) and
 // compute the ghost lists on the device (build_dist_plan's `pre`); A0d is the

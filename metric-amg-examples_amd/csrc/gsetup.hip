@@ -1885,29 +1885,19 @@ __global__ __launch_bounds__(256) void stage_copy_kernel(int64_t n, const uint8_
 // of the free HBM (MAMG_SPGEMM_STAGE_STRIDE caps it: tests of the long-row
 // list).  Same kernel code, same rank sort: the same bits.
 // MAMG_SPGEMM_PAIR=0: the staged count pass row by row (A/B, tests)
-bool spgemm_pair_on() {
-  const char* e = opt("MAMG_SPGEMM_PAIR");
-  return e ? std::atoi(e) != 0 : true;
-}
 
 // The staging area is the per-device staging block of dmem.h (StageLease),
 // at most min(MAMG_SPGEMM_STAGE_GB, a quarter of the free HBM), kept for the
 // process until the setup cache is released; used in null-stream order, as
 // the setup temporaries are, and held by one product at a time.
-size_t stage_cap_bytes() {
-  const char* e = opt("MAMG_SPGEMM_STAGE_GB");
-  const double cap_gb = e ? std::atof(e) : 16.0;
-  return cap_gb > 0.0 ? (size_t)(cap_gb * 1e9) : 0;
+size_t stage_cap_bytes(const Switches& sw) {
+  return sw.spgemm_stage_gb > 0.0 ? (size_t)(sw.spgemm_stage_gb * 1e9) : 0;
 }
 
-int64_t spgemm_stage_stride(int64_t n, size_t pool) {
-  const char* e = opt("MAMG_SPGEMM_STAGE_GB");
-  if (e && std::atof(e) <= 0.0) return 0;
-  e = opt("MAMG_SPGEMM_STAGE_STRIDE");
-  const int64_t smax = e ? std::atoll(e) : 128;
-  if (n <= 0) return 0;
+int64_t spgemm_stage_stride(const Switches& sw, int64_t n, size_t pool) {
+  if (sw.spgemm_stage_gb <= 0.0 || n <= 0) return 0;
   for (int64_t s : {128, 64, 32, 16})
-    if (s <= smax && (double)n * (double)s * 12.0 <= (double)pool) return s;
+    if (s <= sw.spgemm_stage_stride && (double)n * (double)s * 12.0 <= (double)pool) return s;
   return 0;
 }
 
@@ -1931,9 +1921,9 @@ int spgemm_gl(GHier* G, const DevMat& A, BS B, int64_t ncols, DevMat* C, std::st
   RCHK(S.alloc(&ctr, 5, err));
   HIPCHK(dev_memset(ctr, 0, 5 * sizeof(int)));
   SpStage stg;
-  StageLease lease(stage_cap_bytes());     // held until the product returns
+  StageLease lease(stage_cap_bytes(G->sw));     // held until the product returns
   void* pool = lease.p;
-  stg.stride = pool ? spgemm_stage_stride(n, lease.bytes) : 0;
+  stg.stride = pool ? spgemm_stage_stride(G->sw, n, lease.bytes) : 0;
   int32_t* l3 = nullptr;
   int n3 = 0;
   if (stg.stride) {   // values first (8-byte aligned), then the columns
@@ -1965,7 +1955,7 @@ int spgemm_gl(GHier* G, const DevMat& A, BS B, int64_t ncols, DevMat* C, std::st
     int32_t* cc = pass ? C->col : nullptr;
     double* cv = pass ? C->val : nullptr;
     if (pass == 0) {
-      if (pair && stg.stride && n % 2 == 0 && spgemm_pair_on()) {   // only when most pairs agree
+      if (pair && stg.stride && n % 2 == 0 && G->sw.spgemm_pair) {   // only when most pairs agree
         unsigned long long* dc = nullptr;
         RCHK(shards_alloc(&S, &dc, err));
         const int64_t ns = (n / 2 + PAIR_SAMPLE - 1) / PAIR_SAMPLE;   // pairs sampled
@@ -1975,7 +1965,7 @@ int spgemm_gl(GHier* G, const DevMat& A, BS B, int64_t ncols, DevMat* C, std::st
         RCHK(shards_read(dc, false, &nd, err));
         pair = nd * 8 <= (unsigned long long)ns;
       }
-      if (pair && stg.stride && n % 2 == 0 && spgemm_pair_on()) {
+      if (pair && stg.stride && n % 2 == 0 && G->sw.spgemm_pair) {
         int32_t* lm = nullptr;
         int* nm = nullptr;
         RCHK(S.alloc(&lm, n, err));
@@ -2277,8 +2267,7 @@ int aggregate(GHier* G, const DevMat& A, int64_t nv, int level, double theta, bo
     RCHK(to_host(&Gr.nnz, Gr.ptr + nv, 1, err));
     RCHK(S.alloc(&Gr.col, Gr.nnz, err));
     RCHK(S.alloc(&Gr.val, Gr.nnz, err));
-    const char* fe = opt("MAMG_CSR2BSR_FILL");   // 0: the column + value staged merge (tests, A/B)
-    if (fe && std::atoi(fe) == 0) {
+    if (!G->sw.csr2bsr_fill) {   // the column + value staged merge (tests, A/B)
       node_graph_kernel<true><<<g, RS_NODES>>>(nv, A.ptr, A.col, A.val, Gr.ptr, Gr.col, Gr.val);
     } else {
       Scratch TS;
@@ -2349,8 +2338,7 @@ int aggregate(GHier* G, const DevMat& A, int64_t nv, int level, double theta, bo
   RCHK(S.alloc(&m1, nv, err));
   RCHK(shards_alloc(&S, &und, err));
   mis_init_kernel<<<nblk(nv), 256>>>(nv, Gr.ptr, flag, level, state, low, nonisol);
-  const char* ms = opt("MAMG_MIS_STAGED");   // 0: the lane-per-row walks (tests, A/B)
-  const bool mis_staged = ms ? std::atoi(ms) != 0 : true;
+  const bool mis_staged = G->sw.mis_staged;   // 0: the lane-per-row walks (tests, A/B)
   for (int rounds = 0;; ++rounds) {
     if (rounds > 10000) { *err = "mis2 did not converge"; return MAMG_ERR_SETUP; }
     RCHK(shards_zero(und));
@@ -2606,8 +2594,8 @@ int block_inverse_dev(GHier* G, const DevMat& A, const SeedBlocks& B, Scratch* S
 
 // rho_B = max_i sum_j |(D A)_ij| (setup.cpp block_rho: SMMP row of D A, sorted
 // columns, zeros skipped) through the hash SpGEMM
-int block_rho_dev(const DevMat& D, const DevMat& A, double* rho, std::string* err) {
-  GHier tmp;
+int block_rho_dev(const Switches& sw, const DevMat& D, const DevMat& A, double* rho, std::string* err) {
+  GHier tmp(sw);
   DevMat C;
   RCHK(spgemm(&tmp, D, BCsr{A.ptr, A.col, A.val}, A.m, &C, err, A.n ? (double)A.nnz / (double)A.n : 1.0));
   Scratch S;
@@ -2991,7 +2979,7 @@ int gpu_setup(const DevMat& A0, const int32_t* idofs, int64_t n_idofs, const mam
       } else {
         RCHK(block_inverse_dev(G, cur, B, &S, &L.WB, err));
         double rho = 0.0;
-        RCHK(block_rho_dev(L.WB, cur, &rho, err));
+        RCHK(block_rho_dev(G->sw, L.WB, cur, &rho, err));
         scale_vals_kernel<<<nblk(L.WB.nnz), 256>>>(L.WB.nnz, p.relaxation / rho, L.WB.val);
         HIPCHK(hipGetLastError());
       }
@@ -3025,7 +3013,7 @@ int gpu_setup(const DevMat& A0, const int32_t* idofs, int64_t n_idofs, const mam
       }
       const double w = p.sa_omega / rho_sa;
       L.w_sa = w;
-      GHier tmp;                    // A T lives only until P is built
+      GHier tmp(G->sw);             // A T lives only until P is built
       DevMat AT;
       RCHK(spgemm(&tmp, cur, BTent{agg, nv, nagg}, 2 * nagg, &AT, err, 1.0, true));
       L.P.n = n;
@@ -3046,7 +3034,7 @@ int gpu_setup(const DevMat& A0, const int32_t* idofs, int64_t n_idofs, const mam
     } else if (pointSA) {           // point SA: c_i = (sa_omega / rho) / a_ii
       const double w = p.sa_omega / PL.rho;
       L.w_sa = w;
-      GHier tmp;
+      GHier tmp(G->sw);
       DevMat AT;
       RCHK(spgemm(&tmp, cur, BTent{agg, nv, nagg}, nf * nagg, &AT, err, 1.0));
       L.P.n = n;
@@ -3301,8 +3289,7 @@ int upload_a0(const CsrView& A, GHier* G, DevMat* D, std::string* err) {
   // pinned buffers on the calling thread, ~36 GB/s for one thread.  A/B at
   // nrefs=6 (MAMG_UPLOAD_THREADS, profiles/r05_upload_threads.txt): k = 1
   // 348-397 ms, 2 323 ms (default), 4 335 ms
-  const char* e = opt("MAMG_UPLOAD_THREADS");
-  const int k = e ? std::max(1, std::min(16, std::atoi(e))) : 2;
+  const int k = G->sw.upload_threads;
   if (k == 1) {
     HIPCHK(hipMemcpy(D->ptr, A.ptr, (A.n + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     if (D->nnz) {
@@ -3427,14 +3414,14 @@ std::vector<int64_t> node_rows(int64_t lo, int64_t hi, int64_t h) {
 }  // namespace
 
 int sharded_galerkin_check(const CsrView& Av, const CsrView& Pv, const CsrView& Acv, int nranks, int device,
-                           int64_t res[6], std::string* err) {
+                           const Switches& sw, int64_t res[6], std::string* err) {
   for (int k = 0; k < 6; ++k) res[k] = 0;
   if (nranks < 1 || Av.n != Av.m || Av.n % 2 || Pv.n != Av.n || Pv.m % 2 || Acv.n != Pv.m || Acv.m != Pv.m) {
     *err = "sharded Galerkin check: A (2 nv x 2 nv), P (2 nv x 2 nc) and A_c (2 nc x 2 nc), field-major, nranks >= 1";
     return MAMG_ERR_ARG;
   }
   HIPCHK(hipSetDevice(device));
-  GHier G;
+  GHier G(sw);
   G.device = device;
   const int64_t n = Av.n, nv = n / 2, m = Pv.m, nc = m / 2;
   const Csr A = view_csr(Av), P = view_csr(Pv), Ac = view_csr(Acv);
@@ -3469,7 +3456,7 @@ int sharded_galerkin_check(const CsrView& Av, const CsrView& Pv, const CsrView& 
       }
       Pext.ptr.push_back((int64_t)Pext.col.size());
     }
-    GHier T;
+    GHier T(sw);
     T.device = device;
     DevMat dAp, dPe, dC;
     RCHK(up_csr(&T, Ap, &dAp, err));
@@ -3509,7 +3496,7 @@ int sharded_galerkin_check(const CsrView& Av, const CsrView& Pv, const CsrView& 
       }
       APe.ptr.push_back((int64_t)APe.col.size());
     }
-    GHier T;
+    GHier T(sw);
     T.device = device;
     DevMat dRp, dAPe, dC;
     Csr Cp;

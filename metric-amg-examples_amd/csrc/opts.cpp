@@ -1,12 +1,13 @@
 // opts.cpp -- process-wide switch table (opts.h).
 #include "opts.h"
 
+#include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <map>
 #include <mutex>
-#include <string>
 
 #ifndef MAMG_DIAG
 #define MAMG_DIAG 0
@@ -15,37 +16,10 @@
 namespace mamg {
 namespace {
 
-// every switch of the product library, with the default it stands for
-// (DESIGN.md section 4 gives the measurements behind each default)
 constexpr const char* kNames[] = {
-    "MAMG_POST_K",                // 1: K = P - W A P after the coarse correction; 0: [P | AP]; 2: split K
-    "MAMG_SELL_MIN_ROWS",         // rows from which level 0's operators take SELL-64 (1 << 20)
-    "MAMG_MSELL_MIN_ROWS",        // rows from which coarse levels take multi-lane SELL-64 (never)
-    "MAMG_TAIL_NODES",            // coarse tail: first level with at most this many nodes (auto)
-    "MAMG_TAIL_VL",               // coarse tail: lanes per row cap (4)
-    "MAMG_TAIL_LDS",              // coarse tail: LDS program size (auto)
-    "MAMG_TAIL_PROG_LDS",         // 1: coarse tail's op descriptors copied into LDS; 0: scalar loads (default)
-    "MAMG_TAIL_RES",              // 1: coarse tail's operators held in registers, one row per thread
-    "MAMG_HALF",                  // 1: half-symmetric level-0 A; 0: SELL-64
-    "MAMG_HALF_BANDS",            // 1: plane-band schedule of the half-symmetric kernel
-    "MAMG_R_BANDS",               // 1: plane-band schedule of the level-0 restriction
-    "MAMG_K_SORT",                // 1: K rows sorted by length inside SELL slices
-    "MAMG_K_COL16",               // 1: level-0 K's columns as 16-bit offsets from a per-slice base
-    "MAMG_FUSE_RBD",              // which restrictions write the next first sweep (2)
-    "MAMG_CSR2BSR_FILL",          // 1: column-only LDS fill of CSR -> BSR2; 0: staged merge
-    "MAMG_KREGION_TRIES",         // K value regions timed at upload
-    "MAMG_KREGION_BUDGET_MS",     // time budget of that search
-    "MAMG_REHOME",                // 1: operators re-homed after the setup
-    "MAMG_PRERESERVE_B_PER_NNZ",  // layout reservation, bytes per A0 entry (20)
-    "MAMG_POISON",                // 1: new double arrays start as NaN bytes (tests)
-    "MAMG_OVERLAP",               // multi-GPU: interior rows during the halo (1)
-    "MAMG_DIST_TEST",             // multi-GPU virtual ranks: "dry" skips exchanges (timing)
-    "MAMG_SPGEMM_PAIR",           // 1: staged count pass over node row pairs
-    "MAMG_SPGEMM_STAGE_GB",       // staging block cap (16; 0: unstaged products)
-    "MAMG_SPGEMM_STAGE_STRIDE",   // staging stride cap (128)
-    "MAMG_MIS_STAGED",            // 1: MIS-2 maxima over staged rows
-    "MAMG_UPLOAD_THREADS",        // host threads copying A0 (2)
-    "MAMG_PATCH_INV",             // node-patch inverses: 1 one patch per wave (round 5), 2 two per wave, 3 matrix cores (default)
+#define X(name, field, type, def) #name,
+    MAMG_SWITCHES(X)
+#undef X
 };
 
 struct Table {
@@ -63,21 +37,42 @@ bool known(const char* name) {
     if (std::strcmp(k, name) == 0) return true;
   return false;
 }
-
-}  // namespace
-
-const char* opt(const char* name) {
-  Table& t = table();
-  {
-    std::lock_guard<std::mutex> g(t.m);
-    auto it = t.set.find(name);
-    if (it != t.set.end()) return t.vals[it->second].c_str();
-  }
+// with t.m held
+const char* find(Table& t, const char* name) {
+  auto it = t.set.find(name);
+  if (it != t.set.end()) return t.vals[it->second].c_str();
 #if MAMG_DIAG
   return std::getenv(name);
 #else
   return nullptr;
 #endif
+}
+
+// one parser and one printer per field type (e != nullptr)
+void parse(const char* e, int* v) { *v = std::atoi(e); }
+void parse(const char* e, int64_t* v) { *v = std::atoll(e); }
+void parse(const char* e, double* v) { *v = std::atof(e); }
+void parse(const char* e, bool* v) { *v = std::atoi(e) != 0; }
+void parse(const char* e, std::string* v) { *v = e; }
+void parse(const char* e, AutoCount* v) { *v = {true, std::atoll(e)}; }
+
+std::string show(int v) { return std::to_string(v); }
+std::string show(int64_t v) { return std::to_string(v); }
+std::string show(bool v) { return v ? "1" : "0"; }
+std::string show(const std::string& v) { return v; }
+std::string show(const AutoCount& v) { return v.set ? std::to_string(v.v) : "auto"; }
+std::string show(double v) {
+  char b[32];
+  std::snprintf(b, sizeof b, "%g", v);
+  return b;
+}
+
+}  // namespace
+
+const char* opt(const char* name) {
+  Table& t = table();
+  std::lock_guard<std::mutex> g(t.m);
+  return find(t, name);
 }
 
 bool set_opt(const char* name, const char* value) {
@@ -102,6 +97,33 @@ const char* opt_names() {
       t.names += k;
     }
   return t.names.c_str();
+}
+
+Switches read_switches() {
+  Switches s;
+  {
+    Table& t = table();
+    std::lock_guard<std::mutex> g(t.m);
+#define X(name, field, type, def) \
+    if (const char* e = find(t, #name)) parse(e, &s.field);
+    MAMG_SWITCHES(X)
+#undef X
+  }
+  s.tail_vl = std::max(1, std::min(64, s.tail_vl));
+  s.upload_threads = std::max(1, std::min(16, s.upload_threads));
+  if (s.patch_inv < 1 || s.patch_inv > (MAMG_DIAG ? 5 : 3)) s.patch_inv = 3;   // 4, 5: diagnosis variants
+#if MAMG_DIAG
+  if (const char* e = std::getenv("MAMG_K_VARIANT")) s.k_variant = std::atoi(e);
+#endif
+  return s;
+}
+
+std::string format_switches(const Switches& s) {
+  std::string out;
+#define X(name, field, type, def) out += (out.empty() ? "" : ",") + std::string(#name "=") + show(s.field);
+  MAMG_SWITCHES(X)
+#undef X
+  return out;
 }
 
 }  // namespace mamg

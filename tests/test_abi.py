@@ -334,3 +334,59 @@ def test_setup_cache_limit_api(lib_built):
     assert lim.value == 5 * 10**9 and idle.value == 0
     M._lib.check(L.mamg_set_setup_cache_limit(-1))
     assert L.mamg_setup_cache_bytes(64, None, None) == -1
+
+
+# every switch as a setup reads it with nothing set (mamg_handle_options(NULL));
+# the values this change did not restate are the parent's, at the cited lines
+DEFAULT_OPTIONS = {
+    'MAMG_POST_K': '1', 'MAMG_SELL_MIN_ROWS': str(1 << 20), 'MAMG_MSELL_MIN_ROWS': str(1 << 40),
+    'MAMG_TAIL_NODES': 'auto', 'MAMG_TAIL_VL': '4', 'MAMG_TAIL_LDS': '1', 'MAMG_TAIL_PROG_LDS': '0',
+    'MAMG_TAIL_RES': '1', 'MAMG_HALF': '1', 'MAMG_HALF_BANDS': '1', 'MAMG_R_BANDS': '1', 'MAMG_K_SORT': '1',
+    'MAMG_K_COL16': '1', 'MAMG_FUSE_RBD': '2',
+    'MAMG_CSR2BSR_FILL': '1',            # device.hip:3704 (on unless 0) and gsetup.hip:2280 (off when 0) agree
+    'MAMG_KREGION_TRIES': '4', 'MAMG_KREGION_BUDGET_MS': '200',
+    'MAMG_REHOME': '1',                  # device.hip:6357: off only when given as 0
+    'MAMG_PRERESERVE_B_PER_NNZ': '20',   # device.hip:6587: atof, default 20.0
+    'MAMG_POISON': '0', 'MAMG_OVERLAP': '1', 'MAMG_DIST_TEST': '', 'MAMG_SPGEMM_PAIR': '1',
+    'MAMG_SPGEMM_STAGE_GB': '16', 'MAMG_SPGEMM_STAGE_STRIDE': '128',
+    'MAMG_MIS_STAGED': '1',              # gsetup.hip:2352: on unless given as 0
+    'MAMG_UPLOAD_THREADS': '2',          # gsetup.hip:3304: default 2, clamped to [1, 16]
+    'MAMG_PATCH_INV': '3',               # device.hip:2335: 1 and 2 as given, anything else 3
+}
+
+
+def test_resolved_options_defaults(lib_built):
+    import metric_amg_examples_amd as M
+    got = M._lib.resolved_options()
+    assert got == DEFAULT_OPTIONS
+    assert list(got) == M._lib.option_names() == list(PRODUCT_OPTIONS)
+
+
+@pytest.mark.parametrize('name,given,want', [
+    ('MAMG_TAIL_VL', '0', '1'), ('MAMG_TAIL_VL', '1000', '64'),      # clamped to [1, 64]
+    ('MAMG_HALF', '7', '1'), ('MAMG_HALF', '0', '0'),                # a flag: nonzero is on
+    ('MAMG_SPGEMM_STAGE_GB', '0', '0'),                              # <= 0: staging off
+    ('MAMG_TAIL_NODES', '0', '0'),                                   # given as 0 (off) is not unset (auto)
+    ('MAMG_TAIL_LDS', '0', '0'), ('MAMG_TAIL_RES', '0', '0'), ('MAMG_TAIL_PROG_LDS', '1', '1'),
+    ('MAMG_UPLOAD_THREADS', '99', '16'), ('MAMG_PATCH_INV', '7', '3'), ('MAMG_PATCH_INV', '2', '2'),
+    ('MAMG_DIST_TEST', 'rows', 'rows'), ('MAMG_KREGION_BUDGET_MS', '12.5', '12.5'),
+])
+def test_resolved_options_parsing(lib_built, name, given, want):
+    import metric_amg_examples_amd as M
+    from conftest import set_opt
+    set_opt(name, given)
+    got = M._lib.resolved_options()
+    assert got[name] == want
+    assert {k: v for k, v in got.items() if k != name} == {k: v for k, v in DEFAULT_OPTIONS.items() if k != name}
+    M._lib.set_option(name, None)                                    # reset: the default again
+    assert M._lib.resolved_options() == DEFAULT_OPTIONS
+
+
+def test_options_buffer_too_small(lib_built):
+    import metric_amg_examples_amd as M
+    L = M._lib.lib()
+    need = len(','.join('%s=%s' % kv for kv in DEFAULT_OPTIONS.items()))
+    buf = C.create_string_buffer(need + 1)
+    assert L.mamg_handle_options(None, buf, need) == -1 and L.mamg_dist_options(None, buf, need) == -1
+    assert L.mamg_handle_options(None, buf, need + 1) == 0 and len(buf.value) == need
+    assert L.mamg_dist_options(None, buf, need + 1) == 0 and len(buf.value) == need
