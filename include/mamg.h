@@ -397,6 +397,45 @@ int mamg_dist_virtual_spmv(mamg_dhandle** hs, int n, const double** d_x, double*
  * once (tests: the graph path against the eager lockstep run). */
 int mamg_dist_virtual_apply_graph(mamg_dhandle** hs, int n, const double** d_r, double** d_z,
                                   void* stream);
+/* Device-resident PCG on the rank's local slices (a contiguous run of
+ * w * nloc doubles: field-major on a nodal handle, plain on a scalar one):
+ * mamg_pcg_device's loop and semantics on N ranks.  x0 = d_x_local on entry;
+ * residuals[k] = sqrt(<r, B r>) (maxiter + 1 entries), alphas / betas maxiter
+ * entries, *niters = len(residuals) - 1; MAMG_ERR_BREAKDOWN with the messages
+ * of mamg_pcg_device.  stop_type 0: cbc.block's rule (tol absolute unless
+ * relativeconv); 1: HAZmath's linear_stop_type 1, ||r||_2 <= tol ||b||_2 with
+ * ||b|| = 0 taken as 1 (one more dot per iteration, fused into the x / r
+ * update); rnorms[maxiter + 1] then receives ||r||_2 per iteration and may be
+ * NULL for stop_type 0.  Any other stop_type, a NULL handle or buffer and
+ * maxiter < 0 return MAMG_ERR_ARG before anything touches the GPU.
+ * Every scalar lives in HBM.  One iteration is one op list -- halo + A_loc,
+ * <d,q>, alpha, x / r update, the apply, <r,z>, beta + stop test, d update --
+ * replayed as one hipGraph per (d_x_local, maxiter, stop_type) on an RCCL or
+ * single-rank handle (RCCL calls inside the capture; eager after a failed
+ * capture) and run op by op through the callbacks on a host-staged handle.
+ * Each rank writes its share of a dot to its own slot of a zeroed P-vector,
+ * the P-vector is all-reduced and every rank adds the slots in rank order,
+ * so all ranks hold the same bits and issue the same number of iterations;
+ * the host stays one iteration ahead and an iteration queued after the
+ * stopping one runs its exchanges but leaves x, r and d untouched.
+ * Replaces the ConjGrad loop of src/bidomain_3d.py:149 on N GPUs. */
+int mamg_dist_pcg_device(mamg_dhandle* h, const double* d_b_local, double* d_x_local,
+                         double tol, int maxiter, int relativeconv, int stop_type,
+                         double* residuals, double* rnorms, double* alphas, double* betas,
+                         int* niters, void* stream);
+/* Test mode, as mamg_dist_virtual_apply: the n virtual ranks' iterations in
+ * lockstep on one device; graph != 0 captures one lockstep iteration once and
+ * replays it.  Every rank's state is compared with rank 0's byte for byte
+ * whenever it is read back (a difference: MAMG_ERR_SETUP, the message names
+ * the iteration); the histories are rank 0's. */
+int mamg_dist_virtual_pcg(mamg_dhandle** hs, int n, const double** d_b, double** d_x,
+                          double tol, int maxiter, int relativeconv, int stop_type, int graph,
+                          double* residuals, double* rnorms, double* alphas, double* betas,
+                          int* niters, void* stream);
+/* what one PCG iteration issues on this rank, counted as by
+ * mamg_dist_apply_launches: the SpMV, the apply, the PCG kernels and two
+ * all-reduces of the dots */
+int mamg_dist_pcg_launches(const mamg_dhandle* h, int stop_type, int64_t counts[5]);
 void mamg_dist_destroy(mamg_dhandle* h);
 /* Host-staged exchange backend: a pluggable transport for a handle made
  * with comm_id == NULL (one process per rank, e.g. torch.distributed gloo).

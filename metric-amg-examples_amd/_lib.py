@@ -118,6 +118,12 @@ SIGNATURES = {
     'mamg_dist_virtual_apply': (C.c_int, [C.POINTER(VP), C.c_int, C.POINTER(VP), C.POINTER(VP), VP]),
     'mamg_dist_spmv_device': (C.c_int, [VP, VP, VP, VP]),
     'mamg_dist_virtual_spmv': (C.c_int, [C.POINTER(VP), C.c_int, C.POINTER(VP), C.POINTER(VP), VP]),
+    'mamg_dist_pcg_device': (C.c_int, [VP, VP, VP, C.c_double, C.c_int, C.c_int, C.c_int, P_F64, P_F64,
+                                       P_F64, P_F64, P_I32, VP]),
+    'mamg_dist_virtual_pcg': (C.c_int, [C.POINTER(VP), C.c_int, C.POINTER(VP), C.POINTER(VP), C.c_double,
+                                        C.c_int, C.c_int, C.c_int, C.c_int, P_F64, P_F64, P_F64, P_F64,
+                                        P_I32, VP]),
+    'mamg_dist_pcg_launches': (C.c_int, [VP, C.c_int, C.POINTER(C.c_int64)]),
     'mamg_dist_destroy': (None, [VP]),
     'mamg_dist_set_exchange': (C.c_int, [VP, C.POINTER(mamg_exchange)]),
     'mamg_setup': (C.c_int, [C.POINTER(mamg_csr), P_I32, C.c_int64, C.POINTER(mamg_params),

@@ -687,6 +687,13 @@ class DistMetricAMG:
         _lib.check(self._L.mamg_dist_apply_launches(self._h, c))
         return dict(zip(('kernels', 'p2p_groups', 'p2p_messages', 'allreduces', 'stream_forks'), list(c)))
 
+    def pcg_launches(self, stop_type=None):
+        """The same table for one iteration of the device-resident PCG
+        (mamg_dist_pcg_launches): SpMV, apply, PCG kernels, two all-reduces."""
+        c = (C.c_int64 * 5)()
+        _lib.check(self._L.mamg_dist_pcg_launches(self._h, int(stop_type or 0), c))
+        return dict(zip(('kernels', 'p2p_groups', 'p2p_messages', 'allreduces', 'stream_forks'), list(c)))
+
     def apply_device(self, r, z, stream=None):
         _lib.check(self._L.mamg_dist_apply_device(self._h, _device_ptr(r), _device_ptr(z),
                                                   _stream_ptr(stream)))

@@ -720,6 +720,64 @@ int mamg_dist_virtual_apply(mamg_dhandle** hs, int n, const double** d_r, double
   GUARD_END
 }
 
+namespace {
+// the argument errors of the distributed PCG entries, before anything touches the GPU
+int dist_pcg_args(int maxiter, int stop_type, const double* residuals, const double* rnorms,
+                  const double* alphas, const double* betas, const int* niters) {
+  if (stop_type != 0 && stop_type != 1) {
+    set_error("stop_type must be 0 (cbc.block) or 1 (||r|| <= tol ||b||)");
+    return MAMG_ERR_ARG;
+  }
+  if (maxiter < 0) { set_error("maxiter must be >= 0"); return MAMG_ERR_ARG; }
+  if (!residuals || !alphas || !betas || !niters) { set_error("null history buffer"); return MAMG_ERR_ARG; }
+  if (stop_type == 1 && !rnorms) { set_error("stop_type 1 needs the rnorms history"); return MAMG_ERR_ARG; }
+  return MAMG_OK;
+}
+}  // namespace
+
+int mamg_dist_pcg_device(mamg_dhandle* h, const double* d_b_local, double* d_x_local, double tol, int maxiter,
+                         int relativeconv, int stop_type, double* residuals, double* rnorms, double* alphas,
+                         double* betas, int* niters, void* stream) {
+  GUARD_BEGIN
+  if (!h) { set_error("null handle"); return MAMG_ERR_ARG; }
+  int rc = dist_pcg_args(maxiter, stop_type, residuals, rnorms, alphas, betas, niters);
+  if (rc) return rc;
+  std::string err;
+  rc = mamg::dist_pcg(h->d, d_b_local, d_x_local, tol, maxiter, relativeconv, stop_type, residuals, rnorms,
+                      alphas, betas, niters, stream, &err);
+  if (rc) set_error(err);
+  return rc;
+  GUARD_END
+}
+
+int mamg_dist_virtual_pcg(mamg_dhandle** hs, int n, const double** d_b, double** d_x, double tol, int maxiter,
+                          int relativeconv, int stop_type, int graph, double* residuals, double* rnorms,
+                          double* alphas, double* betas, int* niters, void* stream) {
+  GUARD_BEGIN
+  if (!hs || n < 1 || !d_b || !d_x) { set_error("null argument"); return MAMG_ERR_ARG; }
+  for (int i = 0; i < n; ++i)
+    if (!hs[i]) { set_error("null handle"); return MAMG_ERR_ARG; }
+  int rc = dist_pcg_args(maxiter, stop_type, residuals, rnorms, alphas, betas, niters);
+  if (rc) return rc;
+  std::vector<mamg::DistHandle*> H(n);
+  std::vector<const double*> B(d_b, d_b + n);
+  std::vector<double*> X(d_x, d_x + n);
+  for (int i = 0; i < n; ++i) H[i] = hs[i]->d;
+  std::string err;
+  rc = mamg::dist_virtual_pcg(H, B, X, tol, maxiter, relativeconv, stop_type, graph, residuals, rnorms, alphas,
+                              betas, niters, stream, &err);
+  if (rc) set_error(err);
+  return rc;
+  GUARD_END
+}
+
+int mamg_dist_pcg_launches(const mamg_dhandle* h, int stop_type, int64_t counts[5]) {
+  if (!h || !counts) { set_error("null argument"); return MAMG_ERR_ARG; }
+  if (stop_type != 0 && stop_type != 1) { set_error("stop_type must be 0 or 1"); return MAMG_ERR_ARG; }
+  mamg::dist_pcg_launches(h->d, stop_type, counts);
+  return MAMG_OK;
+}
+
 int mamg_dist_set_exchange(mamg_dhandle* h, const mamg_exchange* ex) {
   GUARD_BEGIN
   if (!h || !ex || !ex->sendrecv || !ex->allreduce) { set_error("null argument"); return MAMG_ERR_ARG; }

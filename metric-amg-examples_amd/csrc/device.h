@@ -91,5 +91,19 @@ int dist_apply_graph(DistHandle* h, const double* d_r, double* d_z, void* stream
 int dist_graph_prepare(DistHandle* h, const double* d_r, double* d_z, std::string* err);
 int dist_virtual_apply_graph(const std::vector<DistHandle*>& hs, const std::vector<const double*>& r,
                              const std::vector<double*>& z, void* stream, std::string* err);
+// device-resident PCG on the rank's local slices (dev_pcg's loop with the
+// halo exchanges and the dots' all-reduces inside each iteration); stop 0:
+// cbc.block's rule, 1: ||r||_2 <= tol ||b||_2 (rnorms then required)
+int dist_pcg(DistHandle* h, const double* d_b, double* d_x, double tol, int maxiter, int relativeconv,
+             int stop, double* residuals, double* rnorms, double* alphas, double* betas, int* niters,
+             void* stream, std::string* err);
+// the same on virtual ranks in lockstep; graph: one captured lockstep
+// iteration replayed; every rank's state compared with rank 0's
+int dist_virtual_pcg(const std::vector<DistHandle*>& hs, const std::vector<const double*>& b,
+                     const std::vector<double*>& x, double tol, int maxiter, int relativeconv, int stop,
+                     int graph, double* residuals, double* rnorms, double* alphas, double* betas, int* niters,
+                     void* stream, std::string* err);
+// what one PCG iteration issues on this rank (counts as dist_apply_launches)
+void dist_pcg_launches(const DistHandle* h, int stop, int64_t c[5]);
 
 }  // namespace mamg

@@ -1002,6 +1002,183 @@ __global__ __launch_bounds__(256) void pcg_d_kernel(int64_t n, const PcgState* _
   else d[i] = z[i] + st->beta * d[i];
 }
 
+// ---- the same loop on N row-partitioned ranks (dist_pcg).  A
+// rank's dot is its block partials summed in a fixed order into ONE double,
+// written to slot [rank] of a P-vector whose other slots are zero; the
+// all-reduce of the P-vector only ever adds zeros to it (exact), so every
+// rank and every backend reads the same P doubles, and the alpha / beta
+// kernels add them in rank order: the same bits everywhere, whatever the
+// reduction tree.  rr / thr: ||r||^2 and stop_type 1's threshold tol ||b||.
+struct DPcgState {
+  double rz, dq, alpha, beta, tol, rr, thr;
+  int it, maxiter, active, run, status, stop;
+};
+
+// what the distributed PCG ops of one (x, maxiter, stop_type) plan work on
+// (device pointers; the struct itself lives on the host, owned by the plan)
+struct DPcgCtx {
+  DPcgState* st = nullptr;
+  int64_t n = 0;                  // w * nloc owned entries
+  int P = 1, rank = 0, stop = 0;
+  double *x = nullptr, *r = nullptr, *z = nullptr, *d = nullptr, *q = nullptr;
+  double* part = nullptr;         // 3 * DOT_BLOCKS block partials (dot 0, ||r||^2, ||b||^2)
+  double* pv = nullptr;           // 3 P-vectors
+  double *res = nullptr, *rn = nullptr, *al = nullptr, *be = nullptr;   // histories
+  // the solve in flight (start-up ops only; the iteration reads none of them)
+  const double* b = nullptr;
+  double tol = 0.0;
+  int relconv = 0, maxiter = 0;
+};
+
+__device__ __forceinline__ void block_part256(double s, double* __restrict__ out) {
+  __shared__ double red[4];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) *out = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();
+}
+
+// part[block] = this block's share of <a, b> (DOT_BLOCKS blocks, grid stride)
+__global__ __launch_bounds__(256) void dpcg_dot_kernel(int64_t n, const double* __restrict__ a,
+                                                       const double* __restrict__ b, double* __restrict__ part) {
+  double s = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    s += a[i] * b[i];
+  block_part256(s, part + blockIdx.x);
+}
+
+// the rank's nd dots: partials part[k * nb .. ) -> pv[k * P + rank], zeros in
+// the other ranks' slots (one block)
+__global__ __launch_bounds__(256) void dpcg_slot_kernel(int nb, int nd, const double* __restrict__ part,
+                                                        double* __restrict__ pv, int P, int rank) {
+  __shared__ double tot[3];
+  for (int k = 0; k < nd; ++k) {
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nb; i += 256) s += part[(int64_t)k * nb + i];
+    block_part256(s, &tot[k]);
+  }
+  for (int i = threadIdx.x; i < nd * P; i += 256) pv[i] = (i % P == rank) ? tot[i / P] : 0.0;
+}
+
+__device__ __forceinline__ double dpcg_rank_sum(const double* __restrict__ pv, int P) {
+  double s = 0.0;
+  for (int q = 0; q < P; ++q) s += pv[q];   // rank order, on every rank
+  return s;
+}
+
+// start-up: r = b - q (q = A x0), partials of ||r||^2 and ||b||^2 for stop_type 1
+__global__ __launch_bounds__(256) void dpcg_r0_kernel(int64_t n, int stop, const double* __restrict__ b,
+                                                      const double* __restrict__ q, double* __restrict__ r,
+                                                      double* __restrict__ part, int nb) {
+  double rr = 0.0, bb = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const double bi = b[i], ri = bi - q[i];
+    r[i] = ri;
+    rr += ri * ri;
+    bb += bi * bi;
+  }
+  if (!stop) return;
+  block_part256(rr, part + nb + blockIdx.x);
+  block_part256(bb, part + 2 * nb + blockIdx.x);
+}
+
+// pv = [<r,z> | ||r||^2 | ||b||^2] (the last two with stop_type 1): first state
+__global__ void dpcg_init_kernel(const double* __restrict__ pv, int P, DPcgState* st, double tol, int relconv,
+                                 int maxiter, int stop, double* res, double* rn) {
+  if (threadIdx.x || blockIdx.x) return;
+  const double s = dpcg_rank_sum(pv, P);
+  st->it = 0; st->maxiter = maxiter; st->run = 0; st->alpha = 0.0; st->beta = 0.0; st->dq = 0.0;
+  st->stop = stop; st->rr = 0.0; st->thr = 0.0;
+  st->rz = s;
+  st->tol = tol;
+  if (s < 0.0) { st->active = 0; st->status = PCG_NOT_POS; res[0] = 0.0; return; }
+  const double r0 = sqrt(s);
+  res[0] = r0;
+  bool go;
+  if (stop) {                       // ||r|| <= tol ||b||, ||b|| = 0 taken as 1
+    const double rr = dpcg_rank_sum(pv + P, P), bb = dpcg_rank_sum(pv + 2 * P, P);
+    const double bn = bb == 0.0 ? 1.0 : sqrt(bb);
+    st->rr = rr;
+    st->thr = tol * bn;             // the threshold itself (the host loop's tolerance * bnorm)
+    rn[0] = sqrt(rr);
+    go = rn[0] > st->thr;
+  } else {
+    st->tol = relconv ? tol * r0 : tol;
+    go = r0 > st->tol;
+  }
+  st->active = (go && maxiter > 0) ? 1 : 0;
+  st->status = st->active ? PCG_RUNNING : PCG_STOPPED;
+}
+
+// dq = <d, A d> over all ranks; alpha = rz / dq
+__global__ void dpcg_alpha_kernel(const double* __restrict__ pv, int P, DPcgState* st) {
+  if (threadIdx.x || blockIdx.x) return;
+  st->run = st->active;
+  if (!st->active) return;
+  const double s = dpcg_rank_sum(pv, P);
+  st->dq = s;
+  if (s == 0.0) { st->active = 0; st->status = PCG_DQ_ZERO; return; }
+  st->alpha = st->rz / s;
+}
+
+// x += alpha d, r -= alpha q (nothing when inactive); RR: this block's share
+// of the new ||r||^2 into part[nb + block], in the same pass
+template <bool RR>
+__global__ __launch_bounds__(256) void dpcg_xr_kernel(int64_t n, const DPcgState* __restrict__ st,
+                                                      const double* __restrict__ d, const double* __restrict__ q,
+                                                      double* __restrict__ x, double* __restrict__ r,
+                                                      double* __restrict__ part, int nb) {
+  if (!st->active) return;          // uniform over the grid
+  const double alpha = st->alpha;
+  double rr = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    x[i] = x[i] + alpha * d[i];
+    const double ri = r[i] - alpha * q[i];
+    r[i] = ri;
+    rr += ri * ri;
+  }
+  if (RR) block_part256(rr, part + nb + blockIdx.x);
+}
+
+// rz' = <r, B r> over all ranks: beta, the history entries, the stop test
+__global__ void dpcg_beta_kernel(const double* __restrict__ pv, int P, DPcgState* st, double* res, double* rn,
+                                 double* alphas, double* betas) {
+  if (threadIdx.x || blockIdx.x) return;
+  if (!st->active) return;
+  const double s = dpcg_rank_sum(pv, P);
+  if (s < 0.0) { st->active = 0; st->status = PCG_RZ_NEG; return; }
+  const double beta = s / st->rz;
+  const int k = st->it;
+  st->beta = beta;
+  st->rz = s;
+  res[k + 1] = sqrt(s);
+  alphas[k] = st->alpha;
+  betas[k] = beta;
+  st->it = k + 1;
+  bool go;
+  if (st->stop) {
+    st->rr = dpcg_rank_sum(pv + P, P);
+    rn[k + 1] = sqrt(st->rr);
+    go = rn[k + 1] > st->thr;
+  } else {
+    go = res[k + 1] > st->tol;
+  }
+  if (!go || k + 1 >= st->maxiter) { st->active = 0; st->status = PCG_STOPPED; }
+}
+
+// d = z + beta d; on <r, Br> < 0 this iteration's x update is undone instead
+__global__ __launch_bounds__(256) void dpcg_d_kernel(int64_t n, const DPcgState* __restrict__ st,
+                                                     const double* __restrict__ z, double* __restrict__ d,
+                                                     double* __restrict__ x) {
+  if (!st->run || st->status == PCG_DQ_ZERO) return;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  if (st->status == PCG_RZ_NEG) x[i] = x[i] - st->alpha * d[i];
+  else d[i] = z[i] + st->beta * d[i];
+}
+
 // field-major [v0; v1] (stride bs) -> node-interleaved pairs
 __global__ __launch_bounds__(256) void interleave2_kernel(int64_t n, const double* __restrict__ in, int64_t bs,
                                                           double* __restrict__ out) {
@@ -2874,7 +3051,12 @@ enum OpKind { OP_CSR = 0, OP_SCALE = 1, OP_GEMV = 2, OP_AXPY = 3, OP_BSR = 4, OP
               OP_CGS = 15,     // point-wise GS, one colour of a CSR level (csr_gs_kernel)
               OP_CGSF = 16,    // point-wise GS, a small level's whole smoothing call (csr_gs_small_kernel)
               OP_CRING = 17,   // one colour of a seed-ring sweep on the CSR layout (ring_csr_kernel)
-              OP_COPY = 18 };  // out = x (n doubles): a rank's plain slice into its [owned | ghost] buffer
+              OP_COPY = 18,    // out = x (n doubles): a rank's plain slice into its [owned | ghost] buffer
+              // the distributed PCG's kernels on Op::pcg (dpcg_*_kernel)
+              OP_PDOT = 19,    // block partials of <x, y> over the owned entries
+              OP_PSLOT = 20,   // n dots' partials -> slot [rank] of their P-vectors
+              OP_PR0 = 21,     // r = b - q (start-up)
+              OP_PINIT = 22, OP_PALPHA = 23, OP_PXR = 24, OP_PBETA = 25, OP_PD = 26 };
 // kernel classes (kernel_ms / class_bytes slots)
 enum Cls {
   C_L0_RESID = 0,   // dominant: r = b - A0 x (once per apply)
@@ -2906,6 +3088,7 @@ struct Op {
   const struct DLevel* lev = nullptr;   // PATCH: the level's patch data
   const TOp* prog = nullptr;        // TAIL: the device op list (n ops)
   int tail_pl = -1;                 // TAIL: the program's LDS byte offset (-1: read from global memory)
+  const DPcgCtx* pcg = nullptr;     // OP_P*: the distributed PCG plan's pointers
   double bytes = 0.0;
 };
 
@@ -6078,6 +6261,39 @@ void launch(const Op& o, hipStream_t s) {
     case OP_CSCALE:
       if (o.n) cscale_kernel<<<(unsigned)std::min<int64_t>(SCALE_BLOCKS, nblocks(o.n)), 256, 0, s>>>(o.n, SCALE_BLOCKS, o.part, o.out);
       break;
+    // distributed PCG: launched even for an empty slice (the partials and
+    // the rank's slot must be written on every rank)
+    case OP_PDOT:
+      dpcg_dot_kernel<<<DOT_BLOCKS, 256, 0, s>>>(o.pcg->n, o.x, o.y, o.pcg->part);
+      break;
+    case OP_PSLOT:
+      dpcg_slot_kernel<<<1, 256, 0, s>>>(DOT_BLOCKS, (int)o.n, o.pcg->part, o.pcg->pv, o.pcg->P, o.pcg->rank);
+      break;
+    case OP_PR0:
+      dpcg_r0_kernel<<<DOT_BLOCKS, 256, 0, s>>>(o.pcg->n, o.pcg->stop, o.pcg->b, o.pcg->q, o.pcg->r, o.pcg->part,
+                                                DOT_BLOCKS);
+      break;
+    case OP_PINIT:
+      dpcg_init_kernel<<<1, 64, 0, s>>>(o.pcg->pv, o.pcg->P, o.pcg->st, o.pcg->tol, o.pcg->relconv, o.pcg->maxiter,
+                                        o.pcg->stop, o.pcg->res, o.pcg->rn);
+      break;
+    case OP_PALPHA:
+      dpcg_alpha_kernel<<<1, 64, 0, s>>>(o.pcg->pv, o.pcg->P, o.pcg->st);
+      break;
+    case OP_PXR:
+      if (o.pcg->stop)
+        dpcg_xr_kernel<true><<<DOT_BLOCKS, 256, 0, s>>>(o.pcg->n, o.pcg->st, o.pcg->d, o.pcg->q, o.pcg->x, o.pcg->r,
+                                                        o.pcg->part, DOT_BLOCKS);
+      else
+        dpcg_xr_kernel<false><<<DOT_BLOCKS, 256, 0, s>>>(o.pcg->n, o.pcg->st, o.pcg->d, o.pcg->q, o.pcg->x, o.pcg->r,
+                                                         o.pcg->part, DOT_BLOCKS);
+      break;
+    case OP_PBETA:
+      dpcg_beta_kernel<<<1, 64, 0, s>>>(o.pcg->pv, o.pcg->P, o.pcg->st, o.pcg->res, o.pcg->rn, o.pcg->al, o.pcg->be);
+      break;
+    case OP_PD:
+      if (o.pcg->n) dpcg_d_kernel<<<nblocks(o.pcg->n), 256, 0, s>>>(o.pcg->n, o.pcg->st, o.pcg->z, o.pcg->d, o.pcg->x);
+      break;
   }
 }
 
@@ -7303,9 +7519,36 @@ struct DistHandle {
     }
     graphs.clear();
   }
+  // device-resident PCG (dist_pcg): r, z, d, q of w * nloc
+  // doubles, the dots' block partials and P-vectors, the state with its
+  // pinned mirror (two slots per rank whose state is read here), and one
+  // plan per (x, maxiter, stop_type): histories, the ops' context and, on
+  // an RCCL or single-rank handle, the captured iteration
+  double *cr = nullptr, *cz = nullptr, *cd = nullptr, *cq = nullptr, *ppart = nullptr, *pv = nullptr;
+  DPcgState* pst = nullptr;
+  DPcgState* hst = nullptr;
+  int hst_ranks = 0;
+  struct PcgPlan {
+    std::unique_ptr<DPcgCtx> c;
+    double* hist = nullptr;            // residuals, ||r||, alphas, betas
+    hipGraph_t g = nullptr;
+    hipGraphExec_t e = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    void release() {
+      if (e) (void)hipGraphExecDestroy(e);
+      if (g) (void)hipGraphDestroy(g);
+      for (hipEvent_t v : ev) if (v) (void)hipEventDestroy(v);
+      if (hist) (void)raw_free(hist);
+      e = nullptr; g = nullptr; hist = nullptr; ev[0] = ev[1] = nullptr;
+    }
+  };
+  std::vector<PcgPlan> pcgs;
+  std::string pcg_graph_err;           // why the iteration runs eagerly on this handle
   ~DistHandle() {
     if (last) (void)hipEventSynchronize(last);
     drop_graphs();
+    for (auto& q : pcgs) q.release();
+    if (hst) (void)hipHostFree(hst);
     if (cap) (void)hipStreamDestroy(cap);
     for (void* q : pinned) (void)hipHostFree(q);
     if (ev_in) (void)hipEventDestroy(ev_in);
@@ -9166,10 +9409,16 @@ int dist_mark(DistHandle* h, hipStream_t s, std::string* err) {
 // send / receive groups, c[2] point-to-point messages, c[3] all-reduces,
 // c[4] stream forks (interior rows on the side stream).  With P == 1 only
 // the kernels remain.
+static void count_launches(const DistHandle* h, const std::vector<DOp>& ops, int64_t c[5]);
+
 void dist_apply_launches(const DistHandle* h, int64_t c[5]) {
-  for (int k = 0; k < 5; ++k) c[k] = 0;
   std::vector<DOp> ops;
   dapply_ops(h, nullptr, nullptr, &ops);
+  count_launches(h, ops, c);
+}
+
+static void count_launches(const DistHandle* h, const std::vector<DOp>& ops, int64_t c[5]) {
+  for (int k = 0; k < 5; ++k) c[k] = 0;
   const int P = h->nranks;
   for (const DOp& d : ops) {
     if (d.dk == D_OP || (P == 1 && d.dk == D_OVERLAP)) { ++c[0]; continue; }
@@ -9516,6 +9765,7 @@ int dist_set_exchange(DistHandle* h, const mamg_exchange& ex, std::string* err) 
       red = std::max(red, w * D.nv);
     }
     red = std::max<int64_t>(red, 2 * SCALE_BLOCKS);   // coarse scaling partials
+    red = std::max<int64_t>(red, 3 * (int64_t)h->nranks);   // the PCG dots' P-vectors (dist_pcg)
     int rc = pin(&h->hred, red);
     if (rc) return rc;
   }
@@ -9585,6 +9835,341 @@ int dist_virtual_spmv(const std::vector<DistHandle*>& hs, const std::vector<cons
     dspmv_ops(hs[p], x[p], y[p], &ops[p]);
   }
   return virtual_run(hs, ops, (hipStream_t)stream, err);
+}
+
+// ---------------------------------------------------------------------------
+// Device-resident PCG on row-partitioned ranks: dev_pcg's loop
+// with the operator, the preconditioner and the dots as one DOp list per
+// iteration, so the RCCL, captured-graph, host-staged and virtual backends
+// all execute the same schedule.
+// ---------------------------------------------------------------------------
+namespace {
+
+void append(std::vector<DOp>* ops, const std::vector<DOp>& more) { ops->insert(ops->end(), more.begin(), more.end()); }
+
+DOp pcg_op(int kind, const DPcgCtx* c, double bytes, int64_t n = 0) {
+  Op o;
+  o.kind = kind; o.cls = C_MISC; o.pcg = c; o.n = n; o.bytes = bytes;
+  return wrap(o);
+}
+
+// the rank's partials of <a, b> (dot 0), its slot in each of the nd
+// P-vectors (dots 1, 2: partials already written by the pass before), and
+// the all-reduce of the nd P-vectors
+void dpcg_dot_ops(const DPcgCtx* c, const double* a, const double* b, int nd, std::vector<DOp>* ops) {
+  DOp d = pcg_op(OP_PDOT, c, 16.0 * c->n);
+  d.op.x = a; d.op.y = b;
+  ops->push_back(d);
+  ops->push_back(pcg_op(OP_PSLOT, c, 8.0 * nd * DOT_BLOCKS, nd));
+  DOp r;
+  r.dk = D_ALLREDUCE; r.cls = C_COMM; r.buf = c->pv; r.count = (int64_t)nd * c->P; r.bytes = 16.0 * r.count;
+  ops->push_back(r);
+}
+
+// one iteration: q = A d, <d,q>, alpha, x / r update (+ ||r||^2 partials),
+// z = B r, <r,z> (and ||r||^2), beta + histories + stop test, d update.  An
+// inactive iteration issues every op and every exchange; the state's flags
+// mask the x, r and d updates only.
+void dpcg_iter_ops(const DistHandle* h, const DPcgCtx* c, std::vector<DOp>* ops) {
+  ops->clear();
+  std::vector<DOp> part;
+  dspmv_ops(h, c->d, c->q, &part);
+  append(ops, part);
+  dpcg_dot_ops(c, c->d, c->q, 1, ops);
+  ops->push_back(pcg_op(OP_PALPHA, c, 0.0));
+  ops->push_back(pcg_op(OP_PXR, c, 48.0 * c->n));
+  dapply_ops(h, c->r, c->z, &part);
+  append(ops, part);
+  dpcg_dot_ops(c, c->r, c->z, c->stop ? 2 : 1, ops);
+  ops->push_back(pcg_op(OP_PBETA, c, 0.0));
+  ops->push_back(pcg_op(OP_PD, c, 24.0 * c->n));
+}
+
+// start-up: r = b - A x0, z = B r, d = z, <r,z> (and ||r||^2, ||b||^2), first state
+void dpcg_start_ops(const DistHandle* h, const DPcgCtx* c, std::vector<DOp>* ops) {
+  ops->clear();
+  std::vector<DOp> part;
+  dspmv_ops(h, c->x, c->q, &part);
+  append(ops, part);
+  ops->push_back(pcg_op(OP_PR0, c, 24.0 * c->n));
+  dapply_ops(h, c->r, c->z, &part);
+  append(ops, part);
+  Op cp;
+  cp.kind = OP_COPY; cp.cls = C_MISC; cp.n = c->n; cp.x = c->z; cp.out = c->d; cp.bytes = 16.0 * c->n;
+  ops->push_back(wrap(cp));
+  dpcg_dot_ops(c, c->r, c->z, c->stop ? 3 : 1, ops);
+  ops->push_back(pcg_op(OP_PINIT, c, 0.0));
+}
+
+int dpcg_check(const DistHandle* h, int maxiter, int stop, const double* rnorms, std::string* err) {
+  if (stop != 0 && stop != 1) { *err = "stop_type must be 0 (cbc.block) or 1 (||r|| <= tol ||b||)"; return MAMG_ERR_ARG; }
+  if (maxiter < 0) { *err = "maxiter must be >= 0"; return MAMG_ERR_ARG; }
+  if (stop == 1 && !rnorms) { *err = "stop_type 1 needs the rnorms history"; return MAMG_ERR_ARG; }
+  if (h->L.empty() || h->L[0].coarsest) { *err = "single-level hierarchy: no distributed operator"; return MAMG_ERR_ARG; }
+  return MAMG_OK;
+}
+
+// the handle's plan for (x, maxiter, stop): work buffers on first use,
+// histories and the ops' context per plan (at most 4, the oldest evicted
+// once the handle's work is done); slots: host mirrors of the state wanted
+int dpcg_plan(DistHandle* h, double* x, int maxiter, int stop, int slots, DistHandle::PcgPlan** out,
+              std::string* err) {
+  int rc;
+  const int64_t n = (int64_t)h->w * h->L[0].nloc;
+  if (!h->pst) {
+    double** v[] = {&h->cr, &h->cz, &h->cd, &h->cq};
+    for (double** q : v)
+      if ((rc = ddalloc(h, q, std::max<int64_t>(n, 1), err))) return rc;
+    if ((rc = ddalloc(h, &h->ppart, 3 * DOT_BLOCKS, err))) return rc;
+    if ((rc = ddalloc(h, &h->pv, 3 * (int64_t)h->nranks, err))) return rc;
+    if ((rc = ddalloc(h, &h->pst, 1, err))) return rc;
+  }
+  if (h->hst_ranks < slots) {
+    if (h->last) HIPCHK(hipEventSynchronize(h->last));
+    if (h->hst) HIPCHK(hipHostFree(h->hst));
+    h->hst = nullptr;
+    h->hst_ranks = 0;
+    HIPCHK(hipHostMalloc((void**)&h->hst, 2 * (size_t)slots * sizeof(DPcgState), hipHostMallocDefault));
+    h->hst_ranks = slots;
+  }
+  for (auto& q : h->pcgs)
+    if (q.c->x == x && q.c->maxiter == maxiter && q.c->stop == stop) { *out = &q; return MAMG_OK; }
+  if (h->pcgs.size() >= 4) {
+    if (h->last) HIPCHK(hipEventSynchronize(h->last));
+    h->pcgs.front().release();
+    h->pcgs.erase(h->pcgs.begin());
+  }
+  DistHandle::PcgPlan q;
+  if (raw_malloc((void**)&q.hist, (4 * (size_t)maxiter + 2) * sizeof(double), "long") != hipSuccess) {
+    (void)hipGetLastError();
+    *err = "PCG history allocation failed";
+    return MAMG_ERR_HIP;
+  }
+  hipError_t e = hipSuccess;
+  for (hipEvent_t& v : q.ev)
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&v, hipEventDisableTiming);
+  if (e != hipSuccess) {
+    q.release();
+    *err = std::string("PCG events: ") + hipGetErrorString(e);
+    return MAMG_ERR_HIP;
+  }
+  q.c.reset(new DPcgCtx());
+  DPcgCtx& c = *q.c;
+  c.st = h->pst; c.n = n; c.P = h->nranks; c.rank = h->rank; c.stop = stop; c.maxiter = maxiter;
+  c.x = x; c.r = h->cr; c.z = h->cz; c.d = h->cd; c.q = h->cq; c.part = h->ppart; c.pv = h->pv;
+  c.res = q.hist; c.rn = c.res + maxiter + 1; c.al = c.rn + maxiter + 1; c.be = c.al + maxiter;
+  h->pcgs.push_back(std::move(q));
+  *out = &h->pcgs.back();
+  return MAMG_OK;
+}
+
+// histories and the return code from the final state (dev_pcg's messages)
+int dpcg_finish(const DPcgCtx& c, const DPcgState& fin, double* residuals, double* rnorms, double* alphas,
+                double* betas, int* niters, std::string* err) {
+  const int it = fin.it;
+  HIPCHK(hipMemcpy(residuals, c.res, (it + 1) * sizeof(double), hipMemcpyDeviceToHost));
+  if (c.stop && rnorms) HIPCHK(hipMemcpy(rnorms, c.rn, (it + 1) * sizeof(double), hipMemcpyDeviceToHost));
+  if (it > 0) {
+    HIPCHK(hipMemcpy(alphas, c.al, it * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(betas, c.be, it * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  *niters = it;
+  if (fin.status == PCG_DQ_ZERO) { *err = "ConjGrad stopped: <d,Ad> = 0"; return MAMG_ERR_BREAKDOWN; }
+  if (fin.status == PCG_RZ_NEG) { *err = "ConjGrad breakdown (<r,Br> < 0)"; return MAMG_ERR_BREAKDOWN; }
+  return MAMG_OK;
+}
+
+}  // namespace
+
+void dist_pcg_launches(const DistHandle* h, int stop, int64_t c[5]) {
+  DPcgCtx ctx;
+  ctx.P = h->nranks; ctx.rank = h->rank; ctx.stop = stop; ctx.n = (int64_t)h->w * h->L[0].nloc;
+  std::vector<DOp> ops;
+  dpcg_iter_ops(h, &ctx, &ops);
+  count_launches(h, ops, c);
+}
+
+int dist_pcg(DistHandle* h, const double* d_b, double* d_x, double tol, int maxiter, int relativeconv,
+             int stop, double* residuals, double* rnorms, double* alphas, double* betas, int* niters,
+             void* stream, std::string* err) {
+  int rc;
+  if ((rc = dpcg_check(h, maxiter, stop, rnorms, err))) return rc;
+  if (!h->comm && h->nranks > 1 && !h->host_ex && !h->dry) {
+    *err = "virtual rank handle (no communicator): use mamg_dist_virtual_pcg";
+    return MAMG_ERR_ARG;
+  }
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  DistHandle::PcgPlan* pl = nullptr;
+  if ((rc = dpcg_plan(h, d_x, maxiter, stop, 1, &pl, err))) return rc;
+  DPcgCtx& c = *pl->c;
+  c.b = d_b; c.tol = tol; c.relconv = relativeconv;
+  DPcgState* st = h->pst;
+  DPcgState* hst = h->hst;
+  std::vector<DOp> ops;
+  dpcg_iter_ops(h, &c, &ops);
+  // one iteration as one hipGraph (RCCL calls inside) on an RCCL or
+  // single-rank handle; a failed capture is recorded and the same op list
+  // runs eagerly -- the RCCL sequence of a rank is the same either way
+  const bool graphable = (h->comm || h->nranks == 1) && h->graph_err.empty() && h->pcg_graph_err.empty();
+  if (graphable && !pl->e) {
+    std::string cerr;
+    if (dist_capture(h, ops, &pl->g, &pl->e, &cerr)) {
+      h->pcg_graph_err = cerr;
+      pl->g = nullptr;
+      pl->e = nullptr;
+    }
+  }
+  if (h->last) HIPCHK(hipStreamWaitEvent(s, h->last, 0));   // the work buffers are the handle's
+  std::vector<DOp> start;
+  dpcg_start_ops(h, &c, &start);
+  for (const DOp& d : start)
+    if ((rc = run_dop(h, d, s, err))) return rc;
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(&hst[0], st, sizeof(DPcgState), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (hst[0].status == PCG_NOT_POS) {
+    *niters = 0;
+    residuals[0] = 0.0;
+    (void)dist_mark(h, s, err);
+    *err = "Matrix is not positive";
+    return MAMG_ERR_BREAKDOWN;
+  }
+  if (hst[0].active) {
+    // iteration k's state lands in hst[k & 1].  The host-staged exchange
+    // synchronises at every exchange, so its state is read after each
+    // iteration; otherwise iteration k + 1 is queued before the host waits
+    // for iteration k.  Either way the number of iterations a rank issues
+    // depends on all-reduced state only: the same on every rank.
+    const bool ahead = !(h->host_ex && !h->comm);
+    for (int k = 0; k < maxiter; ++k) {
+      if (pl->e) {
+        HIPCHK(hipGraphLaunch(pl->e, s));
+      } else {
+        for (const DOp& d : ops)
+          if ((rc = run_dop(h, d, s, err))) return rc;
+      }
+      HIPCHK(hipMemcpyAsync(&hst[k & 1], st, sizeof(DPcgState), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipEventRecord(pl->ev[k & 1], s));
+      if (ahead && k == 0) continue;
+      const int w = ahead ? (k - 1) & 1 : k & 1;
+      HIPCHK(hipEventSynchronize(pl->ev[w]));
+      if (!hst[w].active) break;
+    }
+  }
+  HIPCHK(hipMemcpyAsync(&hst[0], st, sizeof(DPcgState), hipMemcpyDeviceToHost, s));
+  if ((rc = dist_mark(h, s, err))) return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipGetLastError());
+  return dpcg_finish(c, hst[0], residuals, rnorms, alphas, betas, niters, err);
+}
+
+// test mode: the ranks' op lists in lockstep (virtual_run), eager or as one
+// captured lockstep iteration replayed; every rank's state is compared with
+// rank 0's, byte for byte, whenever it is read back
+int dist_virtual_pcg(const std::vector<DistHandle*>& hs, const std::vector<const double*>& b,
+                     const std::vector<double*>& x, double tol, int maxiter, int relativeconv, int stop,
+                     int graph, double* residuals, double* rnorms, double* alphas, double* betas, int* niters,
+                     void* stream, std::string* err) {
+  const int P = (int)hs.size();
+  int rc;
+  for (int p = 0; p < P; ++p) {
+    if ((rc = dpcg_check(hs[p], maxiter, stop, rnorms, err))) return rc;
+    if (hs[p]->nranks != P || hs[p]->rank != p) { *err = "rank handles do not form ranks 0..n-1 of n"; return MAMG_ERR_ARG; }
+  }
+  DistHandle* h0 = hs[0];
+  HIPCHK(hipSetDevice(h0->device));
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<DistHandle::PcgPlan*> pl(P, nullptr);
+  std::vector<std::vector<DOp>> start(P), ops(P);
+  for (int p = 0; p < P; ++p) {
+    if ((rc = dpcg_plan(hs[p], x[p], maxiter, stop, p == 0 ? P : 1, &pl[p], err))) return rc;
+    DPcgCtx& c = *pl[p]->c;
+    c.b = b[p]; c.tol = tol; c.relconv = relativeconv;
+    dpcg_start_ops(hs[p], &c, &start[p]);
+    dpcg_iter_ops(hs[p], &c, &ops[p]);
+    if (hs[p]->last) HIPCHK(hipStreamWaitEvent(s, hs[p]->last, 0));
+  }
+  DPcgState* hst = h0->hst;                    // [2][P]
+  auto read_states = [&](int slot) -> int {
+    for (int p = 0; p < P; ++p)
+      HIPCHK(hipMemcpyAsync(&hst[(size_t)slot * P + p], hs[p]->pst, sizeof(DPcgState), hipMemcpyDeviceToHost, s));
+    return MAMG_OK;
+  };
+  auto same_states = [&](int slot, int k) -> int {
+    for (int p = 1; p < P; ++p)
+      if (std::memcmp(&hst[(size_t)slot * P + p], &hst[(size_t)slot * P], sizeof(DPcgState))) {
+        *err = "virtual PCG: rank " + std::to_string(p) + "'s state differs from rank 0's after iteration " +
+               std::to_string(k);
+        return MAMG_ERR_SETUP;
+      }
+    return MAMG_OK;
+  };
+  hipGraph_t g = nullptr;
+  hipGraphExec_t ex = nullptr;
+  auto drop = [&]() {
+    if (ex) (void)hipGraphExecDestroy(ex);
+    if (g) (void)hipGraphDestroy(g);
+    ex = nullptr; g = nullptr;
+  };
+  if (graph && maxiter > 0) {
+    std::lock_guard<std::recursive_mutex> capture_lock(capture_mutex());
+    if (!h0->cap) HIPCHK(hipStreamCreateWithFlags(&h0->cap, hipStreamNonBlocking));
+    HIPCHK(hipStreamBeginCapture(h0->cap, hipStreamCaptureModeThreadLocal));
+    rc = virtual_run(hs, ops, h0->cap, err, false);
+    const hipError_t e = hipStreamEndCapture(h0->cap, &g);
+    if (rc || e != hipSuccess) {
+      drop();
+      (void)hipGetLastError();
+      if (!rc) *err = std::string("stream capture of the virtual PCG iteration: ") + hipGetErrorString(e);
+      return rc ? rc : MAMG_ERR_HIP;
+    }
+    const hipError_t ei = graph_instantiate(&ex, g);
+    if (ei != hipSuccess) {
+      drop();
+      *err = std::string("hipGraphInstantiate of the virtual PCG iteration: ") + hipGetErrorString(ei);
+      return MAMG_ERR_HIP;
+    }
+  }
+  // from here on every exit drains the stream and drops the graph
+  auto body = [&]() -> int {
+    int r;
+    if ((r = virtual_run(hs, start, s, err, false))) return r;
+    if ((r = read_states(0))) return r;
+    HIPCHK(hipStreamSynchronize(s));
+    if ((r = same_states(0, 0))) return r;
+    if (hst[0].status == PCG_NOT_POS || !hst[0].active) return MAMG_OK;
+    for (int k = 0; k < maxiter; ++k) {
+      if (ex) HIPCHK(hipGraphLaunch(ex, s));
+      else if ((r = virtual_run(hs, ops, s, err, false))) return r;
+      if ((r = read_states(k & 1))) return r;
+      HIPCHK(hipEventRecord(pl[0]->ev[k & 1], s));
+      if (k == 0) continue;
+      const int w = (k - 1) & 1;
+      HIPCHK(hipEventSynchronize(pl[0]->ev[w]));
+      if ((r = same_states(w, k))) return r;
+      if (!hst[(size_t)w * P].active) break;
+    }
+    if ((r = read_states(0))) return r;
+    HIPCHK(hipStreamSynchronize(s));
+    return same_states(0, hst[0].it);
+  };
+  rc = body();
+  for (DistHandle* h : hs) {
+    std::string merr;
+    (void)dist_mark(h, s, &merr);
+  }
+  (void)hipStreamSynchronize(s);
+  drop();
+  if (rc) return rc;
+  HIPCHK(hipGetLastError());
+  if (hst[0].status == PCG_NOT_POS) {
+    *niters = 0;
+    residuals[0] = 0.0;
+    *err = "Matrix is not positive";
+    return MAMG_ERR_BREAKDOWN;
+  }
+  return dpcg_finish(*pl[0]->c, hst[0], residuals, rnorms, alphas, betas, niters, err);
 }
 
 }  // namespace mamg

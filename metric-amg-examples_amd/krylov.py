@@ -230,14 +230,30 @@ class DistConjGrad:
         self.relativeconv, self.stop_type = relativeconv, stop_type
         self.residuals, self.alphas, self.betas, self.residual_norms = [], [], [], []
         self.breakdown = False
+        self._device = None      # (handles, stream, graph, virtual) of a device-resident solver
 
     @classmethod
-    def for_handles(cls, handles, stream=None, group=None, **kw):
+    def for_handles(cls, handles, stream=None, group=None, device=False, graph=False, **kw):
         """PCG for DistMetricAMG handles: one handle per process (RCCL ranks;
         dots all-reduced over ``group`` of the initialised torch.distributed
-        world) or a list of virtual rank handles of one process."""
+        world) or a list of virtual rank handles of one process.
+
+        device=True: the loop runs device-resident (``mamg_dist_pcg_device``
+        for one handle -- its exchanges and all-reduces go through the
+        handle's own backend, ``group`` is not used -- or
+        ``mamg_dist_virtual_pcg`` for a list, ``graph=True`` replaying one
+        captured lockstep iteration).  The default stays this host loop."""
         from .amg import DistMetricAMG
         hs = list(handles) if isinstance(handles, (list, tuple)) else [handles]
+        if device:
+            if kw.get('stop_type') not in (None, 0, 1):
+                raise ValueError('stop_type must be None / 0 (cbc.block) or 1 (||r||/||b||)')
+            if not hs:
+                raise ValueError('for_handles(device=True) needs at least one DistMetricAMG handle')
+            solver = cls(None, None, None, **kw)
+            # a list is a set of virtual ranks (also a list of one); a bare handle is this process's rank
+            solver._device = (hs, stream, bool(graph), isinstance(handles, (list, tuple)))
+            return solver
         if len(hs) > 1:        # virtual ranks: lockstep, exchanges as device copies
             return cls(lambda xs, ys: DistMetricAMG.virtual_spmv(hs, xs, ys, stream),
                        lambda rs, zs: DistMetricAMG.virtual_apply(hs, rs, zs, stream), None, **kw)
@@ -263,9 +279,56 @@ class DistConjGrad:
             v += float((x * y).sum())
         return self.allreduce(v) if self.allreduce is not None else v
 
-    def solve(self, bs):
+    def _solve_device(self, bs, xs=None):
+        from .amg import _device_ptr, _stream_ptr
+        hs, stream, graph, virtual = self._device
+        if len(bs) != len(hs):
+            raise ValueError('one right-hand-side slice per handle (%d handles, %d slices)' % (len(hs), len(bs)))
+        for h, b in zip(hs, bs):
+            if b.numel() != h.local_size:
+                raise ValueError('local slice of rank %d must hold %d doubles' % (h.rank, h.local_size))
+        if xs is None:
+            xs = [b.new_zeros(b.shape) for b in bs]
+        maxiter, stop = int(self.maxiter), int(self.stop_type or 0)
+        res, rn = np.zeros(maxiter + 1), np.zeros(maxiter + 1)
+        al, be = np.zeros(max(maxiter, 1)), np.zeros(max(maxiter, 1))
+        it = C.c_int(0)
+        L = _lib.lib()
+        tail = (_lib.ptr(res, C.c_double), _lib.ptr(rn, C.c_double), _lib.ptr(al, C.c_double),
+                _lib.ptr(be, C.c_double), C.byref(it), _stream_ptr(stream))
+        if not virtual:
+            rc = L.mamg_dist_pcg_device(hs[0]._h, _device_ptr(bs[0]), _device_ptr(xs[0]), float(self.tolerance),
+                                        maxiter, int(bool(self.relativeconv)), stop, *tail)
+        else:
+            n = len(hs)
+            H = (C.c_void_p * n)(*[h._h.value for h in hs])
+            B = (C.c_void_p * n)(*[_device_ptr(b).value for b in bs])
+            X = (C.c_void_p * n)(*[_device_ptr(x).value for x in xs])
+            rc = L.mamg_dist_virtual_pcg(H, n, B, X, float(self.tolerance), maxiter,
+                                         int(bool(self.relativeconv)), stop, int(graph), *tail)
+        k = it.value
+        self.breakdown = False
+        if rc == _lib.ERR_BREAKDOWN:
+            self.breakdown = True
+            msg = L.mamg_last_error().decode()
+            if k == 0 and 'not positive' in msg:
+                raise ValueError('Matrix is not positive')
+            if '<d,Ad> = 0' not in msg:        # the host loop stops silently on <d,Ad> = 0 too
+                warnings.warn('ConjGrad breakdown')
+        else:
+            _lib.check(rc)
+        self.residuals, self.alphas, self.betas = list(res[:k + 1]), list(al[:k]), list(be[:k])
+        self.residual_norms = list(rn[:k + 1]) if stop == 1 else []
+        return xs
+
+    def solve(self, bs, xs=None):
         """bs: list of local right-hand-side slices (torch tensors); returns
-        the list of local solution slices."""
+        the list of local solution slices.  xs (device-resident solver only):
+        the slices holding x0, overwritten with the solution."""
+        if self._device is not None:
+            return self._solve_device(bs, xs)
+        if xs is not None:
+            raise ValueError('the host loop starts from x0 = 0: xs= needs for_handles(..., device=True)')
         xs = [b.new_zeros(b.shape) for b in bs]
         rs = [b.clone() for b in bs]
         zs = [b.new_zeros(b.shape) for b in bs]
