@@ -402,7 +402,11 @@ int mamg_dist_virtual_apply_graph(mamg_dhandle** hs, int n, const double** d_r, 
  * mamg_pcg_device's loop and semantics on N ranks.  x0 = d_x_local on entry;
  * residuals[k] = sqrt(<r, B r>) (maxiter + 1 entries), alphas / betas maxiter
  * entries, *niters = len(residuals) - 1; MAMG_ERR_BREAKDOWN with the messages
- * of mamg_pcg_device.  stop_type 0: cbc.block's rule (tol absolute unless
+ * of mamg_pcg_device and what it leaves in residuals / alphas / betas /
+ * *niters / d_x_local on each of them (not positive: *niters = 0,
+ * residuals[0] = 0.0, nothing else written, every rank's x slice untouched;
+ * <r,Br> < 0 in iteration k: *niters = k, k + 1 residuals (and rnorms), k
+ * alphas / betas, x slices restored to x_k to round-off).  stop_type 0: cbc.block's rule (tol absolute unless
  * relativeconv); 1: HAZmath's linear_stop_type 1, ||r||_2 <= tol ||b||_2 with
  * ||b|| = 0 taken as 1 (one more dot per iteration, fused into the x / r
  * update); rnorms[maxiter + 1] then receives ||r||_2 per iteration and may be
@@ -556,8 +560,20 @@ int mamg_spmv_device(mamg_handle* h, const double* d_x, double* d_y,
  * (src/bidomain_3d.py:149-160): x0 = d_x on entry, residuals = sqrt(<r,Br>),
  * stop when residual <= tol (times residual[0] if relativeconv) or after
  * maxiter iterations.  residuals[maxiter+1], alphas[maxiter], betas[maxiter]
- * are host buffers; *niters = len(residuals)-1.  Returns MAMG_ERR_BREAKDOWN
- * (x restored as cbc.block does) if <r,Br> < 0. */
+ * are host buffers; *niters = len(residuals)-1.  maxiter = 0 is legal: one
+ * residual, d_x untouched.
+ * MAMG_ERR_BREAKDOWN (mamg_last_error tells the three apart) leaves:
+ *   "Matrix is not positive" (<r0,Br0> < 0 at the start, cbc.block's
+ *     ValueError): *niters = 0, residuals[0] = 0.0, alphas / betas and every
+ *     other entry of residuals not written, d_x untouched (bitwise x0);
+ *   "ConjGrad breakdown (<r,Br> < 0)" in iteration k: *niters = k, the k + 1
+ *     residuals and k alphas / betas of the completed iterations (the negative
+ *     <r,Br> and the alpha of the broken iteration are not recorded), d_x =
+ *     (x_k + alpha d) - alpha d: the iterate of the last completed iteration
+ *     restored as cbc.block restores it, equal to x_k to round-off of the
+ *     step, not bitwise (k = 0: x0 to round-off);
+ *   "ConjGrad stopped: <d,Ad> = 0" in iteration k: *niters = k, histories as
+ *     above, d_x = x_k bitwise (the x update had not run). */
 int mamg_pcg_device(mamg_handle* h, const double* d_b, double* d_x, double tol,
                     int maxiter, int relativeconv, double* residuals,
                     double* alphas, double* betas, int* niters, void* stream);

@@ -7116,9 +7116,10 @@ int dev_pcg(DeviceHandle* h, const double* d_b, double* d_x, double tol, int max
   HIPCHK(hipMemcpyAsync(&hst[0], st, sizeof(PcgState), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   if (hst[0].status == PCG_NOT_POS) {
-    *err = "Matrix is not positive";
     *niters = 0;
+    residuals[0] = 0.0;
     (void)order_end(h, s, err);
+    *err = "Matrix is not positive";
     return MAMG_ERR_BREAKDOWN;
   }
   if (hst[0].active) {

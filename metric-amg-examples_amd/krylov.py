@@ -138,13 +138,14 @@ class ConjGrad:
                                   _lib.ptr(be, C.c_double), C.byref(it),
                                   C.c_void_p(stream.cuda_stream))
         k = it.value
+        self.breakdown = False
         if rc == _lib.ERR_BREAKDOWN:
             self.breakdown = True
             msg = B._L.mamg_last_error().decode()
+            if k == 0 and 'not positive' in msg:
+                raise ValueError('Matrix is not positive')
             if '<d,Ad> = 0' not in msg:        # the host loop stops silently on <d,Ad> = 0 too
                 warnings.warn('ConjGrad breakdown: ' + msg)
-            if k == 0 and res[0] == 0.0:
-                raise ValueError('Matrix is not positive')
         else:
             _lib.check(rc)
         self.residuals = list(res[:k + 1])
@@ -154,7 +155,8 @@ class ConjGrad:
 
     def _solve_host(self, b):
         A, B = self.A, self.B
-        applyB = (lambda r: B * r) if B is not None else (lambda r: r.copy())
+        self.breakdown = False
+        applyB =(lambda r: B * r) if B is not None else (lambda r: r.copy())
         x = np.zeros_like(b) if self.initial_guess is None else np.array(self.initial_guess, np.float64)
         r = b - A @ x
         z = applyB(r)
