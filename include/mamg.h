@@ -545,6 +545,40 @@ int mamg_kregion_info(const mamg_handle* h, double* ms, int cap, int* n, int* ke
  * (offsets). */
 int mamg_apply_bytes(const mamg_handle* h, double* total_bytes);
 
+/* Storage precision of the operators the cycle streams (DESIGN.md section
+ * 4.7).  MAMG_STORE_F32 narrows a single-GPU BSR2 handle (Jacobi family or
+ * SMOOTHER_POLY; V or W cycle, any nu1 / nu2, with or without coarse scaling)
+ * after its setup: every value array the cycle's launches read -- A_l, K_l or
+ * P_l, R_l of the levels above the coarse tail and the coarsest level -- is
+ * replaced by an fp32 copy rounded to nearest even, in the same layout, and
+ * the kernels convert on load.  Sums, the smoother blocks W, the POLY step
+ * smoothers, the coarsest inverse, every vector and every dot stay fp64: one
+ * apply is the fp64 cycle on the rounded operators up to summation order.
+ * mamg_spmv_device and the A d product of mamg_pcg_device keep reading the
+ * fp64 A_0 (the handle holds both value arrays of A_0; the other fp64
+ * originals are freed), so the PCG solves the caller's system.  A level
+ * stored as merged [P | AP] (MAMG_POST_K=0) keeps that operator fp64.
+ * One way: MAMG_STORE_F32 on a narrowed handle is a no-op, MAMG_STORE_F64
+ * returns MAMG_OK on an un-narrowed handle and MAMG_ERR_UNSUPPORTED on a
+ * narrowed one.  MAMG_ERR_UNSUPPORTED, the handle untouched and the message
+ * naming the reason, for CSR-layout handles, GS / SGS, SCHWARZ_PATCHES and
+ * SCHWARZ_RINGS handles, and for a handle holding a finite value whose fp32
+ * rounding is not finite.  MAMG_ERR_ARG for a NULL handle or another storage
+ * value.  The call waits for the handle's queued work and drops its cached
+ * apply and PCG graphs; it must not run concurrently with other calls on the
+ * same handle.
+ * Bytes (mamg_apply_bytes, mamg_time_apply's class_bytes): a narrowed
+ * operator counts 4 bytes per stored value, so a block with its column is
+ * 16 B where fp64 counts 28 (SYM and half-symmetric upper blocks: 3 values +
+ * a 4-byte column), 20 B where it counts 36 (general: 4 values + a 4-byte
+ * column) and 18 B where it counts 34 (K with 16-bit columns); pointers, row
+ * meta, mirror slots and every vector term are unchanged. */
+enum { MAMG_STORE_F64 = 0, MAMG_STORE_F32 = 1 };
+/* Narrow the operators the cycle reads to fp32 storage (one way). */
+int mamg_set_cycle_storage(mamg_handle* h, int storage);
+/* bit 0: A_l as the cycle reads it, bit 1: K_l / P_l, bit 2: R_l stored fp32; 0 before narrowing */
+int mamg_level_storage(const mamg_handle* h, int level);
+
 /* z = B r : one preconditioner application (`maxit` cycles from x0 = 0).
  * Host pointers (copies in/out, synchronous). */
 int mamg_apply(mamg_handle* h, const double* r, double* z);

@@ -147,6 +147,8 @@ SIGNATURES = {
     'mamg_handle_params': (C.c_int, [VP, C.POINTER(mamg_params)]),
     'mamg_kregion_info': (C.c_int, [VP, P_F64, C.c_int, P_I32, P_I32]),
     'mamg_apply_bytes': (C.c_int, [VP, P_F64]),
+    'mamg_set_cycle_storage': (C.c_int, [VP, C.c_int]),
+    'mamg_level_storage': (C.c_int, [VP, C.c_int]),
     'mamg_apply': (C.c_int, [VP, P_F64, P_F64]),
     'mamg_apply_device': (C.c_int, [VP, VP, VP, VP]),
     'mamg_spmv_device': (C.c_int, [VP, VP, VP, VP]),

@@ -104,6 +104,17 @@ def _stream_ptr(stream):
     return C.c_void_p(int(stream))
 
 
+STORE_F64, STORE_F32 = 0, 1
+
+
+def _storage_code(storage):
+    """'f64' / 'f32' (or the MAMG_STORE_* value) -> MAMG_STORE_*."""
+    codes = {'f64': STORE_F64, 'f32': STORE_F32, STORE_F64: STORE_F64, STORE_F32: STORE_F32}
+    if isinstance(storage, bool) or storage not in codes:
+        raise ValueError("cycle_storage must be 'f64' or 'f32'")
+    return codes[storage]
+
+
 def gpu_setup_supported(p) -> bool:
     """The GPU setup (mamg_setup_gpu) covers num_functions 1 and 2: node-block,
     general seed-block, overlapping-ring (SCHWARZ_ADDITIVE) and point smoothers,
@@ -144,10 +155,14 @@ class MetricAMG:
        equal to the host setup), 'host' (mamg_setup: C++/OpenMP setup, then
        upload), or 'auto' (default): 'gpu' when the profile is one the GPU
        setup covers, else 'host'.  ``setup_path`` records what ran and why.
+    cycle_storage: 'f64' (default) or 'f32': after the setup, narrow the
+       operators the cycle streams to fp32 storage (``set_cycle_storage``).
     """
 
-    def __init__(self, A, W=None, idofs=None, parameters=None, setup='auto', **overrides):
+    def __init__(self, A, W=None, idofs=None, parameters=None, setup='auto', cycle_storage='f64',
+                 **overrides):
         self._L = _lib.lib()
+        _storage_code(cycle_storage)                     # a bad value before any GPU work
         ov, self.notes = _with_functions(W, parameters, overrides)
         self.params = make_params(parameters, **ov)
         if idofs is not None:
@@ -173,6 +188,7 @@ class MetricAMG:
                                                      C.byref(h)))
             self._h = h
             self.setup_path = 'gpu'
+            self.set_cycle_storage(cycle_storage)
             return
         indptr, indices, data, n, m = csr_arrays(A)
         if n != m:
@@ -196,6 +212,7 @@ class MetricAMG:
         if not self.setup_path == 'gpu':
             _lib.check(self._L.mamg_setup(C.byref(csr), ip, ni, C.byref(self.params), C.byref(h)))
         self._h = h
+        self.set_cycle_storage(cycle_storage)
 
     @property
     def setup_timings(self) -> dict:
@@ -254,6 +271,21 @@ class MetricAMG:
                 'post_k': bool(f & 8), 'post_sell': bool(f & 16), 'half': bool(f & 32),
                 'bands': bool(f & 64), 'patches': bool(f & 128), 'gs': bool(f & 256),
                 'rings': bool(f & 512), 'r_bands': bool(f & 1024), 'k_col16': bool(f & 2048)}
+
+    def set_cycle_storage(self, storage):
+        """'f32': narrow the operators the cycle streams to fp32 storage
+        (mamg_set_cycle_storage; one way, a no-op when already narrowed).
+        'f64' is accepted on a handle that was never narrowed.  Vectors,
+        sums, the smoother blocks and the Krylov operator (``spmv_device``,
+        the device PCG's A d) stay fp64."""
+        _lib.check(self._L.mamg_set_cycle_storage(self._h, _storage_code(storage)))
+
+    def level_storage(self, level: int) -> dict:
+        """Which operators of level ``level`` are stored fp32
+        (mamg_level_storage): A as the cycle reads it, K / P, R."""
+        f = self._L.mamg_level_storage(self._h, int(level))
+        _lib.check(min(f, 0))
+        return {'A': bool(f & 1), 'KP': bool(f & 2), 'R': bool(f & 4)}
 
     @property
     def kregion(self) -> dict:
@@ -575,7 +607,10 @@ class DistMetricAMG:
     builds a virtual (single-GPU, no RCCL) rank for tests."""
 
     def __init__(self, A, W=None, idofs=None, parameters=None, rank=0, nranks=1, comm_id=None,
-                 rep_nodes=32768, exchange=None, **overrides):
+                 rep_nodes=32768, exchange=None, cycle_storage='f64', **overrides):
+        if _storage_code(cycle_storage) != STORE_F64:
+            raise ValueError("cycle_storage='f32' covers single-GPU handles (MetricAMG) only; "
+                             "DistMetricAMG keeps fp64 operators")
         self._L = _lib.lib()
         dev = _device_csr(A)
         if dev is not None:                      # A_0 already in HBM (mamg_setup_dist_device)

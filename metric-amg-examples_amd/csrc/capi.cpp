@@ -979,6 +979,28 @@ int mamg_level_format(const mamg_handle* h, int level) {
   return mamg::dev_level_format(h->d, level);
 }
 
+int mamg_set_cycle_storage(mamg_handle* h, int storage) {
+  GUARD_BEGIN
+  if (!h) { set_error("null handle"); return MAMG_ERR_ARG; }
+  if (storage != MAMG_STORE_F64 && storage != MAMG_STORE_F32) {
+    set_error("mamg_set_cycle_storage: storage must be MAMG_STORE_F64 or MAMG_STORE_F32");
+    return MAMG_ERR_ARG;
+  }
+  std::string err;
+  const int rc = mamg::dev_set_cycle_storage(h->d, storage, &err);
+  if (rc) set_error(err);
+  return rc;
+  GUARD_END
+}
+
+int mamg_level_storage(const mamg_handle* h, int level) {
+  if (!h || level < 0 || level >= mamg::dev_num_levels(h->d)) {
+    mamg::set_error("mamg_level_storage: bad handle or level");
+    return MAMG_ERR_ARG;
+  }
+  return mamg::dev_level_storage(h->d, level);
+}
+
 int mamg_handle_options(const mamg_handle* h, char* buf, int64_t cap) {
   GUARD_BEGIN
   return write_options(h ? mamg::dev_switches(h->d) : mamg::read_switches(), buf, cap);

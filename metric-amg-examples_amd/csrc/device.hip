@@ -324,15 +324,35 @@ __device__ __forceinline__ T ldg(const T* p) {
   return *p;
 }
 
-template <bool SYM, bool NT = false>
-__device__ __forceinline__ dv4 blk(const double* __restrict__ v, const double* __restrict__ off,
+// VT: the stored value type.  double, or float for an operator narrowed by
+// dev_set_cycle_storage: the same element layout at
+// half the width (a general block is one 16-byte float4, a SYM block a float2
+// diagonal pair plus one float, the split streams keep their proportions),
+// converted to fp64 on load; every product and sum stays fp64.
+typedef float fv4 __attribute__((ext_vector_type(4)));
+typedef float fv2 __attribute__((ext_vector_type(2)));
+template <class VT> struct vvec { typedef double s; typedef dv2 v2; typedef dv4 v4; };
+template <> struct vvec<float> { typedef float s; typedef fv2 v2; typedef fv4 v4; };
+template <class VT> __device__ __forceinline__ dv2 widen2(const typename vvec<VT>::v2& a) {
+  if constexpr (sizeof(VT) == 8) return a;
+  else return dv2{(double)a.x, (double)a.y};
+}
+template <class VT> __device__ __forceinline__ dv4 widen4(const typename vvec<VT>::v4& a) {
+  if constexpr (sizeof(VT) == 8) return a;
+  else return dv4{(double)a.x, (double)a.y, (double)a.z, (double)a.w};
+}
+
+template <bool SYM, bool NT = false, class VT = double>
+__device__ __forceinline__ dv4 blk(const VT* __restrict__ v, const typename vvec<VT>::s* __restrict__ off,
                                    int64_t k) {
+  typedef typename vvec<VT>::v2 V2;
+  typedef typename vvec<VT>::v4 V4;
   if (SYM) {
-    const dv2 d = ldg<NT>(reinterpret_cast<const dv2*>(v) + k);
-    const double b = ldg<NT>(off + k);
+    const dv2 d = widen2<VT>(ldg<NT>(reinterpret_cast<const V2*>(v) + k));
+    const double b = (double)ldg<NT>(off + k);
     return dv4{d.x, b, b, d.y};
   }
-  return ldg<NT>(reinterpret_cast<const dv4*>(v) + k);
+  return widen4<VT>(ldg<NT>(reinterpret_cast<const V4*>(v) + k));
 }
 
 // x(node c) as a pair: node-interleaved (one 16-byte load) or field-major
@@ -342,17 +362,17 @@ __device__ __forceinline__ double2 xget(const double* x, int64_t xs, int32_t c) 
   return reinterpret_cast<const double2*>(x)[c];
 }
 
-template <int VL, int EPI, bool XFM, bool SYM, int TAG, bool NT = false>
+template <int VL, int EPI, bool XFM, bool SYM, int TAG, bool NT = false, class VT = double>
 __global__ __launch_bounds__(256) void bsr2_kernel(
     int64_t nr, const int64_t* __restrict__ bptr, const int32_t* __restrict__ bcol,
-    const double* __restrict__ bval, const double* __restrict__ x, int64_t xs,
+    const VT* __restrict__ bval, const double* __restrict__ x, int64_t xs,
     const double* y, const double* __restrict__ b, int64_t bs,
     const dv4* __restrict__ W, double* out, int64_t os, int remap, const int32_t* __restrict__ sched,
     int64_t rb0 = 0) {
   const int lane = threadIdx.x & (VL - 1);
   // rb0: first workgroup of a row-range launch (rows from 256 rb0 / VL)
   const int64_t node = ((sched ? (int64_t)sched[blockIdx.x] : rb0 + row_block(remap)) * 256 + threadIdx.x) / VL;
-  const double* offd = SYM ? bval + 2 * bptr[nr] : nullptr;
+  const VT* offd = SYM ? bval + 2 * bptr[nr] : nullptr;
   double s0 = 0.0, s1 = 0.0, t0 = 0.0, t1 = 0.0;
   // EPI_YBD's W block loaded with the row, not after the reduction (a
   // dependent load at the end of every row measured +36 us on level 0's R)
@@ -368,7 +388,7 @@ __global__ __launch_bounds__(256) void bsr2_kernel(
       const bool ha = ka < p1, hb = kb < p1;
       const int64_t la = ha ? ka : p1 - 1, lb = hb ? kb : p1 - 1;
       const int32_t c0 = ldg<NT>(bcol + la), c1 = ldg<NT>(bcol + lb);
-      const dv4 v0 = blk<SYM, NT>(bval, offd, la), v1 = blk<SYM, NT>(bval, offd, lb);
+      const dv4 v0 = blk<SYM, NT, VT>(bval, offd, la), v1 = blk<SYM, NT, VT>(bval, offd, lb);
       const double2 a = xget<XFM>(x, xs, c0), e = xget<XFM>(x, xs, c1);
       s0 += ha ? v0.x * a.x + v0.y * a.y : 0.0;
       s1 += ha ? v0.z * a.x + v0.w * a.y : 0.0;
@@ -483,37 +503,42 @@ constexpr int SELL_U = 4;     // blocks in flight per lane
 // SPL: general blocks stored as two 16-byte streams per slot, the (0,0)(0,1)
 // pairs at bval[2k] and the (1,0)(1,1) pairs at bval[2 nbs + 2k]: each load
 // instruction reads 1 KB contiguous instead of 16 B of every 32 B over 2 KB
-__device__ __forceinline__ dv4 blk_split(const double* __restrict__ v, int64_t nbs, int64_t k) {
-  const dv2 a = reinterpret_cast<const dv2*>(v)[k];
-  const dv2 b = reinterpret_cast<const dv2*>(v + 2 * nbs)[k];
+template <class VT>
+__device__ __forceinline__ dv4 blk_split(const VT* __restrict__ v, int64_t nbs, int64_t k) {
+  typedef typename vvec<VT>::v2 V2;
+  const dv2 a = widen2<VT>(reinterpret_cast<const V2*>(v)[k]);
+  const dv2 b = widen2<VT>(reinterpret_cast<const V2*>(v + 2 * nbs)[k]);
   return dv4{a.x, a.y, b.x, b.y};
 }
 // split inside each 64-slot SELL slot row: the row's 64 (0,0)(0,1) pairs
 // (1 KB) then its 64 (1,0)(1,1) pairs, so a 16-byte-per-lane load of
 // consecutive slots reads one contiguous piece and the slot row stays 2 KB
-__device__ __forceinline__ dv4 blk_split_local(const double* __restrict__ v, int64_t k) {
+template <class VT>
+__device__ __forceinline__ dv4 blk_split_local(const VT* __restrict__ v, int64_t k) {
+  typedef typename vvec<VT>::v2 V2;
   const int64_t r = k & ~(int64_t)63, i = k & 63;
-  const dv2 a = reinterpret_cast<const dv2*>(v + 4 * r)[i];
-  const dv2 b = reinterpret_cast<const dv2*>(v + 4 * r + 128)[i];
+  const dv2 a = widen2<VT>(reinterpret_cast<const V2*>(v + 4 * r)[i]);
+  const dv2 b = widen2<VT>(reinterpret_cast<const V2*>(v + 4 * r + 128)[i]);
   return dv4{a.x, a.y, b.x, b.y};
 }
-template <int SPL>
-__device__ __forceinline__ dv4 blk_any(const double* __restrict__ v, int64_t nbs, int64_t k) {
-  if (SPL == 1) return blk_split(v, nbs, k);
-  if (SPL == 2) return blk_split_local(v, k);
-  return reinterpret_cast<const dv4*>(v)[k];
+template <int SPL, class VT>
+__device__ __forceinline__ dv4 blk_any(const VT* __restrict__ v, int64_t nbs, int64_t k) {
+  typedef typename vvec<VT>::v4 V4;
+  if (SPL == 1) return blk_split<VT>(v, nbs, k);
+  if (SPL == 2) return blk_split_local<VT>(v, k);
+  return widen4<VT>(reinterpret_cast<const V4*>(v)[k]);
 }
 
-template <int EPI, bool XFM, bool SYM, int U, bool SPL, int TAG>
+template <int EPI, bool XFM, bool SYM, int U, bool SPL, int TAG, class VT = double>
 __global__ __launch_bounds__(256) void sell2_kernel(
     int64_t nr, const int64_t* __restrict__ soff, const int32_t* __restrict__ meta,
-    const int32_t* __restrict__ bcol, const double* __restrict__ bval, int64_t nbs,
+    const int32_t* __restrict__ bcol, const VT* __restrict__ bval, int64_t nbs,
     const double* __restrict__ x, int64_t xs, const double* y, const double* __restrict__ b,
     int64_t bs, const dv4* __restrict__ W, double* out, int64_t os, int remap,
     const int32_t* __restrict__ sched, int lsort) {
   const int64_t slot = (sched ? (int64_t)sched[blockIdx.x] : row_block(remap)) * 256 + threadIdx.x;
   if (slot >= nr) return;
-  const double* offd = SYM ? bval + 2 * nbs : nullptr;
+  const VT* offd = SYM ? bval + 2 * nbs : nullptr;
   const int m = meta[slot];
   const int len = m & 0xffff;
   int64_t k = soff[slot / SELL_C] + (slot & (SELL_C - 1));
@@ -530,7 +555,7 @@ __global__ __launch_bounds__(256) void sell2_kernel(
     for (int u = 0; u < U; ++u) {
       const int64_t kk = k + (int64_t)SELL_C * (j + u < len ? j + u : len - 1);
       c[u] = bcol[kk];
-      v[u] = SPL ? blk_split(bval, nbs, kk) : blk<SYM>(bval, offd, kk);
+      v[u] = SPL ? blk_split<VT>(bval, nbs, kk) : blk<SYM, false, VT>(bval, offd, kk);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) a[u] = xget<XFM>(x, xs, c[u]);
@@ -578,10 +603,11 @@ __global__ __launch_bounds__(256) void sell2_kernel(
 // the block loop.  Used for the level-0 fused post operator
 // z = x1 + W r1 + K e (EPI_KPOST, LPR 2, U 5: K 1.69 -> 1.54 ms on one
 // upload) and the SELL-stored coarse operators.
-template <int LPR, int U, int EPI, bool XFM, bool SYM, int SPL, int TAG, int PROBE = 0, bool C16 = false>
+template <int LPR, int U, int EPI, bool XFM, bool SYM, int SPL, int TAG, int PROBE = 0, bool C16 = false,
+          class VT = double>
 __global__ __launch_bounds__(256) void msell_kernel(
     int64_t nr, const int64_t* __restrict__ soff, const int32_t* __restrict__ meta,
-    const int32_t* __restrict__ bcol, const double* __restrict__ bval, int64_t nbs,
+    const int32_t* __restrict__ bcol, const VT* __restrict__ bval, int64_t nbs,
     const double* __restrict__ x, int64_t xs, const double* y, const double* __restrict__ b, int64_t bs,
     const dv4* __restrict__ W, double* out, int64_t os, int remap, int lsort, int64_t rb0,
     const uint16_t* __restrict__ c16, const int32_t* __restrict__ cbase) {
@@ -597,7 +623,7 @@ __global__ __launch_bounds__(256) void msell_kernel(
   // the row this slot holds (DBsr::lsort: rows sorted by length in the slice)
   const int64_t node = lsort ? (ns & ~(int64_t)(SELL_C - 1)) | ((m >> 16) & (SELL_C - 1)) : ns;
   const int64_t nd = node;
-  const double* offd = SYM ? bval + 2 * nbs : nullptr;
+  const VT* offd = SYM ? bval + 2 * nbs : nullptr;
   const int f = q & 1;
   const bool wr = q < 2;
   constexpr bool NB = EPI == EPI_RESID || EPI == EPI_BJAC || EPI == EPI_KPOST;
@@ -618,7 +644,7 @@ __global__ __launch_bounds__(256) void msell_kernel(
       const int64_t kk = k + (int64_t)SELL_C * (j + u < j1 ? j + u : j1 - 1);
       if constexpr (C16) c[u] = cb0 + (int32_t)c16[kk];
       else c[u] = PROBE == 2 ? __builtin_nontemporal_load(bcol + kk) : bcol[kk];
-      v[u] = SPL ? blk_any<SPL>(bval, nbs, kk) : blk<SYM, (PROBE >= 2)>(bval, offd, kk);
+      v[u] = SPL ? blk_any<SPL, VT>(bval, nbs, kk) : blk<SYM, (PROBE >= 2), VT>(bval, offd, kk);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u)   // PROBE 1 (A/B only, wrong results): no gather, the column as the value
@@ -681,18 +707,18 @@ __device__ __forceinline__ T ld_once(const T* p) {
   else return *p;
 }
 
-template <int EPI, bool XFM, int U, bool GH, int TAG>
+template <int EPI, bool XFM, int U, bool GH, int TAG, class VT = double>
 __global__ __launch_bounds__(256) void hsell2_kernel(
     int64_t row0, int64_t nr, const int32_t* __restrict__ meta, const int32_t* __restrict__ ucol,
-    const double* __restrict__ uval, int64_t nbs, int hwu, const int32_t* __restrict__ lptr, int hwl,
-    const int64_t* __restrict__ gsoff, const int32_t* __restrict__ gcol, const double* __restrict__ gval,
+    const VT* __restrict__ uval, int64_t nbs, int hwu, const int32_t* __restrict__ lptr, int hwl,
+    const int64_t* __restrict__ gsoff, const int32_t* __restrict__ gcol, const VT* __restrict__ gval,
     int64_t ngs, const double* __restrict__ x, int64_t xs, const double* y, const double* __restrict__ b,
     int64_t bs, const dv4* __restrict__ W, double* out, int64_t os, int remap,
     const int32_t* __restrict__ sched) {
   const int64_t blk0 = sched ? (int64_t)sched[blockIdx.x] : row_block(remap);
   const int64_t node = row0 + blk0 * 256 + threadIdx.x;   // rows [row0, nr)
   if (node >= nr) return;
-  const double* offd = uval + 2 * nbs;
+  const VT* offd = uval + 2 * nbs;
   const int m = ld_once(meta + node);
   const int ulen = m & 0xff, llen = (m >> 8) & 0xff;
   const uint32_t urow = 64u * (uint32_t)hwu;
@@ -708,7 +734,7 @@ __global__ __launch_bounds__(256) void hsell2_kernel(
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int32_t c = (int32_t)((p[u] / urow) * 64u + (p[u] & 63u));
-        v[u] = blk<true>(uval, offd, p[u]);
+        v[u] = blk<true, false, VT>(uval, offd, p[u]);
         a[u] = xget<XFM>(x, xs, c);
       }
 #pragma unroll
@@ -729,7 +755,7 @@ __global__ __launch_bounds__(256) void hsell2_kernel(
       for (int u = 0; u < U; ++u) {
         const int64_t kk = k + (int64_t)SELL_C * (j + u < ulen ? j + u : ulen - 1);
         c[u] = ld_once(ucol + kk);
-        v[u] = blk<true>(uval, offd, kk);
+        v[u] = blk<true, false, VT>(uval, offd, kk);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) a[u] = xget<XFM>(x, xs, c[u]);
@@ -744,7 +770,7 @@ __global__ __launch_bounds__(256) void hsell2_kernel(
   if (GH) {   // ghost columns (after every owned column in the row's order)
     const int glen = m >> 16;
     const int64_t k = gsoff[node >> 6] + (node & 63);
-    const double* goff = gval + 2 * ngs;
+    const VT* goff = gval + 2 * ngs;
     for (int j = 0; j < glen; j += U) {
       int32_t c[U];
       dv4 v[U];
@@ -753,7 +779,7 @@ __global__ __launch_bounds__(256) void hsell2_kernel(
       for (int u = 0; u < U; ++u) {
         const int64_t kk = k + (int64_t)SELL_C * (j + u < glen ? j + u : glen - 1);
         c[u] = gcol[kk];
-        v[u] = blk<true>(gval, goff, kk);
+        v[u] = blk<true, false, VT>(gval, goff, kk);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) a[u] = xget<XFM>(x, xs, c[u]);
@@ -2973,6 +2999,9 @@ struct DBsr {              // 2x2 blocks, node-major
   int32_t* rsched = nullptr;
   int64_t nrsched = 0;
   int rsched_vl = 0;
+  // values stored fp32 (dev_set_cycle_storage): val then points to a float
+  // array of the same element layout, read by the kernels' float side
+  bool f32 = false;
 };
 
 struct DLevel {
@@ -2982,6 +3011,12 @@ struct DLevel {
   DBsr Ab, Pb, Rb;         // BSR2 layout
   DBsr PAb;                // BSR2 post fusion: merged [P | AP] rows (ptr: 2 nr + 1)
   DBsr KPb;                // BSR2 post fusion: K = P - W (A P), one operator (default)
+  // fp32 cycle storage (dev_set_cycle_storage), level 0 only: A_0 as the cycle
+  // reads it -- Ab's layout with fp32 copies of its value arrays (Ac.f32), the
+  // index arrays shared; Ab itself stays fp64 for the Krylov operator.  On the
+  // other narrowed levels Ab's values are replaced in place.
+  DBsr Ac;
+  int storage = 0;         // mamg_level_storage bits: 1 A, 2 K / P, 4 R stored fp32
   dv4* Wd = nullptr;       // BSR2 layout: 2x2 smoother block per node
   double* winv = nullptr;
   // SMOOTHER_POLY: the step smoothers w_k W, k = 1..m (BSR2: Wk; CSR: WBk
@@ -5034,9 +5069,13 @@ double index_bytes(const DBsr& M, int64_t ptr_entries) {
 double bsr_bytes(const DBsr& M, int epi) {
   // half-symmetric: upper blocks (28 B with column) + 4-byte mirror slot per
   // lower block + row meta; the mirrors' values are re-reads, not counted
-  double b = M.half ? 28.0 * (M.nb - M.nlo) + 4.0 * M.nlo + 4.0 * M.nr + (M.ngs ? 8.0 * (M.nr / SELL_C + 2) : 0.0) +
+  // fp32 storage (M.f32): 4 bytes per stored value instead of 8, so a block
+  // with its column is 16 B (SYM / half), 18 B (16-bit column) or 20 B
+  const double vb = M.f32 ? 4.0 : 8.0;
+  const double sym_b = 3.0 * vb + 4.0, c16_b = 4.0 * vb + 2.0, gen_b = 4.0 * vb + 4.0;
+  double b = M.half ? sym_b * (M.nb - M.nlo) + 4.0 * M.nlo + 4.0 * M.nr + (M.ngs ? 8.0 * (M.nr / SELL_C + 2) : 0.0) +
                           16.0 * M.nc + 16.0 * M.nr
-                    : (M.sym ? 28.0 : M.col16 ? 34.0 : 36.0) * M.nb + index_bytes(M, M.nr + 1) +
+                    : (M.sym ? sym_b : M.col16 ? c16_b : gen_b) * M.nb + index_bytes(M, M.nr + 1) +
                           (M.col16 ? 4.0 * (M.nr / SELL_C + 1) : 0.0) + 16.0 * M.nc + 16.0 * M.nr;
   if (epi == EPI_YADD) b += 16.0 * M.nr;
   if (epi == EPI_RESID) b += 16.0 * M.nr;
@@ -5748,6 +5787,9 @@ bool starts_with_bd(const DeviceHandle* h, int l) {
 }
 
 // x1_ready: X = W b is already in L.t (written by the restriction's EPI_YBD)
+// A_l as the cycle reads it: level 0's fp32 copy once the handle is narrowed
+inline const DBsr& cyc_A(const DLevel& L) { return L.Ac.f32 ? L.Ac : L.Ab; }
+
 void cycle_ops_bsr(const DeviceHandle* h, int l, const double* b, int64_t bs, double* xout,
                    int64_t os, std::vector<Op>* ops, bool tail_ok, bool x1_ready) {
   if (tail_ok && l > 0 && l == h->tail_level && bs == 0 && os == 0 && tail_ops(h, l, b, xout, ops)) return;
@@ -5792,11 +5834,11 @@ void cycle_ops_bsr(const DeviceHandle* h, int l, const double* b, int64_t bs, do
     o.bytes = 32.0 * nv + 16.0 * nv + 16.0 * nv;
     if (!x1_ready) ops->push_back(o);
     for (int s = 1; s < npre; ++s) {
-      ops->push_back(bsr_op(L.Ab, EPI_BJAC, clsS, tagA, X, 0, X, b, bs, step_wd(L, s, true), X2, 0));
+      ops->push_back(bsr_op(cyc_A(L), EPI_BJAC, clsS, tagA, X, 0, X, b, bs, step_wd(L, s, true), X2, 0));
       std::swap(X, X2);
     }
   }
-  ops->push_back(bsr_op(L.Ab, EPI_RESID, l0 ? C_L0_RESID : C_COARSE, tagA, X, 0, nullptr, b, bs,
+  ops->push_back(bsr_op(cyc_A(L), EPI_RESID, l0 ? C_L0_RESID : C_COARSE, tagA, X, 0, nullptr, b, bs,
                         nullptr, L.r, 0));
   ops->push_back(bsr_op(L.Rb, EPI_Y, l0 ? C_L0_R : C_COARSE, tagA, L.r, 0, nullptr, nullptr, 0,
                         nullptr, C.b, 0));
@@ -5853,7 +5895,7 @@ void cycle_ops_bsr(const DeviceHandle* h, int l, const double* b, int64_t bs, do
   for (int s = s0; s < npost; ++s) {
     const bool last = s == npost - 1;
     double* out = last ? xout : X2;
-    ops->push_back(bsr_op(L.Ab, EPI_BJAC, clsS, tagA, X, 0, X, b, bs, step_wd(L, s, false), out,
+    ops->push_back(bsr_op(cyc_A(L), EPI_BJAC, clsS, tagA, X, 0, X, b, bs, step_wd(L, s, false), out,
                           last ? os : 0));
     if (!last) std::swap(X, X2);
   }
@@ -5866,7 +5908,7 @@ void apply_ops(const DeviceHandle* h, const double* r, double* z, std::vector<Op
     const int64_t nv = L0.n / 2;
     cycle_ops_bsr(h, 0, r, nv, z, nv, ops);
     for (int it = 1; it < h->p.maxit; ++it) {   // z += MG(r - A z), field-major
-      ops->push_back(bsr_op(L0.Ab, EPI_RESID, C_MISC, 1, z, nv, nullptr, r, nv, nullptr, L0.c, nv));
+      ops->push_back(bsr_op(cyc_A(L0), EPI_RESID, C_MISC, 1, z, nv, nullptr, r, nv, nullptr, L0.c, nv));
       cycle_ops_bsr(h, 0, L0.c, nv, L0.e, nv, ops);
       ops->push_back(axpy_op(L0.n, L0.e, z));
     }
@@ -5926,7 +5968,7 @@ void launch_csr_tag(const Op& o, hipStream_t s) {
 
 // rows [o.r0, o.r1) when o.r1 >= 0 (the distributed K's overlap split: r0 a
 // multiple of 256, r1 too or = nr, so each workgroup's rows lie in the range)
-template <int VL, bool XFM, bool SYM, int TAG>
+template <int VL, bool XFM, bool SYM, int TAG, class VT = double>
 void launch_bsr_x(const Op& o, hipStream_t s) {
   const DBsr& M = *o.Mb;
   const bool rng = o.r1 >= 0;
@@ -5934,39 +5976,39 @@ void launch_bsr_x(const Op& o, hipStream_t s) {
   if (r1 <= r0) return;
   const int64_t b0 = r0 * VL / 256;
   const unsigned g = (unsigned)(nblocks(r1 * (int64_t)VL) - b0);
-#define BSR_ARGS r1, M.ptr, M.col, M.val, o.x, o.xs, o.y, o.b, o.bs, o.W, o.out, o.os, remap_of(o), \
+#define BSR_ARGS r1, M.ptr, M.col, reinterpret_cast<const VT*>(M.val), o.x, o.xs, o.y, o.b, o.bs, o.W, o.out, o.os, remap_of(o), \
     (!rng && M.rsched && M.rsched_vl == VL && (int64_t)g == M.nrsched) ? M.rsched : nullptr, b0
   switch (o.epi) {
-    case EPI_Y: bsr2_kernel<VL, EPI_Y, XFM, SYM, TAG><<<g, 256, 0, s>>>(BSR_ARGS); break;
+    case EPI_Y: bsr2_kernel<VL, EPI_Y, XFM, SYM, TAG, false, VT><<<g, 256, 0, s>>>(BSR_ARGS); break;
     case EPI_YBD:   // restrictions only: node-interleaved, never symmetric
-      if constexpr (!XFM && !SYM) bsr2_kernel<VL, EPI_YBD, false, false, TAG><<<g, 256, 0, s>>>(BSR_ARGS);
+      if constexpr (!XFM && !SYM) bsr2_kernel<VL, EPI_YBD, false, false, TAG, false, VT><<<g, 256, 0, s>>>(BSR_ARGS);
       break;
-    case EPI_YADD: bsr2_kernel<VL, EPI_YADD, XFM, SYM, TAG><<<g, 256, 0, s>>>(BSR_ARGS); break;
-    case EPI_RESID: bsr2_kernel<VL, EPI_RESID, XFM, SYM, TAG><<<g, 256, 0, s>>>(BSR_ARGS); break;
+    case EPI_YADD: bsr2_kernel<VL, EPI_YADD, XFM, SYM, TAG, false, VT><<<g, 256, 0, s>>>(BSR_ARGS); break;
+    case EPI_RESID: bsr2_kernel<VL, EPI_RESID, XFM, SYM, TAG, false, VT><<<g, 256, 0, s>>>(BSR_ARGS); break;
     case EPI_KPOST:   // K is never symmetric and e is node-major
-      if constexpr (!XFM && !SYM) bsr2_kernel<VL, EPI_KPOST, false, false, TAG><<<g, 256, 0, s>>>(BSR_ARGS);
+      if constexpr (!XFM && !SYM) bsr2_kernel<VL, EPI_KPOST, false, false, TAG, false, VT><<<g, 256, 0, s>>>(BSR_ARGS);
       break;
-    default: bsr2_kernel<VL, EPI_BJAC, XFM, SYM, TAG><<<g, 256, 0, s>>>(BSR_ARGS); break;
+    default: bsr2_kernel<VL, EPI_BJAC, XFM, SYM, TAG, false, VT><<<g, 256, 0, s>>>(BSR_ARGS); break;
   }
 #undef BSR_ARGS
 }
 
-template <bool XFM, bool SYM, int U, bool NT, int TAG>
+template <bool XFM, bool SYM, int U, bool NT, int TAG, class VT = double>
 void launch_sell_u(const Op& o, hipStream_t s) {
   const DBsr& M = *o.Mb;
   const unsigned g = nblocks(M.nr);
   if (g == 0) return;
-#define SELL_ARGS M.nr, M.soff, M.meta, M.col, M.val, M.nbs, o.x, o.xs, o.y, o.b, o.bs, o.W, o.out, o.os, \
+#define SELL_ARGS M.nr, M.soff, M.meta, M.col, reinterpret_cast<const VT*>(M.val), M.nbs, o.x, o.xs, o.y, o.b, o.bs, o.W, o.out, o.os, \
     0, \
     ((int64_t)g == M.nsched ? M.sched : nullptr), M.lsort ? 1 : 0
   switch (o.epi) {
-    case EPI_Y: sell2_kernel<EPI_Y, XFM, SYM, U, NT, TAG><<<g, 256, 0, s>>>(SELL_ARGS); break;
-    case EPI_YADD: sell2_kernel<EPI_YADD, XFM, SYM, U, NT, TAG><<<g, 256, 0, s>>>(SELL_ARGS); break;
-    case EPI_RESID: sell2_kernel<EPI_RESID, XFM, SYM, U, NT, TAG><<<g, 256, 0, s>>>(SELL_ARGS); break;
+    case EPI_Y: sell2_kernel<EPI_Y, XFM, SYM, U, NT, TAG, VT><<<g, 256, 0, s>>>(SELL_ARGS); break;
+    case EPI_YADD: sell2_kernel<EPI_YADD, XFM, SYM, U, NT, TAG, VT><<<g, 256, 0, s>>>(SELL_ARGS); break;
+    case EPI_RESID: sell2_kernel<EPI_RESID, XFM, SYM, U, NT, TAG, VT><<<g, 256, 0, s>>>(SELL_ARGS); break;
     case EPI_KPOST:
-      if constexpr (!XFM && !SYM) sell2_kernel<EPI_KPOST, false, false, U, NT, TAG><<<g, 256, 0, s>>>(SELL_ARGS);
+      if constexpr (!XFM && !SYM) sell2_kernel<EPI_KPOST, false, false, U, NT, TAG, VT><<<g, 256, 0, s>>>(SELL_ARGS);
       break;
-    default: sell2_kernel<EPI_BJAC, XFM, SYM, U, NT, TAG><<<g, 256, 0, s>>>(SELL_ARGS); break;
+    default: sell2_kernel<EPI_BJAC, XFM, SYM, U, NT, TAG, VT><<<g, 256, 0, s>>>(SELL_ARGS); break;
   }
 #undef SELL_ARGS
 }
@@ -5974,7 +6016,7 @@ void launch_sell_u(const Op& o, hipStream_t s) {
 // rows [o.r0, o.r1) when o.r1 >= 0: the bounds are multiples of 256 (or
 // r1 = nr), so every workgroup of every LPR covers whole 64-row slices of
 // the range (dist K_ROWS_ALIGN)
-template <int LPR, int U, bool XFM, bool SYM, int SPL, int TAG, int PROBE = 0>
+template <int LPR, int U, bool XFM, bool SYM, int SPL, int TAG, int PROBE = 0, class VT = double>
 void launch_msell(const Op& o, hipStream_t s) {
   const DBsr& M = *o.Mb;
   const int64_t rows = 256 / LPR;
@@ -5982,21 +6024,21 @@ void launch_msell(const Op& o, hipStream_t s) {
   if (r1 <= r0) return;
   const int64_t b0 = r0 / rows;
   const unsigned g = (unsigned)((r1 + rows - 1) / rows - b0);
-#define MSELL_ARGS r1, M.soff, M.meta, M.col, M.val, M.nbs, o.x, o.xs, o.y, o.b, o.bs, o.W, o.out, o.os, \
+#define MSELL_ARGS r1, M.soff, M.meta, M.col, reinterpret_cast<const VT*>(M.val), M.nbs, o.x, o.xs, o.y, o.b, o.bs, o.W, o.out, o.os, \
     (TAG == 0 && M.kvar == 3) ? 1 : 0, M.lsort ? 1 : 0, b0, M.col16, M.cbase
   switch (o.epi) {
-    case EPI_Y: msell_kernel<LPR, U, EPI_Y, XFM, SYM, SPL, TAG, PROBE><<<g, 256, 0, s>>>(MSELL_ARGS); break;
-    case EPI_YADD: msell_kernel<LPR, U, EPI_YADD, XFM, SYM, SPL, TAG, PROBE><<<g, 256, 0, s>>>(MSELL_ARGS); break;
-    case EPI_RESID: msell_kernel<LPR, U, EPI_RESID, XFM, SYM, SPL, TAG, PROBE><<<g, 256, 0, s>>>(MSELL_ARGS); break;
+    case EPI_Y: msell_kernel<LPR, U, EPI_Y, XFM, SYM, SPL, TAG, PROBE, false, VT><<<g, 256, 0, s>>>(MSELL_ARGS); break;
+    case EPI_YADD: msell_kernel<LPR, U, EPI_YADD, XFM, SYM, SPL, TAG, PROBE, false, VT><<<g, 256, 0, s>>>(MSELL_ARGS); break;
+    case EPI_RESID: msell_kernel<LPR, U, EPI_RESID, XFM, SYM, SPL, TAG, PROBE, false, VT><<<g, 256, 0, s>>>(MSELL_ARGS); break;
     case EPI_KPOST:
       if constexpr (!XFM && !SYM) {
         if (TAG == 0 && PROBE == 0 && M.col16)   // level-0 K with 16-bit columns (compress_sell_cols)
-          msell_kernel<LPR, U, EPI_KPOST, false, false, SPL, TAG, 0, true><<<g, 256, 0, s>>>(MSELL_ARGS);
+          msell_kernel<LPR, U, EPI_KPOST, false, false, SPL, TAG, 0, true, VT><<<g, 256, 0, s>>>(MSELL_ARGS);
         else
-          msell_kernel<LPR, U, EPI_KPOST, false, false, SPL, TAG, PROBE><<<g, 256, 0, s>>>(MSELL_ARGS);
+          msell_kernel<LPR, U, EPI_KPOST, false, false, SPL, TAG, PROBE, false, VT><<<g, 256, 0, s>>>(MSELL_ARGS);
       }
       break;
-    default: msell_kernel<LPR, U, EPI_BJAC, XFM, SYM, SPL, TAG, PROBE><<<g, 256, 0, s>>>(MSELL_ARGS); break;
+    default: msell_kernel<LPR, U, EPI_BJAC, XFM, SYM, SPL, TAG, PROBE, false, VT><<<g, 256, 0, s>>>(MSELL_ARGS); break;
   }
 #undef MSELL_ARGS
 }
@@ -6007,9 +6049,11 @@ void launch_msell(const Op& o, hipStream_t s) {
 // of 3; 4 / 5 the default with non-temporal loads of the columns and values /
 // the values only (the K stream kept from evicting the gathered e from L2);
 // 9 a probe without the e gathers (wrong results, timing only)
-template <int SPL>
+template <int SPL, class VT = double>
 bool launch_kvariant(const Op& o, hipStream_t s) {
-  switch (o.Mb->kvar) {
+  // fp32 storage: the product kernel only (the A/B variants stay fp64)
+  if constexpr (sizeof(VT) == 4) { launch_msell<2, 5, false, false, SPL, 0, 0, VT>(o, s); return true; }
+  else switch (o.Mb->kvar) {
     case 4: launch_msell<2, 5, false, false, SPL, 0, 2>(o, s); return true;
     case 5: launch_msell<2, 5, false, false, SPL, 0, 3>(o, s); return true;
     case 1: return SPL == 2 ? (launch_msell<1, 6, false, false, SPL, 0>(o, s), true) : false;
@@ -6027,48 +6071,48 @@ bool launch_kvariant(const Op& o, hipStream_t s) {
 // 
 bool k_ranges_ok(const DBsr& K) { return !K.sell || !(K.kvar == 1 && K.split != 2); }
 
-template <bool XFM, bool SYM, int TAG>
+template <bool XFM, bool SYM, int TAG, class VT = double>
 void launch_sell_x(const Op& o, hipStream_t s) {
   // level-0 K operator: two lanes per row (launch_kvariant); multi-lane SELL
   // coarse operators: lanes per row from the mean row length; everything else
   // one lane, chunks of 8
   if constexpr (TAG == 0 && !XFM && !SYM) {
-    if (o.epi == EPI_KPOST && (o.Mb->split == 2   ? launch_kvariant<2>(o, s)
-                               : o.Mb->split ? launch_kvariant<1>(o, s)
-                                             : launch_kvariant<0>(o, s)))
+    if (o.epi == EPI_KPOST && (o.Mb->split == 2   ? launch_kvariant<2, VT>(o, s)
+                               : o.Mb->split ? launch_kvariant<1, VT>(o, s)
+                                             : launch_kvariant<0, VT>(o, s)))
       return;
   }
   if constexpr (!XFM) {
     if (o.Mb->lpr > 1 && !o.Mb->split) {
       switch (o.Mb->lpr) {
-        case 2: launch_msell<2, 5, false, SYM, false, TAG>(o, s); return;
-        case 4: launch_msell<4, 5, false, SYM, false, TAG>(o, s); return;
-        case 8: launch_msell<8, 5, false, SYM, false, TAG>(o, s); return;
-        default: launch_msell<16, 5, false, SYM, false, TAG>(o, s); return;
+        case 2: launch_msell<2, 5, false, SYM, false, TAG, 0, VT>(o, s); return;
+        case 4: launch_msell<4, 5, false, SYM, false, TAG, 0, VT>(o, s); return;
+        case 8: launch_msell<8, 5, false, SYM, false, TAG, 0, VT>(o, s); return;
+        default: launch_msell<16, 5, false, SYM, false, TAG, 0, VT>(o, s); return;
       }
     }
   }
-  if (o.Mb->split && TAG == 0) launch_sell_u<XFM, SYM, post_u, true, TAG>(o, s);
-  else if (o.Mb->split) launch_sell_u<XFM, SYM, sell_u, true, TAG>(o, s);
-  else if (TAG == 0 && o.epi == EPI_KPOST) launch_sell_u<XFM, SYM, post_u, false, TAG>(o, s);
-  else launch_sell_u<XFM, SYM, sell_u, false, TAG>(o, s);
+  if (o.Mb->split && TAG == 0) launch_sell_u<XFM, SYM, post_u, true, TAG, VT>(o, s);
+  else if (o.Mb->split) launch_sell_u<XFM, SYM, sell_u, true, TAG, VT>(o, s);
+  else if (TAG == 0 && o.epi == EPI_KPOST) launch_sell_u<XFM, SYM, post_u, false, TAG, VT>(o, s);
+  else launch_sell_u<XFM, SYM, sell_u, false, TAG, VT>(o, s);
 }
 
-template <int TAG>
+template <int TAG, class VT = double>
 void launch_sell(const Op& o, hipStream_t s) {
   if (o.Mb->sym) {
-    if (o.xfm) launch_sell_x<true, true, TAG>(o, s); else launch_sell_x<false, true, TAG>(o, s);
+    if (o.xfm) launch_sell_x<true, true, TAG, VT>(o, s); else launch_sell_x<false, true, TAG, VT>(o, s);
   } else {
-    if (o.xfm) launch_sell_x<true, false, TAG>(o, s); else launch_sell_x<false, false, TAG>(o, s);
+    if (o.xfm) launch_sell_x<true, false, TAG, VT>(o, s); else launch_sell_x<false, false, TAG, VT>(o, s);
   }
 }
 
-template <int VL, int TAG>
+template <int VL, int TAG, class VT = double>
 void launch_bsr_vl(const Op& o, hipStream_t s) {
   if (o.Mb->sym) {
-    if (o.xfm) launch_bsr_x<VL, true, true, TAG>(o, s); else launch_bsr_x<VL, false, true, TAG>(o, s);
+    if (o.xfm) launch_bsr_x<VL, true, true, TAG, VT>(o, s); else launch_bsr_x<VL, false, true, TAG, VT>(o, s);
   } else {
-    if (o.xfm) launch_bsr_x<VL, true, false, TAG>(o, s); else launch_bsr_x<VL, false, false, TAG>(o, s);
+    if (o.xfm) launch_bsr_x<VL, true, false, TAG, VT>(o, s); else launch_bsr_x<VL, false, false, TAG, VT>(o, s);
   }
 }
 
@@ -6100,53 +6144,65 @@ void launch_post_tag(const Op& o, hipStream_t s) {
   }
 }
 
-template <bool XFM, int U, bool GH, int TAG>
+template <bool XFM, int U, bool GH, int TAG, class VT = double>
 void launch_half_u(const Op& o, hipStream_t s) {
   const DBsr& M = *o.Mb;
   const int64_t r0 = o.r1 < 0 ? 0 : o.r0, r1 = o.r1 < 0 ? M.nr : o.r1;
   const unsigned g = nblocks(r1 - r0);
   if (r1 <= r0) return;
-#define HALF_ARGS r0, r1, M.meta, M.col, M.val, M.nbs, M.hwu, M.lptr, M.hwl, M.gsoff, M.gcol, M.gval, M.ngs, \
+#define HALF_ARGS r0, r1, M.meta, M.col, reinterpret_cast<const VT*>(M.val), M.nbs, M.hwu, M.lptr, M.hwl, M.gsoff, M.gcol, \
+    reinterpret_cast<const VT*>(M.gval), M.ngs, \
     o.x, o.xs, o.y, o.b, o.bs, o.W, o.out, o.os, 1, \
     (r0 == 0 && r1 == M.nr && (int64_t)g == M.nsched) ? M.sched \
     : (r0 == M.sr0 && r1 == M.sr1 && (int64_t)g == M.nsched_r) ? M.sched_r : nullptr
   switch (o.epi) {
-    case EPI_Y: hsell2_kernel<EPI_Y, XFM, U, GH, TAG><<<g, 256, 0, s>>>(HALF_ARGS); break;
-    case EPI_YADD: hsell2_kernel<EPI_YADD, XFM, U, GH, TAG><<<g, 256, 0, s>>>(HALF_ARGS); break;
-    case EPI_RESID: hsell2_kernel<EPI_RESID, XFM, U, GH, TAG><<<g, 256, 0, s>>>(HALF_ARGS); break;
+    case EPI_Y: hsell2_kernel<EPI_Y, XFM, U, GH, TAG, VT><<<g, 256, 0, s>>>(HALF_ARGS); break;
+    case EPI_YADD: hsell2_kernel<EPI_YADD, XFM, U, GH, TAG, VT><<<g, 256, 0, s>>>(HALF_ARGS); break;
+    case EPI_RESID: hsell2_kernel<EPI_RESID, XFM, U, GH, TAG, VT><<<g, 256, 0, s>>>(HALF_ARGS); break;
     case EPI_KPOST: break;   // A is never the K operator
-    default: hsell2_kernel<EPI_BJAC, XFM, U, GH, TAG><<<g, 256, 0, s>>>(HALF_ARGS); break;
+    default: hsell2_kernel<EPI_BJAC, XFM, U, GH, TAG, VT><<<g, 256, 0, s>>>(HALF_ARGS); break;
   }
 #undef HALF_ARGS
 }
 
-template <bool XFM, bool GH, int TAG>
+template <bool XFM, bool GH, int TAG, class VT = double>
 void launch_half_x(const Op& o, hipStream_t s) {
-  launch_half_u<XFM, 4, GH, TAG>(o, s);
+  launch_half_u<XFM, 4, GH, TAG, VT>(o, s);
 }
 
-template <int TAG>
+template <int TAG, class VT = double>
 void launch_half(const Op& o, hipStream_t s) {
   const bool gh = o.Mb->ngs > 0;
+  if constexpr (sizeof(VT) == 4) {   // fp32 storage is single-GPU: the ghost-free form only
+    if (o.xfm) launch_half_x<true, false, TAG, VT>(o, s); else launch_half_x<false, false, TAG, VT>(o, s);
+    return;
+  }
   if (o.xfm) {
-    if (gh) launch_half_x<true, true, TAG>(o, s); else launch_half_x<true, false, TAG>(o, s);
+    if (gh) launch_half_x<true, true, TAG, VT>(o, s); else launch_half_x<true, false, TAG, VT>(o, s);
   } else {
-    if (gh) launch_half_x<false, true, TAG>(o, s); else launch_half_x<false, false, TAG>(o, s);
+    if (gh) launch_half_x<false, true, TAG, VT>(o, s); else launch_half_x<false, false, TAG, VT>(o, s);
   }
 }
 
+template <int TAG, class VT = double>
+void launch_bsr_st(const Op& o, hipStream_t s) {
+  if (o.Mb->half) { launch_half<TAG, VT>(o, s); return; }
+  if (o.Mb->sell) { launch_sell<TAG, VT>(o, s); return; }
+  switch (o.Mb->lanes) {
+    case 2: launch_bsr_vl<2, TAG, VT>(o, s); break;
+    case 4: launch_bsr_vl<4, TAG, VT>(o, s); break;
+    case 8: launch_bsr_vl<8, TAG, VT>(o, s); break;
+    case 16: launch_bsr_vl<16, TAG, VT>(o, s); break;
+    case 32: launch_bsr_vl<32, TAG, VT>(o, s); break;
+    default: launch_bsr_vl<64, TAG, VT>(o, s); break;
+  }
+}
+
+// DBsr::f32: the operator's values are stored fp32 (dev_set_cycle_storage)
 template <int TAG>
 void launch_bsr_tag(const Op& o, hipStream_t s) {
-  if (o.Mb->half) { launch_half<TAG>(o, s); return; }
-  if (o.Mb->sell) { launch_sell<TAG>(o, s); return; }
-  switch (o.Mb->lanes) {
-    case 2: launch_bsr_vl<2, TAG>(o, s); break;
-    case 4: launch_bsr_vl<4, TAG>(o, s); break;
-    case 8: launch_bsr_vl<8, TAG>(o, s); break;
-    case 16: launch_bsr_vl<16, TAG>(o, s); break;
-    case 32: launch_bsr_vl<32, TAG>(o, s); break;
-    default: launch_bsr_vl<64, TAG>(o, s); break;
-  }
+  if (o.Mb->f32) launch_bsr_st<TAG, float>(o, s);
+  else launch_bsr_st<TAG, double>(o, s);
 }
 
 template <int VL>
@@ -6929,6 +6985,168 @@ int dev_level_format(const DeviceHandle* h, int level) {
          (L.KPb.col16 ? MAMG_FMT_K_COL16 : 0);
 }
 
+// ---------------------------------------------------------------------------
+// fp32 storage of the operators the cycle streams (mamg_set_cycle_storage,
+// DESIGN.md section 4.7).  The fp32 arrays keep the element layout of the fp64
+// ones (blk / blk_split / blk_split_local at VT = float), so one element-wise
+// pair of kernels serves every value-array shape: general, SYM, half-symmetric
+// upper part, SELL padding and both split layouts.
+// ---------------------------------------------------------------------------
+namespace {
+
+constexpr unsigned F32_BLOCKS = 4096;   // grid-stride passes over a value array
+
+// a finite fp64 value whose fp32 rounding is not finite: not representable
+__global__ __launch_bounds__(256) void f32_check_kernel(int64_t n, const double* __restrict__ v, int* bad) {
+  bool b = false;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const double x = v[i];
+    b = b || (isfinite(x) && !isfinite((float)x));
+  }
+  if (b) atomicOr(bad, 1);
+}
+
+// round to nearest even (v_cvt_f32_f64 in the default rounding mode): numpy's
+// astype(float32); padding slots are converted like any value
+__global__ __launch_bounds__(256) void f32_convert_kernel(int64_t n, const double* __restrict__ v,
+                                                         float* __restrict__ out) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    out[i] = (float)v[i];
+}
+
+inline unsigned f32_grid(int64_t n) { return (unsigned)std::min<int64_t>(F32_BLOCKS, (n + 255) / 256); }
+
+// stored values of an operator's main array (rehome_bsr's count)
+inline int64_t value_count(const DBsr& M) {
+  if (M.nr == 0 || !M.val) return 0;
+  const int64_t slots = (M.sell || M.half) ? M.nbs : M.nb;
+  return slots * ((M.sym || M.half) ? 3 : 4);
+}
+
+struct NarrowJob {
+  DBsr* src;        // the operator whose fp64 values are read
+  DBsr* dst;        // the operator that reads the fp32 copy (src itself, or level 0's Ac)
+  int level, bit;
+  float* val = nullptr;
+};
+
+// a handle-owned array that nothing reads any more (the caller has waited)
+void release_owned(DeviceHandle* h, void* old) {
+  if (!old) return;
+  const bool in_arena = (char*)old >= h->arena0 && (char*)old < h->arena1;
+  auto it = std::find(h->allocs.begin(), h->allocs.end(), old);
+  if (in_arena || it == h->allocs.end()) return;   // arena memory stays with the reservation
+  (void)raw_free(old);
+  h->allocs.erase(it);
+}
+
+}  // namespace
+
+int dev_level_storage(const DeviceHandle* h, int level) { return h->L[level].storage; }
+
+int dev_set_cycle_storage(DeviceHandle* h, int storage, std::string* err) {
+  std::lock_guard<std::recursive_mutex> lock(capture_mutex());
+  bool narrowed = false;
+  for (const DLevel& L : h->L) narrowed = narrowed || L.storage != 0;
+  if (storage == MAMG_STORE_F64) {
+    if (!narrowed) return MAMG_OK;
+    *err = "cycle storage: the fp64 originals of a narrowed handle are gone (fp32 storage is one way)";
+    return MAMG_ERR_UNSUPPORTED;
+  }
+  if (narrowed) return MAMG_OK;
+  if (!h->bsr) {
+    *err = "cycle storage: fp32 needs the BSR2 layout (this handle holds the CSR layout)";
+    return MAMG_ERR_UNSUPPORTED;
+  }
+  for (const DLevel& L : h->L) {
+    if (L.pcs.size() > 1) { *err = "cycle storage: fp32 is not available with SCHWARZ_PATCHES"; return MAMG_ERR_UNSUPPORTED; }
+    if (L.rcs.size() > 1) { *err = "cycle storage: fp32 is not available with SCHWARZ_RINGS"; return MAMG_ERR_UNSUPPORTED; }
+    if (L.gcs.size() > 1) { *err = "cycle storage: fp32 is not available with the GS / SGS smoothers"; return MAMG_ERR_UNSUPPORTED; }
+  }
+  if (gs_smoother(h->p) || patch_schwarz(h->p) || rings_schwarz(h->p)) {
+    *err = "cycle storage: fp32 is not available with the GS / SGS smoothers or the Schwarz smoothers";
+    return MAMG_ERR_UNSUPPORTED;
+  }
+  HIPCHK(hipSetDevice(h->device));
+  // the launch path's levels: below the coarse tail and above the coarsest
+  std::vector<NarrowJob> jobs;
+  for (int l = 0; l < (int)h->L.size(); ++l) {
+    DLevel& L = h->L[l];
+    if (L.coarsest || (h->tail_level > 0 && l >= h->tail_level)) break;
+    if (L.Ab.ngs > 0) {   // a rank-local A with ghost columns: the fp32 side is the ghost-free kernel
+      *err = "cycle storage: fp32 is not available for a half-symmetric A with a ghost part";
+      return MAMG_ERR_UNSUPPORTED;
+    }
+    if (value_count(L.Ab) > 0) jobs.push_back({&L.Ab, l == 0 ? &L.Ac : &L.Ab, l, 1});
+    if (value_count(L.KPb) > 0) jobs.push_back({&L.KPb, &L.KPb, l, 2});
+    if (value_count(L.Pb) > 0) jobs.push_back({&L.Pb, &L.Pb, l, 2});
+    if (value_count(L.Rb) > 0) jobs.push_back({&L.Rb, &L.Rb, l, 4});
+    // a merged [P | AP] (PAb, MAMG_POST_K=0) stays fp64: bsr2_post_kernel has no fp32 side
+  }
+  // wait for the handle's last work; the kernels below run on the null stream
+  if (h->last) HIPCHK(hipEventSynchronize(h->last));
+  if (h->cap) HIPCHK(hipStreamSynchronize(h->cap));
+  // 1. every array checked before any is converted: the handle stays untouched on refusal
+  int* bad = nullptr;
+  HIPCHK(raw_malloc((void**)&bad, sizeof(int), "tmp"));
+  int hbad = 0;
+  hipError_t e = dev_memset(bad, 0, sizeof(int));
+  for (const NarrowJob& j : jobs) {
+    const int64_t n = value_count(*j.src);
+    f32_check_kernel<<<f32_grid(n), 256>>>(n, j.src->val, bad);
+  }
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpy(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost);
+  (void)raw_free(bad);
+  HIPCHK(e);
+  if (hbad) {
+    *err = "cycle storage: an operator holds a finite value that is not representable in fp32";
+    return MAMG_ERR_UNSUPPORTED;
+  }
+  // 2. the fp32 arrays, all allocated before any operator changes
+  auto undo = [&]() {
+    for (NarrowJob& j : jobs)
+      if (j.val) (void)raw_free(j.val);
+  };
+  for (NarrowJob& j : jobs) {
+    const int64_t n = value_count(*j.src);
+    e = dev_malloc((void**)&j.val, (size_t)n * sizeof(float));
+    if (e != hipSuccess) break;
+    f32_convert_kernel<<<f32_grid(n), 256>>>(n, j.src->val, j.val);
+  }
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) e = null_sync();
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    undo();
+    *err = std::string("cycle storage: ") + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? MAMG_ERR_NOMEM : MAMG_ERR_HIP;
+  }
+  // 3. the cached graphs hold the fp64 op list: dropped, the next apply captures anew
+  for (auto& g : h->graphs) {
+    if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    if (g.graph) (void)hipGraphDestroy(g.graph);
+  }
+  h->graphs.clear();
+  for (auto& g : h->pcgs) g.release();
+  h->pcgs.clear();
+  // 4. swap the arrays in; the fp64 originals go back except A_0's (the Krylov operator)
+  for (NarrowJob& j : jobs) {
+    void* old = j.src->val;
+    if (j.dst != j.src) *j.dst = *j.src;   // level 0: Ac shares Ab's index arrays
+    j.dst->val = reinterpret_cast<double*>(j.val);
+    j.dst->f32 = true;
+    h->allocs.push_back(j.val);
+    if (j.dst == j.src) release_owned(h, old);
+    h->L[j.level].storage |= j.bit;
+  }
+  std::vector<Op> ops;
+  apply_ops(h, h->hr, h->hz, &ops);
+  h->apply_bytes = 0.0;
+  for (const Op& o : ops) h->apply_bytes += o.bytes;
+  return MAMG_OK;
+}
+
 mamg_params dev_params(const DeviceHandle* h) { return h->p; }
 const Switches& dev_switches(const DeviceHandle* h) { return h->sw; }
 void dev_kregion(const DeviceHandle* h, std::vector<double>* ms, int* kept) {
@@ -6981,7 +7199,7 @@ void debug_sums(DeviceHandle* h, const char* stage, bool konly) {
       const int per = (M.sym || M.half) ? 3 : 4;
       const int64_t slots = (M.sell || M.half) ? M.nbs : M.nb;
       std::snprintf(buf, sizeof buf, " L%zu.%s val %016llx col %016llx", l, m.first,
-                    hash(M.val, (size_t)slots * per * 8), hash(M.col, (size_t)slots * 4));
+                    hash(M.val, (size_t)slots * per * (M.f32 ? 4 : 8)), hash(M.col, (size_t)slots * 4));
       line += buf;
     }
     if (L.Wd) {

@@ -103,25 +103,36 @@ def _print_substitutions(precond, BB):
             print('[mamg] -precond %s: %s' % (precond, note), flush=True)
 
 
-def _solve(A, W, b, precond, idofs, tol, maxiter, monolithic_params=None):
+def _storage_kw(cycle_storage, precond):
+    """-cycle_storage as the factories' keyword; nothing for the default, so
+    an existing command line builds exactly what it built before"""
+    if cycle_storage == 'f64':
+        return {}
+    if precond in ('diag', 'metric_hazmath'):
+        raise ValueError('-cycle_storage f32 needs an AMG preconditioner built by a factory, not -precond %s' % precond)
+    return dict(cycle_storage=cycle_storage)
+
+
+def _solve(A, W, b, precond, idofs, tol, maxiter, monolithic_params=None, cycle_storage='f64'):
     """setup + CG, timed together (the reference's timeKSP)."""
     then = time.time()
     Asp = A.scipy() if hasattr(A, 'scipy') else A
     nf = 2 if W[0] == W[1] else 1
+    skw = _storage_kw(cycle_storage, precond)
     if precond in ('metric_mono', 'hazmath_HEM'):   # hazmath_HEM: the same factory, parameters_metric
         BB = get_hazmath_metric_precond_mono(A, W, parameters=monolithic_params, interface_dofs=idofs,
-                                             num_functions=nf)
+                                             num_functions=nf, **skw)
         Aop = A                              # same object: device-resident PCG
     elif precond in ('hazmath', 'hazmath_Schwarz'):   # AMGhaz: no W, no seeds (src/utils.py:40)
-        BB = get_hazmath_amg_precond(Asp, W, parameters=monolithic_params, pointwise=True)
+        BB = get_hazmath_amg_precond(Asp, W, parameters=monolithic_params, pointwise=True, **skw)
         _print_substitutions(precond, BB)
         Aop = BB._Aop
     elif precond == 'metric':
         BB = get_hazmath_metric_precond(Asp, W, parameters=monolithic_params, interface_dofs=idofs,
-                                        num_functions=nf)
+                                        num_functions=nf, **skw)
         Aop = BB.Aop
     elif precond == 'amg':
-        BB = get_hazmath_amg_precond(Asp, W, parameters=monolithic_params)
+        BB = get_hazmath_amg_precond(Asp, W, parameters=monolithic_params, **skw)
         Aop = BB._Aop
     elif precond == 'diag':
         BB = get_block_diag_precond(Asp, W)
@@ -153,6 +164,8 @@ def bidomain_parser(dim):
     ap.add_argument('-rhs', type=str, default='mms', choices=('mms', 'random'))
     ap.add_argument('-profile', type=str, default='reference', choices=('reference', 'mi355x'),
                     help="AMG parameters: the reference driver's dicts, or the GPU profile")
+    ap.add_argument('-cycle_storage', type=str, default='f64', choices=('f64', 'f32'),
+                    help='storage of the operators the cycle streams (f32: MetricAMG.set_cycle_storage)')
     return ap
 
 
@@ -175,10 +188,12 @@ def bidomain(argv, dim):
         else:
             b = problems.seeded_rhs(s.N)
         if args.precond == 'metric_hazmath':     # the whole solve in the library (src/bidomain_2d.py:181-186)
+            _storage_kw(args.cycle_storage, args.precond)   # f32: refused, the solve builds its own handle
             niters, xb, dt = solve_haznics(s, b, s.W, interface_dofs=s.idofs, parameters=prm)
             x, cond, r = np.concatenate(xb), -1, 0
         else:
-            x, niters, cond, dt, r, _ = _solve(s, s.W, b, args.precond, s.idofs, 1e-8, 500, prm)
+            x, niters, cond, dt, r, _ = _solve(s, s.W, b, args.precond, s.idofs, 1e-8, 500, prm,
+                                               cycle_storage=args.cycle_storage)
         h = np.sqrt(dim) / n            # dolfin hmin: the simplices' longest edge
         row = (s.N, niters, cond, dt, r, h)
         rows.append(row)
@@ -211,6 +226,8 @@ def emi(argv, dim):
     ap.add_argument('-rhs', type=str, default='mms', choices=('mms', 'random'))
     ap.add_argument('-profile', type=str, default='reference', choices=('reference', 'mi355x'),
                     help="AMG parameters: the reference's default dict (src/utils.py:60-82), or the GPU profile")
+    ap.add_argument('-cycle_storage', type=str, default='f64', choices=('f64', 'f32'),
+                    help='storage of the operators the cycle streams (f32: MetricAMG.set_cycle_storage)')
     args, _ = ap.parse_known_args(argv)
     prm = _profile_params(args.profile, args.precond)
     rdir = os.path.join(args.results, 'emi_%dd' % dim)
@@ -232,7 +249,7 @@ def emi(argv, dim):
             BB = get_block_diag_precond(s.blocks, s.W)
         else:
             BB = get_hazmath_metric_precond(s.blocks, s.W, parameters=prm, interface_dofs=s.idofs,
-                                            num_functions=2)
+                                            num_functions=2, **_storage_kw(args.cycle_storage, args.precond))
         solver = ConjGrad(s, precond=BB, tolerance=1e-10, maxiter=500)   # src/emi_3d.py:143
         x = solver * b
         dt = time.time() - then
