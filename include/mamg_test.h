@@ -44,6 +44,32 @@ int mamg_dist_options(const mamg_dhandle* h, char* buf, int64_t cap);
 int mamg_sharded_galerkin_check(const mamg_csr* A, const mamg_csr* P, const mamg_csr* Ac, int nranks, int device,
                                 int64_t* res6);
 
+/* Which plan the coarse tail's planner took for a handle (DESIGN.md section
+ * 4.2): the index-th cached tail program (one per (b, x) entry of tail_level:
+ * a V-cycle has one, a W-cycle's second visit a second one).  Programs are
+ * planned at the first apply.  Writes up to cap values and returns how many
+ * the program has (call again with a larger cap if it exceeds cap), 0 when no
+ * program index exists (nothing planned yet, the tail is off, or it was
+ * refused: info[0], info[1] and info[11] are still written), MAMG_ERR_ARG for
+ * a bad argument.  info[]:
+ *   0 cached programs        1 tail_level (0: no tail)
+ *   2 ops of the program     3 dynamic LDS bytes of its launch
+ *   4 xl: every gathered x in LDS (1 / 0)
+ *   5 res: register-resident rows (1 / 0)
+ *   6 prog_lds: LDS byte offset of the op descriptors, -1: read from global
+ *   7 resident rows          8 overflow blocks of rows longer than 12 (nov)
+ *   9 vector operands tagged LDS     10 vector operands in global memory
+ *     (of every op but the copies in and out and the row load)
+ *  11 the planner refused the last attempt (an op the tail cannot express;
+ *     the level then runs as launches)
+ *  12 dense solves (T_GEMV ops)
+ *  13 SpMV / GS ops run from resident rows   14 ... run from global arrays
+ *  15 largest lane count of the ops in 14
+ *  16 a residency plan was made and discarded (its LDS region did not fit next
+ *     to the vectors; values 5, 7, 8 then describe the replanned program)
+ *  17.. per dense solve: n, 1 if its matrix is in the LDS region (else global) */
+int mamg_tail_info(const mamg_handle* h, int index, int64_t* info, int cap);
+
 #ifdef __cplusplus
 }
 #endif

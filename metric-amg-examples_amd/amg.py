@@ -287,6 +287,32 @@ class MetricAMG:
         _lib.check(min(f, 0))
         return {'A': bool(f & 1), 'KP': bool(f & 2), 'R': bool(f & 4)}
 
+    def tail_info(self) -> dict:
+        """Which plan the coarse tail took (mamg_tail_info, a test hook):
+        ``tail_level``, ``refused`` and one dict per cached program under
+        ``programs`` (empty before the first apply, with the tail off, or
+        when the planner refused the level)."""
+        keys = ('ops', 'lds_bytes', 'xl', 'res', 'prog_lds', 'resident_rows', 'nov', 'vec_lds', 'vec_global',
+                'refused', 'gemvs', 'ops_res', 'ops_global', 'max_vl', 'replanned')
+        out = {'programs': []}
+        index = 0
+        while True:
+            cap = 64
+            v = (C.c_int64 * cap)()
+            n = self._L.mamg_tail_info(self._h, index, v, cap)
+            if n > cap:
+                cap = n
+                v = (C.c_int64 * cap)()
+                n = self._L.mamg_tail_info(self._h, index, v, cap)
+            _lib.check(min(n, 0))
+            out['tail_level'], out['refused'] = int(v[1]), bool(v[11])
+            if n == 0:
+                return out
+            p = {k: int(v[2 + i]) for i, k in enumerate(keys) if k != 'refused'}
+            p['gemv'] = [(int(v[17 + 2 * i]), 'lds' if v[18 + 2 * i] else 'global') for i in range(p.pop('gemvs'))]
+            out['programs'].append(p)
+            index += 1
+
     @property
     def kregion(self) -> dict:
         """Placement of the level-0 K values chosen at upload: K ms per

@@ -1001,6 +1001,16 @@ int mamg_level_storage(const mamg_handle* h, int level) {
   return mamg::dev_level_storage(h->d, level);
 }
 
+int mamg_tail_info(const mamg_handle* h, int index, int64_t* info, int cap) {
+  GUARD_BEGIN
+  if (!h || index < 0 || cap < 0 || (cap > 0 && !info)) {
+    set_error("mamg_tail_info: bad handle, index or buffer");
+    return MAMG_ERR_ARG;
+  }
+  return mamg::dev_tail_info(h->d, index, info, cap);
+  GUARD_END
+}
+
 int mamg_handle_options(const mamg_handle* h, char* buf, int64_t cap) {
   GUARD_BEGIN
   return write_options(h ? mamg::dev_switches(h->d) : mamg::read_switches(), buf, cap);

@@ -42,6 +42,8 @@ int dev_level_format(const DeviceHandle* h, int level);
 // fp32 storage of the operators the cycle streams (mamg.h mamg_set_cycle_storage)
 int dev_set_cycle_storage(DeviceHandle* h, int storage, std::string* err);
 int dev_level_storage(const DeviceHandle* h, int level);
+// the coarse tail's plan (mamg_test.h mamg_tail_info)
+int dev_tail_info(const DeviceHandle* h, int index, int64_t* info, int cap);
 mamg_params dev_params(const DeviceHandle* h);
 // the switches the handle was built with (dev_upload's sw, dev_from_ghier's G->sw)
 const Switches& dev_switches(const DeviceHandle* h);

@@ -3176,8 +3176,12 @@ struct DeviceHandle {
   int tail_level = 0;
   std::vector<double> kregion_ms;  // select_k_region: K ms per candidate region, the one kept
   int kregion_best = -1;
-  struct TailProg { const double* b; double* x; TOp* prog; int n; double bytes; int64_t lds; bool xl; int prog_lds; bool res; };
+  struct TailProg {
+    const double* b; double* x; TOp* prog; int n; double bytes; int64_t lds; bool xl; int prog_lds; bool res;
+    std::vector<int64_t> info;     // what the planner decided (dev_tail_info; mamg_test.h mamg_tail_info)
+  };
   mutable std::vector<TailProg> tails;
+  mutable bool tail_refused = false;   // the last plan attempt met an op the tail cannot express (to_tail)
   double* hr = nullptr;            // host-apply staging (device)
   double* hz = nullptr;
   double *cr = nullptr, *cz = nullptr, *cd = nullptr, *cq = nullptr;  // PCG
@@ -5439,6 +5443,9 @@ void cycle_ops_bsr(const DeviceHandle* h, int l, const double* b, int64_t bs, do
                    int64_t os, std::vector<Op>* ops, bool tail_ok = true, bool x1_ready = false);
 
 static_assert(sizeof(TOp) % 8 == 0, "TOp is copied into LDS as 8-byte words");
+// mamg_tail_info's values (include/mamg_test.h): the header, then (n, matrix in LDS) per T_GEMV
+enum TailInfo { TI_PROGS = 0, TI_LEVEL, TI_OPS, TI_LDS, TI_XL, TI_RES, TI_PROG_LDS, TI_ROWS, TI_NOV, TI_VEC_LDS,
+                TI_VEC_GLOBAL, TI_REFUSED, TI_GEMVS, TI_OPS_RES, TI_OPS_BSR, TI_MAX_VL, TI_REPLANNED, TAIL_INFO_HEAD };
 constexpr int64_t TAIL_LDS_MAX = 160 * 1024 - 1024;   // gfx950: 160 KB per workgroup, minus the static arrays
 
 // LDS residency of a coarse-tail program (see T_COPY): every work vector of
@@ -5553,8 +5560,10 @@ int64_t tail_lds_plan(const DeviceHandle* h, int l, std::vector<TOp>* prog, int6
 // (byte offset in img + 1) until the caller sets device pointers, its r0 / r1
 // the LDS region's place once the LDS plan is known.  Returns false when
 // nothing is resident.
-bool tail_res_plan(const DeviceHandle* h, int l, std::vector<TOp>* prog, std::vector<char>* img, int64_t* nov) {
+bool tail_res_plan(const DeviceHandle* h, int l, std::vector<TOp>* prog, std::vector<char>* img, int64_t* nov,
+                   int* rrows) {
   *nov = 0;
+  *rrows = 0;
   if (!h->sw.tail_res) return false;
   constexpr int T = TAIL_THREADS;
   std::vector<dv4> iv((size_t)RES_RB * T, dv4{0.0, 0.0, 0.0, 0.0});
@@ -5632,6 +5641,7 @@ bool tail_res_plan(const DeviceHandle* h, int l, std::vector<TOp>* prog, std::ve
   }
   if (rbase == 0) return false;
   *nov = (int64_t)ovv.size();
+  *rrows = rbase;
   // the image: values, columns, header, then the LDS region's bytes (block
   // inverses, overflow values, overflow columns padded to 16 B)
   auto put = [&](const void* p, size_t bytes) {
@@ -5692,20 +5702,20 @@ bool tail_ops(const DeviceHandle* h, int l, const double* b, double* xout, std::
     std::vector<TOp> prog(sub.size());
     double bytes = 0.0;
     for (size_t k = 0; k < sub.size(); ++k) {
-      if (!to_tail(sub[k], h->sw.tail_vl, &prog[k])) return false;
+      if (!to_tail(sub[k], h->sw.tail_vl, &prog[k])) { h->tail_refused = true; return false; }
       bytes += sub[k].bytes;
     }
+    h->tail_refused = false;
+    bool replanned = false;   // a residency plan was made, did not fit the LDS and was discarded
     std::vector<char> img;
     int64_t nov = 0;
+    int rrows = 0;
     const std::vector<TOp> plain = prog;
-    bool res = tail_res_plan(h, l, &prog, &img, &nov);
+    bool res = tail_res_plan(h, l, &prog, &img, &nov, &rrows);
     int64_t region = 0;   // the resident rows' LDS region, kept free of vectors
     for (const TOp& t : prog)
       if (t.kind == T_RLOAD) region = t.n;
     int64_t lds = tail_lds_plan(h, l, &prog, region + 16);
-    bool xl = lds > 0;   // every gathered x in LDS: the ds_read variant of the kernel
-    for (const TOp& t : prog)
-      if ((t.kind == T_BSR || t.kind == T_GS) && !((uintptr_t)t.x & 1)) xl = false;
     // the program itself into the LDS after the vectors when it fits
     // (TAIL_LDS_MAX); the dynamic LDS then covers both
     int prog_lds = -1;
@@ -5736,6 +5746,9 @@ bool tail_ops(const DeviceHandle* h, int l, const double* b, double* xout, std::
         lds = off + need;
       } else {
         res = false;
+        replanned = true;
+        nov = 0;
+        rrows = 0;
         img.clear();
         prog = plain;
         lds = tail_lds_plan(h, l, &prog);
@@ -5748,6 +5761,29 @@ bool tail_ops(const DeviceHandle* h, int l, const double* b, double* xout, std::
             lds = o2 + pbytes;
           }
         }
+      }
+    }
+    // every gathered x in LDS: the ds_read variant of the kernel (read off
+    // the final program: a replan above may have placed the vectors anew)
+    bool xl = lds > 0;
+    for (const TOp& t : prog)
+      if ((t.kind == T_BSR || t.kind == T_GS) && !((uintptr_t)t.x & 1)) xl = false;
+    // the plan as the tests read it (before the T_RLOAD's fields become device pointers)
+    std::vector<int64_t> info(TAIL_INFO_HEAD, 0);
+    info[TI_OPS] = (int64_t)prog.size(); info[TI_LDS] = lds; info[TI_XL] = xl ? 1 : 0; info[TI_RES] = res ? 1 : 0;
+    info[TI_PROG_LDS] = prog_lds; info[TI_ROWS] = rrows; info[TI_NOV] = nov; info[TI_REPLANNED] = replanned ? 1 : 0;
+    for (const TOp& t : prog) {
+      if (t.kind != T_RLOAD && t.kind != T_COPY)   // a copy in or out is one of each by construction
+        for (const double* v : {t.x, t.y, t.b, (const double*)t.out, (const double*)t.part})
+          if (v) ++info[((uintptr_t)v & 1) ? TI_VEC_LDS : TI_VEC_GLOBAL];
+      if (t.kind == T_BSR || t.kind == T_GS) {
+        ++info[t.res ? TI_OPS_RES : TI_OPS_BSR];
+        if (!t.res) info[TI_MAX_VL] = std::max<int64_t>(info[TI_MAX_VL], t.vl);
+      }
+      if (t.kind == T_GEMV) {
+        ++info[TI_GEMVS];
+        info.push_back(t.n);
+        info.push_back(((uintptr_t)t.w & 1) ? 1 : 0);
       }
     }
     void* d = nullptr;
@@ -5766,7 +5802,7 @@ bool tail_ops(const DeviceHandle* h, int l, const double* b, double* xout, std::
       (void)raw_free(d);
       return false;
     }
-    h->tails.push_back({b, xout, (TOp*)d, (int)prog.size(), bytes, lds, xl, prog_lds, res});
+    h->tails.push_back({b, xout, (TOp*)d, (int)prog.size(), bytes, lds, xl, prog_lds, res, std::move(info)});
     tp = &h->tails.back();
   }
   Op o;
@@ -7043,6 +7079,18 @@ void release_owned(DeviceHandle* h, void* old) {
 }  // namespace
 
 int dev_level_storage(const DeviceHandle* h, int level) { return h->L[level].storage; }
+
+int dev_tail_info(const DeviceHandle* h, int index, int64_t* info, int cap) {
+  std::lock_guard<std::recursive_mutex> lock(capture_mutex());
+  const int np = (int)h->tails.size();
+  std::vector<int64_t> v(TAIL_INFO_HEAD, 0);
+  if (index < np) v = h->tails[index].info;
+  v[TI_PROGS] = np;
+  v[TI_LEVEL] = h->tail_level;
+  v[TI_REFUSED] = h->tail_refused ? 1 : 0;
+  for (int i = 0; i < cap && i < (int)v.size(); ++i) info[i] = v[i];
+  return index < np ? (int)v.size() : 0;
+}
 
 int dev_set_cycle_storage(DeviceHandle* h, int storage, std::string* err) {
   std::lock_guard<std::recursive_mutex> lock(capture_mutex());

@@ -43,14 +43,19 @@ def round32(M):
 class StorageRef:
     """h: the oracle's Hierarchy (Jacobi family or POLY, node-block smoothers).
     masks: one int per level (missing levels and the coarsest: 0), or one int
-    for every level.  kform: one bool per level, or one bool for every level."""
+    for every level.  kform: one bool per level, or one bool for every level.
+    levels: the levels to narrow (None: every level masks names); the others
+    keep their fp64 operators whatever masks says -- a handle with a coarse
+    tail narrows the launch path's levels only."""
 
-    def __init__(self, h, masks=0, kform=True):
+    def __init__(self, h, masks=0, kform=True, levels=None):
         self.params = h.params
         self.levels = h.levels
         n = len(h.levels)
         masks = [masks] * n if np.isscalar(masks) else list(masks) + [0] * (n - len(masks))
         kform = [kform] * n if isinstance(kform, (bool, np.bool_)) else list(kform) + [False] * (n - len(kform))
+        if levels is not None:
+            masks = [m if l in levels else 0 for l, m in enumerate(masks)]
         self.masks, self.kform = masks, kform
         self.A, self.R, self.P, self.K = [], [], [], []
         for l, lev in enumerate(h.levels):

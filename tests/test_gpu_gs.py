@@ -129,7 +129,7 @@ def test_sgs_symmetric_and_deterministic(lib_built):
     (3, 16, 1e6, dict(smoother='SGS')),
 ])
 def test_coarse_tail_equals_launches(lib_built, monkeypatch, dim, n, g, kw):
-    """The coarse tail (one 1024-thread workgroup runs the whole cycle below
+    """The coarse tail (one 512-thread workgroup runs the whole cycle below
     tail_level, device.hip tail_kernel) equals the launch-by-launch cycle up
     to FMA contraction (1e-13) and the oracle (1e-10): SGS colour sweeps,
     coarse scaling, W-cycle second visits, the dense coarsest solve."""

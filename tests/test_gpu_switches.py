@@ -39,8 +39,9 @@ def test_tail_switches_snapshot_at_setup_not_first_apply(lib_built, n):
     (tail_res_plan, tail_lds_plan, the program's place): it takes the switches
     of the handle's setup, not those set when the apply comes.  Each apply is
     bitwise that of a handle built and applied entirely under its settings
-    (test_gpu_gs.py::test_coarse_tail_equals_launches compares the variants
-    with one another)."""
+    (this test compares no variant with another or with a reference:
+    tests/test_gpu_tail.py runs every tail switch against the oracle and the
+    launch path and asserts the plan each one selects)."""
     M = _M()
     s = M.problems.bidomain(3, n, 1e6)
     A = s.scipy()
