@@ -21,6 +21,15 @@ checks the two virtual applies bitwise.
 With MAMG_DIST_TEST=dry it instead times each rank's cycle with the exchanges
 skipped: the compute part of the P-GPU apply (RCCL latency not included),
 eager and as hipGraph replays.
+
+--cycle-storage f32 builds a second set of rank
+handles of the same hierarchy, narrows it (set_cycle_storage('f32')) and times
+the two sets alternately, round by round, in this process: under
+MAMG_DIST_TEST=dry each rank's compute-only ms per apply with the level-0
+residual, K and restriction classes; otherwise the assembled virtual apply
+(one lockstep graph-free run of all ranks), the virtual device PCG's
+iterations and time, and the distance between the two applies.  One JSON
+line per measurement, then the summary line.
 """
 import argparse
 import json
@@ -50,6 +59,9 @@ def main():
                     help='mi355x: the GPU profile (default); schwarz: the reference preset '
                          'parameters_metric_schwarz verbatim (node patches on level 0); patch: '
                          'parameters_metric_mi355x_patch')
+    ap.add_argument('--cycle-storage', choices=('f64', 'f32'), default='f64',
+                    help='f32: also build a narrowed set of rank handles and time it against the fp64 set')
+    ap.add_argument('--rounds', type=int, default=3, help='alternating rounds of the fp64 / f32 comparison')
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -97,6 +109,9 @@ def main():
     out['rank_rss_estimate_GB'] = round(out['rss_after_A0_GB'] + max(q['rss_growth_GB'] for q in out['per_rank']), 2)
     rs = [torch.as_tensor(h.local_slice(r)).cuda() for h in hs]
     zs = [torch.zeros_like(x) for x in rs]
+    if args.cycle_storage == 'f32':
+        compare_storage(args, M, A, s, prm, hs, rs, zs, out)
+        return
     if os.environ.get('MAMG_DIST_TEST') == 'dry':
         # compute-only time of each rank's cycle (exchanges skipped; the
         # numbers exclude RCCL latency, the results are not used)
@@ -160,6 +175,89 @@ def main():
         zt = _t.zeros_like(rt)
         out['single_gpu_ms_per_apply'] = round(B.time_apply(rt, zt, 3, 0)[0], 3)
     out['rel_diff_vs_single_gpu'] = float(np.linalg.norm(z - z1) / np.linalg.norm(z1))
+    print(json.dumps(out), flush=True)
+
+
+CLASSES = ['L0_resid', 'L0_smooth_spmv', 'L0_smoother', 'L0_restrict', 'L0_prolong',
+           'coarse_levels', 'coarsest_dense', 'misc', 'comm']
+
+
+def compare_storage(args, M, A, s, prm, hs, rs, zs, out):
+    """fp64 rank handles against a narrowed set of the same hierarchy, timed
+    alternately (bench/cycle_storage.py's scheme on N ranks)."""
+    import numpy as np
+    import torch
+    P = args.ranks
+    t0 = time.time()
+    hn = [M.DistMetricAMG(A, s.W, idofs=s.idofs, rank=p, nranks=P, comm_id=None, parameters=prm,
+                          num_functions=2) for p in range(P)]
+    for h in hn:
+        h.set_cycle_storage('f32')
+    torch.cuda.synchronize()
+    out['narrowed_set_s'] = round(time.time() - t0, 2)
+    out['level_storage'] = [[h.level_storage(l) for l in range(h.num_levels)] for h in hn][0]
+    out['apply_bytes'] = {'f64': [h.apply_bytes for h in hs], 'f32': [h.apply_bytes for h in hn]}
+    sets = (('f64', hs), ('f32', hn))
+    zn = [torch.zeros_like(x) for x in rs]
+    med = lambda v: float(np.median(v))
+    if os.environ.get('MAMG_DIST_TEST') == 'dry':
+        # compute-only per rank: total (events around the apply) and the classes (events around every op)
+        tot = {k: [[] for _ in range(P)] for k, _ in sets}
+        cls = {k: [[] for _ in range(P)] for k, _ in sets}
+        for k, H in sets:
+            for p, h in enumerate(H):
+                h.time_apply(rs[p], zs[p], 3, 0)
+        for rnd in range(args.rounds):
+            for k, H in sets:
+                for p, h in enumerate(H):
+                    tot[k][p].append(h.time_apply(rs[p], zs[p], 20, 0)[0])
+                    cls[k][p].append(h.time_apply(rs[p], zs[p], 5, 1)[1])
+        for p in range(P):
+            row = {'rank': p, 'ranks': P, 'N': s.N, 'mode': 'dry'}
+            for k, _ in sets:
+                row[k + '_ms_per_apply'] = round(med(tot[k][p]), 4)
+                c = np.median(np.array(cls[k][p]), axis=0)
+                row[k + '_classes_ms'] = {n: round(float(v), 4) for n, v in zip(CLASSES, c) if v}
+            row['speedup'] = round(row['f64_ms_per_apply'] / row['f32_ms_per_apply'], 3)
+            print(json.dumps(row), flush=True)
+        out['compute_ms_per_apply'] = {k: round(max(med(tot[k][p]) for p in range(P)), 4) for k, _ in sets}
+        print(json.dumps(out), flush=True)
+        return
+    # the assembled virtual apply: all ranks in lockstep, device copies for the exchanges
+    reps = 10
+    wall = {k: [] for k, _ in sets}
+    res = {}
+    for k, H in sets:
+        M.DistMetricAMG.virtual_apply(H, rs, zs if k == 'f64' else zn)
+    torch.cuda.synchronize()
+    for rnd in range(args.rounds):
+        for k, H in sets:
+            z = zs if k == 'f64' else zn
+            t0 = time.time()
+            for _ in range(reps):
+                M.DistMetricAMG.virtual_apply(H, rs, z)
+            torch.cuda.synchronize()
+            wall[k].append((time.time() - t0) / reps * 1e3)
+    num = sum(float(torch.sum((a - b) ** 2)) for a, b in zip(zs, zn))
+    den = sum(float(torch.sum(a ** 2)) for a in zs)
+    out['virtual_apply_ms'] = {k: round(med(wall[k]), 3) for k, _ in sets}
+    out['f32_vs_f64_apply_rel'] = float(np.sqrt(num / den))
+    print(json.dumps({'ranks': P, 'N': s.N, 'mode': 'virtual_apply', 'rounds_ms': wall}), flush=True)
+    # the virtual device PCG (A d on the fp64 A_loc of either set)
+    pcg = {k: [] for k, _ in sets}
+    for rnd in range(args.rounds):
+        for k, H in sets:
+            cg = M.DistConjGrad.for_handles(list(H), device=True, tolerance=1e-8, maxiter=500)
+            torch.cuda.synchronize()
+            t0 = time.time()
+            xs = cg.solve([x.clone() for x in rs])
+            torch.cuda.synchronize()
+            pcg[k].append(time.time() - t0)
+            res[k] = (len(cg.residuals) - 1, xs)
+    num = sum(float(torch.sum((a - b) ** 2)) for a, b in zip(res['f64'][1], res['f32'][1]))
+    den = sum(float(torch.sum(a ** 2)) for a in res['f64'][1])
+    out['virtual_pcg'] = {k: {'iterations': res[k][0], 'seconds': round(med(pcg[k]), 3)} for k, _ in sets}
+    out['f32_vs_f64_solution_rel'] = float(np.sqrt(num / den))
     print(json.dumps(out), flush=True)
 
 

@@ -579,6 +579,40 @@ int mamg_set_cycle_storage(mamg_handle* h, int storage);
 /* bit 0: A_l as the cycle reads it, bit 1: K_l / P_l, bit 2: R_l stored fp32; 0 before narrowing */
 int mamg_level_storage(const mamg_handle* h, int level);
 
+/* The same on a rank handle, after its setup.  The
+ * call needs no communication and every rank of a communicator (every
+ * virtual rank of a list) MUST make the same call: ranks cannot check each
+ * other without an exchange, and a narrowed rank next to an fp64 one applies
+ * an operator that is neither.  Narrowed, on every level above the coarsest,
+ * distributed or replicated: A_loc (on level 0 both value arrays of the
+ * half-symmetric form, the owned part and the ghost part), K_loc -- formed in
+ * fp64, then rounded -- or plain P_loc under post_fusion 0, and the partial
+ * restriction Rp_loc.  Kept fp64: the smoother blocks W / Wk, the coarsest
+ * inverse, every vector, the halo, send and receive buffers, a merged
+ * [P_loc | AP_loc] (MAMG_POST_K=0: bits 1 and 4 only), and the Krylov
+ * operator -- mamg_dist_spmv_device, mamg_dist_virtual_spmv and the A d
+ * product of mamg_dist_pcg_device / mamg_dist_virtual_pcg keep reading the
+ * fp64 level-0 A_loc, whose index arrays the fp32 copy shares.  One apply of
+ * N narrowed ranks is the narrowed one-GPU apply up to summation order.
+ * Returns as mamg_set_cycle_storage: MAMG_ERR_UNSUPPORTED, the handle
+ * untouched and the reason named, for scalar (CSR, dofs_per_node 1) rank
+ * handles, GS / SGS, SCHWARZ_PATCHES and SCHWARZ_RINGS rank handles, a finite
+ * value whose fp32 rounding is not finite (every array is checked before any
+ * is converted) and MAMG_STORE_F64 on a narrowed handle; MAMG_OK for
+ * MAMG_STORE_F64 on an un-narrowed handle and a second MAMG_STORE_F32;
+ * MAMG_ERR_ARG for a NULL handle or another storage value.  The call waits
+ * for the handle's queued work, drops its cached apply graphs and PCG plans
+ * and recounts mamg_dist_apply_bytes at 4 bytes per narrowed value.
+ * mamg_dist_virtual_apply, _apply_graph, _spmv and _virtual_pcg return
+ * MAMG_ERR_ARG when the handles of one list disagree in storage. */
+int mamg_dist_set_cycle_storage(mamg_dhandle* h, int storage);
+/* mamg_level_storage's bits for the rank-local operators of `level` */
+int mamg_dist_level_storage(const mamg_dhandle* h, int level);
+/* levels of the rank's hierarchy, and mamg_level_format's bits for the
+ * rank-local operators of one (0 on a scalar rank handle) */
+int mamg_dist_num_levels(const mamg_dhandle* h);
+int mamg_dist_level_format(const mamg_dhandle* h, int level);
+
 /* z = B r : one preconditioner application (`maxit` cycles from x0 = 0).
  * Host pointers (copies in/out, synchronous). */
 int mamg_apply(mamg_handle* h, const double* r, double* z);

@@ -149,6 +149,10 @@ SIGNATURES = {
     'mamg_apply_bytes': (C.c_int, [VP, P_F64]),
     'mamg_set_cycle_storage': (C.c_int, [VP, C.c_int]),
     'mamg_level_storage': (C.c_int, [VP, C.c_int]),
+    'mamg_dist_set_cycle_storage': (C.c_int, [VP, C.c_int]),
+    'mamg_dist_level_storage': (C.c_int, [VP, C.c_int]),
+    'mamg_dist_num_levels': (C.c_int, [VP]),
+    'mamg_dist_level_format': (C.c_int, [VP, C.c_int]),
     'mamg_tail_info': (C.c_int, [VP, C.c_int, P_I64, C.c_int]),
     'mamg_apply': (C.c_int, [VP, P_F64, P_F64]),
     'mamg_apply_device': (C.c_int, [VP, VP, VP, VP]),

@@ -630,7 +630,12 @@ class DistMetricAMG:
     partitions the rows themselves: ``dofs_per_node`` is 1, ``nv`` the row count and the local
     slice the plain r[o0:o1]; it takes a host matrix only.  comm_id: bytes from
     ``DistMetricAMG.unique_id()`` on rank 0, broadcast to all ranks; None
-    builds a virtual (single-GPU, no RCCL) rank for tests."""
+    builds a virtual (single-GPU, no RCCL) rank for tests.
+
+    fp32 storage of the cycle's operators is the call after setup,
+    ``set_cycle_storage('f32')``, made by every rank.  The constructor keyword
+    ``cycle_storage`` takes 'f64' only here and raises for 'f32' (on
+    ``MetricAMG`` the keyword is only shorthand for that call)."""
 
     def __init__(self, A, W=None, idofs=None, parameters=None, rank=0, nranks=1, comm_id=None,
                  rep_nodes=32768, exchange=None, cycle_storage='f64', **overrides):
@@ -739,6 +744,38 @@ class DistMetricAMG:
         b = C.c_double()
         _lib.check(self._L.mamg_dist_apply_bytes(self._h, C.byref(b)))
         return b.value
+
+    @property
+    def num_levels(self) -> int:
+        return self._L.mamg_dist_num_levels(self._h)
+
+    def level_format(self, level: int) -> dict:
+        """Device storage of this rank's operators on level ``level``
+        (mamg_dist_level_format: ``MetricAMG.level_format``'s keys)."""
+        f = self._L.mamg_dist_level_format(self._h, int(level))
+        _lib.check(min(f, 0))
+        return {'sell': bool(f & 1), 'sym': bool(f & 2), 'post_fused': bool(f & 4),
+                'post_k': bool(f & 8), 'post_sell': bool(f & 16), 'half': bool(f & 32),
+                'bands': bool(f & 64), 'patches': bool(f & 128), 'gs': bool(f & 256),
+                'rings': bool(f & 512), 'r_bands': bool(f & 1024), 'k_col16': bool(f & 2048)}
+
+    def set_cycle_storage(self, storage):
+        """'f32': narrow the rank-local operators the cycle streams to fp32
+        storage (mamg_dist_set_cycle_storage; one way, a no-op when already
+        narrowed).  No communication: every rank of the communicator (every
+        virtual rank of a list) must make the same call.  'f64' is accepted
+        on a handle that was never narrowed.  Vectors, sums, the smoother
+        blocks, the exchange buffers and the Krylov operator (``spmv_device``,
+        the device PCG's A d) stay fp64."""
+        code = _storage_code(storage)                    # a bad value before the library is touched
+        _lib.check(self._L.mamg_dist_set_cycle_storage(self._h, code))
+
+    def level_storage(self, level: int) -> dict:
+        """Which of this rank's operators on level ``level`` are stored fp32
+        (mamg_dist_level_storage): A as the cycle reads it, K / P, R."""
+        f = self._L.mamg_dist_level_storage(self._h, int(level))
+        _lib.check(min(f, 0))
+        return {'A': bool(f & 1), 'KP': bool(f & 2), 'R': bool(f & 4)}
 
     @property
     def apply_launches(self):

@@ -650,6 +650,41 @@ int mamg_dist_apply_bytes(const mamg_dhandle* h, double* bytes) {
   return MAMG_OK;
 }
 
+int mamg_dist_set_cycle_storage(mamg_dhandle* h, int storage) {
+  GUARD_BEGIN
+  if (!h) { set_error("null handle"); return MAMG_ERR_ARG; }
+  if (storage != MAMG_STORE_F64 && storage != MAMG_STORE_F32) {
+    set_error("mamg_dist_set_cycle_storage: storage must be MAMG_STORE_F64 or MAMG_STORE_F32");
+    return MAMG_ERR_ARG;
+  }
+  std::string err;
+  const int rc = mamg::dist_set_cycle_storage(h->d, storage, &err);
+  if (rc) set_error(err);
+  return rc;
+  GUARD_END
+}
+
+int mamg_dist_level_storage(const mamg_dhandle* h, int level) {
+  if (!h || level < 0 || level >= mamg::dist_num_levels(h->d)) {
+    set_error("mamg_dist_level_storage: bad handle or level");
+    return MAMG_ERR_ARG;
+  }
+  return mamg::dist_level_storage(h->d, level);
+}
+
+int mamg_dist_num_levels(const mamg_dhandle* h) {
+  if (!h) { set_error("null handle"); return MAMG_ERR_ARG; }
+  return mamg::dist_num_levels(h->d);
+}
+
+int mamg_dist_level_format(const mamg_dhandle* h, int level) {
+  if (!h || level < 0 || level >= mamg::dist_num_levels(h->d)) {
+    set_error("mamg_dist_level_format: bad handle or level");
+    return MAMG_ERR_ARG;
+  }
+  return mamg::dist_level_format(h->d, level);
+}
+
 int mamg_dist_apply_launches(const mamg_dhandle* h, int64_t counts[5]) {
   if (!h || !counts) { set_error("null argument"); return MAMG_ERR_ARG; }
   mamg::dist_apply_launches(h->d, counts);
@@ -668,9 +703,26 @@ int mamg_dist_graph_prepare(mamg_dhandle* h, const double* d_r, double* d_z) {
   DEV_CALL(mamg::dist_graph_prepare(h->d, d_r, d_z, &err))
 }
 
+namespace {
+// the rank handles of one virtual list run one op list each in lockstep: all
+// narrowed (mamg_dist_set_cycle_storage) or none
+int same_storage(mamg_dhandle** hs, int n, const char* what) {
+  for (int i = 0; i < n; ++i) {
+    if (!hs[i]) { set_error("null handle"); return MAMG_ERR_ARG; }
+    if (mamg::dist_cycle_storage(hs[i]->d) != mamg::dist_cycle_storage(hs[0]->d)) {
+      set_error(std::string(what) + ": the rank handles disagree in cycle storage (every rank makes the same "
+                "mamg_dist_set_cycle_storage call)");
+      return MAMG_ERR_ARG;
+    }
+  }
+  return MAMG_OK;
+}
+}  // namespace
+
 int mamg_dist_virtual_apply_graph(mamg_dhandle** hs, int n, const double** d_r, double** d_z, void* stream) {
   GUARD_BEGIN
   if (!hs || n < 1 || !d_r || !d_z) { set_error("null argument"); return MAMG_ERR_ARG; }
+  if (int src = same_storage(hs, n, "mamg_dist_virtual_apply_graph")) return src;
   std::vector<mamg::DistHandle*> H(n);
   std::vector<const double*> R(d_r, d_r + n);
   std::vector<double*> Z(d_z, d_z + n);
@@ -689,6 +741,7 @@ int mamg_dist_spmv_device(mamg_dhandle* h, const double* d_x, double* d_y, void*
 int mamg_dist_virtual_spmv(mamg_dhandle** hs, int n, const double** d_x, double** d_y, void* stream) {
   GUARD_BEGIN
   if (!hs || n < 1 || !d_x || !d_y) { set_error("null argument"); return MAMG_ERR_ARG; }
+  if (int src = same_storage(hs, n, "mamg_dist_virtual_spmv")) return src;
   std::vector<mamg::DistHandle*> H(n);
   std::vector<const double*> X(d_x, d_x + n);
   std::vector<double*> Y(d_y, d_y + n);
@@ -709,6 +762,7 @@ int mamg_dist_virtual_apply(mamg_dhandle** hs, int n, const double** d_r, double
                             void* stream) {
   GUARD_BEGIN
   if (!hs || n < 1 || !d_r || !d_z) { set_error("null argument"); return MAMG_ERR_ARG; }
+  if (int src = same_storage(hs, n, "mamg_dist_virtual_apply")) return src;
   std::vector<mamg::DistHandle*> H(n);
   std::vector<const double*> R(d_r, d_r + n);
   std::vector<double*> Z(d_z, d_z + n);
@@ -757,6 +811,7 @@ int mamg_dist_virtual_pcg(mamg_dhandle** hs, int n, const double** d_b, double**
   if (!hs || n < 1 || !d_b || !d_x) { set_error("null argument"); return MAMG_ERR_ARG; }
   for (int i = 0; i < n; ++i)
     if (!hs[i]) { set_error("null handle"); return MAMG_ERR_ARG; }
+  if (int src = same_storage(hs, n, "mamg_dist_virtual_pcg")) return src;
   int rc = dist_pcg_args(maxiter, stop_type, residuals, rnorms, alphas, betas, niters);
   if (rc) return rc;
   std::vector<mamg::DistHandle*> H(n);

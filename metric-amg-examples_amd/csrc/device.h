@@ -78,6 +78,14 @@ void dist_range(const DistHandle* h, int64_t* o0, int64_t* o1, int64_t* nv);
 // dofs per node: 2 nodal (BSR2; local vectors field-major), 1 scalar (CSR; plain slices)
 int dist_dofs(const DistHandle* h);
 double dist_apply_bytes(const DistHandle* h);
+int dist_num_levels(const DistHandle* h);
+// mamg_level_format's bits for the rank-local operators of a level
+int dist_level_format(const DistHandle* h, int level);
+// fp32 storage of the operators the rank's cycle streams (mamg.h
+// mamg_dist_set_cycle_storage); dist_cycle_storage: MAMG_STORE_* of the handle
+int dist_set_cycle_storage(DistHandle* h, int storage, std::string* err);
+int dist_level_storage(const DistHandle* h, int level);
+int dist_cycle_storage(const DistHandle* h);
 void dist_apply_launches(const DistHandle* h, int64_t c[5]);
 int dist_apply(DistHandle* h, const double* d_r, double* d_z, void* stream, std::string* err);
 int dist_spmv(DistHandle* h, const double* d_x, double* d_y, void* stream, std::string* err);

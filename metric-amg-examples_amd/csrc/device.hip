@@ -6208,11 +6208,7 @@ void launch_half_x(const Op& o, hipStream_t s) {
 
 template <int TAG, class VT = double>
 void launch_half(const Op& o, hipStream_t s) {
-  const bool gh = o.Mb->ngs > 0;
-  if constexpr (sizeof(VT) == 4) {   // fp32 storage is single-GPU: the ghost-free form only
-    if (o.xfm) launch_half_x<true, false, TAG, VT>(o, s); else launch_half_x<false, false, TAG, VT>(o, s);
-    return;
-  }
+  const bool gh = o.Mb->ngs > 0;   // a rank-local A's ghost part (fp32 storage: gval narrowed with val)
   if (o.xfm) {
     if (gh) launch_half_x<true, true, TAG, VT>(o, s); else launch_half_x<true, false, TAG, VT>(o, s);
   } else {
@@ -7058,6 +7054,9 @@ inline int64_t value_count(const DBsr& M) {
   const int64_t slots = (M.sell || M.half) ? M.nbs : M.nb;
   return slots * ((M.sym || M.half) ? 3 : 4);
 }
+// stored values of a half-symmetric operator's ghost part (gval: the diagonal
+// pairs of its ngs slots, then their off-diagonals)
+inline int64_t ghost_value_count(const DBsr& M) { return (M.half && M.gval) ? 3 * M.ngs : 0; }
 
 struct NarrowJob {
   DBsr* src;        // the operator whose fp64 values are read
@@ -7674,6 +7673,13 @@ struct DDLevel {
   int64_t nv = 0, nloc = 0, ng = 0;
   bool replicated = false, coarsest = false;
   DBsr A, P, R;
+  // fp32 cycle storage (dist_set_cycle_storage), level 0 only: A_loc as the
+  // cycle reads it -- A's layout with fp32 copies of val and, half-symmetric,
+  // gval (Ac.f32), the index arrays shared; A itself stays fp64 for the Krylov
+  // operator (dspmv_ops).  On the other narrowed levels A's values are
+  // replaced in place.
+  DBsr Ac;
+  int storage = 0;         // mamg_dist_level_storage bits: 1 A, 2 K / P, 4 R stored fp32
   // scalar (CSR) level: A_loc, P_loc, Rp_loc, on level 0 with seed blocks the
   // owned rows of WB (else the winv slice); POLY: the step smoothers w_k WB
   // (sharing WB's pattern) or w_k winv; vectors hold nloc + ng doubles
@@ -7739,6 +7745,9 @@ struct DOp {
   double bytes = 0.0;
   int cls = 0;
 };
+
+// A_loc as the cycle reads it: level 0's fp32 copy once the rank is narrowed
+inline const DBsr& dcyc_A(const DDLevel& D) { return D.Ac.f32 ? D.Ac : D.A; }
 
 }  // namespace
 
@@ -8326,12 +8335,12 @@ void dcycle_ops(const DistHandle* h, int l, const double* b, int64_t bs, double*
     ops->push_back(wrap(o));
   }
   for (int s = 1; s < npre; ++s) {   // further pre steps: halo of X, then x + w_s W (b - A x)
-    const Op bj = bsr_op(D.A, EPI_BJAC, clsS, tagA, X, 0, X, b, bs, wk(s, true), X2, 0);
+    const Op bj = bsr_op(dcyc_A(D), EPI_BJAC, clsS, tagA, X, 0, X, b, bs, wk(s, true), X2, 0);
     if (D.replicated) ops->push_back(wrap(bj)); else halo_residual(h, l, X, bj, ops);
     std::swap(X, X2);
   }
   {
-    const Op res = bsr_op(D.A, EPI_RESID, l0 ? C_L0_RESID : C_COARSE, tagA, X, 0, nullptr, b, bs, nullptr, D.r, 0);
+    const Op res = bsr_op(dcyc_A(D), EPI_RESID, l0 ? C_L0_RESID : C_COARSE, tagA, X, 0, nullptr, b, bs, nullptr, D.r, 0);
     if (D.replicated) {
       ops->push_back(wrap(res));
     } else {
@@ -8363,7 +8372,7 @@ void dcycle_ops(const DistHandle* h, int l, const double* b, int64_t bs, double*
   }
   for (int s = s0; s < npost; ++s) {   // halo of the iterate, then x + w W (b - A x)
     const bool last = s == npost - 1;
-    const Op bj = bsr_op(D.A, EPI_BJAC, clsS, tagA, X, 0, X, b, bs, wk(s, false), last ? xout : X2,
+    const Op bj = bsr_op(dcyc_A(D), EPI_BJAC, clsS, tagA, X, 0, X, b, bs, wk(s, false), last ? xout : X2,
                          last ? os : 0);
     if (D.replicated) ops->push_back(wrap(bj)); else halo_residual(h, l, X, bj, ops);
     std::swap(X, X2);
@@ -9664,6 +9673,149 @@ void dist_range(const DistHandle* h, int64_t* o0, int64_t* o1, int64_t* nv) {
 }
 
 double dist_apply_bytes(const DistHandle* h) { return h->apply_bytes; }
+
+int dist_num_levels(const DistHandle* h) { return (int)h->L.size(); }
+
+// mamg_level_format's bits for the rank-local operators of a nodal level (0
+// on a scalar handle: its levels are plain CSR)
+int dist_level_format(const DistHandle* h, int level) {
+  const DDLevel& D = h->L[level];
+  if (h->w != 2) return 0;
+  return (D.A.sell ? MAMG_FMT_SELL : 0) | (D.A.sym ? MAMG_FMT_SYM : 0) | (D.A.half ? MAMG_FMT_HALF : 0) |
+         (D.PA.nr > 0 || D.K.nr > 0 ? MAMG_FMT_POST_FUSED : 0) | (D.K.nr > 0 ? MAMG_FMT_POST_K : 0) |
+         (D.K.sell ? MAMG_FMT_POST_SELL : 0) | (D.A.nsched > 0 || D.A.nsched_r > 0 ? MAMG_FMT_BANDS : 0) |
+         (D.patches ? MAMG_FMT_PATCHES : 0) | (D.gcs.size() > 1 ? MAMG_FMT_GS : 0) |
+         (D.rings ? MAMG_FMT_RINGS : 0) | (D.R.nrsched > 0 ? MAMG_FMT_R_BANDS : 0) |
+         (D.K.col16 ? MAMG_FMT_K_COL16 : 0);
+}
+
+// ---------------------------------------------------------------------------
+// fp32 storage of the operators a rank's cycle streams
+// (mamg_dist_set_cycle_storage): dev_set_cycle_storage
+// on the rank-local operators.  A_loc (level 0: both value arrays of the
+// half-symmetric form, owned part and ghost part), K_loc or plain P_loc and
+// the partial restriction of every level above the coarsest become fp32
+// copies in the same layout; W / Wk, the coarsest inverse, the merged
+// [P_loc | AP_loc], every vector and every exchange buffer stay fp64, and so
+// does level 0's A_loc itself (dspmv_ops: the Krylov operator), whose index
+// arrays the fp32 copy Ac shares.  No communication: every rank calls it.
+// ---------------------------------------------------------------------------
+int dist_level_storage(const DistHandle* h, int level) { return h->L[level].storage; }
+
+int dist_cycle_storage(const DistHandle* h) {
+  for (const DDLevel& D : h->L)
+    if (D.storage != 0) return MAMG_STORE_F32;
+  return MAMG_STORE_F64;
+}
+
+int dist_set_cycle_storage(DistHandle* h, int storage, std::string* err) {
+  std::lock_guard<std::recursive_mutex> lock(capture_mutex());
+  const bool narrowed = dist_cycle_storage(h) == MAMG_STORE_F32;
+  if (storage == MAMG_STORE_F64) {
+    if (!narrowed) return MAMG_OK;
+    *err = "cycle storage: the fp64 originals of a narrowed handle are gone (fp32 storage is one way)";
+    return MAMG_ERR_UNSUPPORTED;
+  }
+  if (narrowed) return MAMG_OK;
+  if (h->w != 2) {
+    *err = "cycle storage: fp32 needs the BSR2 layout (this rank handle holds a scalar hierarchy in the CSR layout)";
+    return MAMG_ERR_UNSUPPORTED;
+  }
+  for (const DDLevel& D : h->L) {
+    if (D.patches) { *err = "cycle storage: fp32 is not available with SCHWARZ_PATCHES"; return MAMG_ERR_UNSUPPORTED; }
+    if (D.rings) { *err = "cycle storage: fp32 is not available with SCHWARZ_RINGS"; return MAMG_ERR_UNSUPPORTED; }
+    if (D.gcs.size() > 1) { *err = "cycle storage: fp32 is not available with the GS / SGS smoothers"; return MAMG_ERR_UNSUPPORTED; }
+  }
+  if (gs_smoother(h->p) || patch_schwarz(h->p) || rings_schwarz(h->p)) {
+    *err = "cycle storage: fp32 is not available with the GS / SGS smoothers or the Schwarz smoothers";
+    return MAMG_ERR_UNSUPPORTED;
+  }
+  HIPCHK(hipSetDevice(h->device));
+  struct Job {
+    DBsr* src;        // the operator whose fp64 values are read
+    DBsr* dst;        // the operator that reads the fp32 copy (src itself, or level 0's Ac)
+    bool ghost;       // the half-symmetric ghost part (gval) instead of the main array
+    float* val = nullptr;
+    const double* from() const { return ghost ? src->gval : src->val; }
+    int64_t count() const { return ghost ? ghost_value_count(*src) : value_count(*src); }
+  };
+  std::vector<Job> jobs;
+  auto add = [&](DBsr* src, DBsr* dst) {
+    if (value_count(*src) > 0) jobs.push_back({src, dst, false});
+    if (ghost_value_count(*src) > 0) jobs.push_back({src, dst, true});
+  };
+  std::vector<int> bits(h->L.size(), 0);
+  for (size_t l = 0; l < h->L.size(); ++l) {
+    DDLevel& D = h->L[l];
+    if (D.coarsest) break;
+    add(&D.A, l == 0 ? &D.Ac : &D.A);
+    add(&D.K, &D.K);
+    add(&D.P, &D.P);
+    add(&D.R, &D.R);
+    // a merged [P_loc | AP_loc] (PA, MAMG_POST_K=0) stays fp64: bsr2_post_kernel has no fp32 side
+    bits[l] = 1 | (D.PA.nr > 0 ? 0 : 2) | 4;
+  }
+  // wait for the rank's last work; the kernels below run on the null stream
+  if (h->last) HIPCHK(hipEventSynchronize(h->last));
+  if (h->side) HIPCHK(hipStreamSynchronize(h->side));
+  if (h->cap) HIPCHK(hipStreamSynchronize(h->cap));
+  // 1. every array checked before any is converted: the handle stays untouched on refusal
+  int* bad = nullptr;
+  HIPCHK(raw_malloc((void**)&bad, sizeof(int), "tmp"));
+  int hbad = 0;
+  hipError_t e = dev_memset(bad, 0, sizeof(int));
+  if (e == hipSuccess)
+    for (const Job& j : jobs) f32_check_kernel<<<f32_grid(j.count()), 256>>>(j.count(), j.from(), bad);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpy(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost);
+  (void)raw_free(bad);
+  HIPCHK(e);
+  if (hbad) {
+    *err = "cycle storage: an operator holds a finite value that is not representable in fp32";
+    return MAMG_ERR_UNSUPPORTED;
+  }
+  // 2. the fp32 arrays, all allocated and filled before any operator changes
+  for (Job& j : jobs) {
+    e = dev_malloc((void**)&j.val, (size_t)j.count() * sizeof(float));
+    if (e != hipSuccess) break;
+    f32_convert_kernel<<<f32_grid(j.count()), 256>>>(j.count(), j.from(), j.val);
+  }
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) e = null_sync();
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    for (Job& j : jobs)
+      if (j.val) (void)raw_free(j.val);
+    *err = std::string("cycle storage: ") + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? MAMG_ERR_NOMEM : MAMG_ERR_HIP;
+  }
+  // 3. the cached graphs and PCG plans hold the fp64 op list: dropped, the next use captures anew
+  h->drop_graphs();
+  for (auto& q : h->pcgs) q.release();
+  h->pcgs.clear();
+  // 4. swap the arrays in; the fp64 originals go back except level 0's A_loc (the Krylov operator)
+  auto release = [&](void* old) {
+    auto it = std::find(h->allocs.begin(), h->allocs.end(), old);
+    if (!old || it == h->allocs.end()) return;
+    (void)raw_free(old);
+    h->allocs.erase(it);
+  };
+  if (!h->L.empty() && !h->L[0].coarsest) h->L[0].Ac = h->L[0].A;   // shares A's index arrays
+  for (Job& j : jobs) {
+    double*& slot = j.ghost ? j.dst->gval : j.dst->val;
+    void* old = slot;
+    slot = reinterpret_cast<double*>(j.val);
+    j.dst->f32 = true;
+    h->allocs.push_back(j.val);
+    if (j.dst == j.src) release(old);
+  }
+  for (size_t l = 0; l < h->L.size(); ++l) h->L[l].storage = bits[l];
+  std::vector<DOp> ops;
+  dapply_ops(h, nullptr, nullptr, &ops);
+  h->apply_bytes = 0.0;
+  for (const DOp& d : ops) h->apply_bytes += d.bytes;
+  return MAMG_OK;
+}
 
 int dist_mark(DistHandle* h, hipStream_t s, std::string* err) {
   if (!h->last) HIPCHK(hipEventCreateWithFlags(&h->last, hipEventDisableTiming));
