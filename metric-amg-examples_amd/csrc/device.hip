@@ -5243,7 +5243,6 @@ void cycle_ops_csr_rings(const DeviceHandle* h, const double* b, double* xout, s
 // branch restated for CSR): x = 0, nu1 x (forward [+ backward if SGS]),
 // r = b - A x, restrict, recurse (W: a second visit on the updated residual),
 // coarse scaling, x += P e, nu2 x ([forward if SGS] + backward); in place on xout
-void cycle_ops_csr(const DeviceHandle* h, int l, const double* b, double* xout, std::vector<Op>* ops);
 void cycle_ops_csr_gs(const DeviceHandle* h, int l, const double* b, double* xout, std::vector<Op>* ops) {
   const DLevel& L = h->L[l];
   const DLevel& C = h->L[l + 1];
@@ -6660,7 +6659,65 @@ void apply_k_layout_knob(DeviceHandle* h) {
     if (!D.coarsest) set_k_split(D.KPb, 1);
 }
 
-void debug_sums(DeviceHandle* h, const char* stage, bool konly);
+// MAMG_DEBUG_SUMS=1 (diagnosis): a 64-bit FNV-1a hash of every operator
+// array of the handle, per level, printed to stderr at the end of the upload
+// and before each apply, so two handles of one problem (which must hold the
+// same bytes wherever they live) name the array that differs
+void debug_sums(DeviceHandle* h, const char* stage, bool konly) {
+#if MAMG_DIAG
+  static const bool on = [] {
+    const char* e = std::getenv("MAMG_DEBUG_SUMS");
+    return e && std::atoi(e) != 0;
+  }();
+#else
+  constexpr bool on = false;   // diagnosis build only
+#endif
+  if (!on) return;
+  // no device-wide sync: the copies below are ordered on the null stream,
+  // as every layout-builder step is
+  auto hash = [](const void* p, size_t b) -> unsigned long long {
+    if (!p || !b) return 0ull;
+    std::vector<unsigned char> v(b);
+    if (hipMemcpy(v.data(), p, b, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return 1ull; }
+    unsigned long long x = 1469598103934665603ull;
+    for (unsigned char c : v) x = (x ^ c) * 1099511628211ull;
+    return x;
+  };
+  std::string line;
+  char buf[160];
+  if (konly) {   // level 0's K values and where they live (build-time trace)
+    const DBsr& K = h->L[0].KPb;
+    const int64_t slots = (K.sell || K.half) ? K.nbs : K.nb;
+    const int per = (K.sym || K.half) ? 3 : 4;
+    const bool ar = (char*)K.val >= h->arena0 && (char*)K.val < h->arena1;
+    std::fprintf(stderr, "[mamg sums] %s L0.K val %016llx at %p (%s, %lld B)\n", stage,
+                 hash(K.val, (size_t)slots * per * 8), (void*)K.val, ar ? "arena" : "own", (long long)(slots * per * 8));
+    return;
+  }
+  for (size_t l = 0; l < h->L.size(); ++l) {
+    const DLevel& L = h->L[l];
+    const std::pair<const char*, const DBsr*> ms[] = {{"A", &L.Ab}, {"K", &L.KPb}, {"PA", &L.PAb}, {"P", &L.Pb},
+                                                      {"R", &L.Rb}, {"G", &L.Gb}};
+    for (const auto& m : ms) {
+      const DBsr& M = *m.second;
+      if (!M.nr) continue;
+      const int per = (M.sym || M.half) ? 3 : 4;
+      const int64_t slots = (M.sell || M.half) ? M.nbs : M.nb;
+      std::snprintf(buf, sizeof buf, " L%zu.%s val %016llx col %016llx", l, m.first,
+                    hash(M.val, (size_t)slots * per * (M.f32 ? 4 : 8)), hash(M.col, (size_t)slots * 4));
+      line += buf;
+    }
+    if (L.Wd) {
+      std::snprintf(buf, sizeof buf, " L%zu.W %016llx", l, hash(L.Wd, (size_t)(L.n / 2) * 32));
+      line += buf;
+    }
+    if (L.Ainv) {
+      std::snprintf(buf, sizeof buf, " L%zu.Ainv %016llx", l, hash(L.Ainv, (size_t)L.n * L.n * 8));
+      line += buf;
+    }
+  }
+  std::fprintf(stderr, "[mamg sums] %s%s\n", stage, line.c_str());
+}
 
 std::string layout_error(const mamg_params& p) {
   if (patch_schwarz(p))
@@ -7058,12 +7115,67 @@ inline int64_t value_count(const DBsr& M) {
 // pairs of its ngs slots, then their off-diagonals)
 inline int64_t ghost_value_count(const DBsr& M) { return (M.half && M.gval) ? 3 * M.ngs : 0; }
 
+// one value array to store fp32 (narrow_values)
 struct NarrowJob {
   DBsr* src;        // the operator whose fp64 values are read
   DBsr* dst;        // the operator that reads the fp32 copy (src itself, or level 0's Ac)
-  int level, bit;
+  bool ghost;       // the half-symmetric ghost part (gval) instead of the main array
   float* val = nullptr;
+  const double* from() const { return ghost ? src->gval : src->val; }
+  int64_t count() const { return ghost ? ghost_value_count(*src) : value_count(*src); }
 };
+
+// fp32 copies of the jobs' value arrays (either handle type).  1. every array
+// is checked before any is converted: a refusal leaves the handle untouched;
+// 2. all copies are made before any operator changes (undone on failure);
+// 3. drop_cached(): the caller drops what holds the fp64 op list; 4. the copies
+// are swapped in (a dst other than its src first takes src's layout: level 0's
+// Ac shares A's index arrays); release() gets each replaced original.
+template <class Drop, class Release>
+int narrow_values(std::vector<NarrowJob>& jobs, std::vector<void*>* allocs, Drop drop_cached, Release release,
+                  std::string* err) {
+  int* bad = nullptr;
+  HIPCHK(raw_malloc((void**)&bad, sizeof(int), "tmp"));
+  int hbad = 0;
+  hipError_t e = dev_memset(bad, 0, sizeof(int));
+  if (e == hipSuccess)
+    for (const NarrowJob& j : jobs) f32_check_kernel<<<f32_grid(j.count()), 256>>>(j.count(), j.from(), bad);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpy(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost);
+  (void)raw_free(bad);
+  HIPCHK(e);
+  if (hbad) {
+    *err = "cycle storage: an operator holds a finite value that is not representable in fp32";
+    return MAMG_ERR_UNSUPPORTED;
+  }
+  for (NarrowJob& j : jobs) {
+    e = dev_malloc((void**)&j.val, (size_t)j.count() * sizeof(float));
+    if (e != hipSuccess) break;
+    f32_convert_kernel<<<f32_grid(j.count()), 256>>>(j.count(), j.from(), j.val);
+  }
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) e = null_sync();
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    for (NarrowJob& j : jobs)
+      if (j.val) (void)raw_free(j.val);
+    *err = std::string("cycle storage: ") + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? MAMG_ERR_NOMEM : MAMG_ERR_HIP;
+  }
+  drop_cached();
+  // job order matters: the first job of a dst that is not its src copies src's layout into it and
+  // sets f32; a later job of the same dst (the ghost part) must find f32 set, or it would copy again
+  for (NarrowJob& j : jobs) {
+    if (j.dst != j.src && !j.dst->f32) *j.dst = *j.src;
+    double*& slot = j.ghost ? j.dst->gval : j.dst->val;
+    void* old = slot;
+    slot = reinterpret_cast<double*>(j.val);
+    j.dst->f32 = true;
+    allocs->push_back(j.val);
+    if (j.dst == j.src) release(old);
+  }
+  return MAMG_OK;
+}
 
 // a handle-owned array that nothing reads any more (the caller has waited)
 void release_owned(DeviceHandle* h, void* old) {
@@ -7117,6 +7229,12 @@ int dev_set_cycle_storage(DeviceHandle* h, int storage, std::string* err) {
   HIPCHK(hipSetDevice(h->device));
   // the launch path's levels: below the coarse tail and above the coarsest
   std::vector<NarrowJob> jobs;
+  std::vector<std::pair<int, int>> lev_bit;   // level and mamg_level_storage bit of each job
+  auto add = [&](DBsr* src, DBsr* dst, int l, int bit) {
+    if (value_count(*src) == 0) return;
+    jobs.push_back({src, dst, false});
+    lev_bit.push_back({l, bit});
+  };
   for (int l = 0; l < (int)h->L.size(); ++l) {
     DLevel& L = h->L[l];
     if (L.coarsest || (h->tail_level > 0 && l >= h->tail_level)) break;
@@ -7124,69 +7242,29 @@ int dev_set_cycle_storage(DeviceHandle* h, int storage, std::string* err) {
       *err = "cycle storage: fp32 is not available for a half-symmetric A with a ghost part";
       return MAMG_ERR_UNSUPPORTED;
     }
-    if (value_count(L.Ab) > 0) jobs.push_back({&L.Ab, l == 0 ? &L.Ac : &L.Ab, l, 1});
-    if (value_count(L.KPb) > 0) jobs.push_back({&L.KPb, &L.KPb, l, 2});
-    if (value_count(L.Pb) > 0) jobs.push_back({&L.Pb, &L.Pb, l, 2});
-    if (value_count(L.Rb) > 0) jobs.push_back({&L.Rb, &L.Rb, l, 4});
+    add(&L.Ab, l == 0 ? &L.Ac : &L.Ab, l, 1);
+    add(&L.KPb, &L.KPb, l, 2);
+    add(&L.Pb, &L.Pb, l, 2);
+    add(&L.Rb, &L.Rb, l, 4);
     // a merged [P | AP] (PAb, MAMG_POST_K=0) stays fp64: bsr2_post_kernel has no fp32 side
   }
-  // wait for the handle's last work; the kernels below run on the null stream
+  // wait for the handle's last work; narrow_values' kernels run on the null stream
   if (h->last) HIPCHK(hipEventSynchronize(h->last));
   if (h->cap) HIPCHK(hipStreamSynchronize(h->cap));
-  // 1. every array checked before any is converted: the handle stays untouched on refusal
-  int* bad = nullptr;
-  HIPCHK(raw_malloc((void**)&bad, sizeof(int), "tmp"));
-  int hbad = 0;
-  hipError_t e = dev_memset(bad, 0, sizeof(int));
-  for (const NarrowJob& j : jobs) {
-    const int64_t n = value_count(*j.src);
-    f32_check_kernel<<<f32_grid(n), 256>>>(n, j.src->val, bad);
-  }
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpy(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost);
-  (void)raw_free(bad);
-  HIPCHK(e);
-  if (hbad) {
-    *err = "cycle storage: an operator holds a finite value that is not representable in fp32";
-    return MAMG_ERR_UNSUPPORTED;
-  }
-  // 2. the fp32 arrays, all allocated before any operator changes
-  auto undo = [&]() {
-    for (NarrowJob& j : jobs)
-      if (j.val) (void)raw_free(j.val);
+  // the cached graphs hold the fp64 op list: dropped, the next apply captures anew
+  auto drop_cached = [&]() {
+    for (auto& g : h->graphs) {
+      if (g.exec) (void)hipGraphExecDestroy(g.exec);
+      if (g.graph) (void)hipGraphDestroy(g.graph);
+    }
+    h->graphs.clear();
+    for (auto& g : h->pcgs) g.release();
+    h->pcgs.clear();
   };
-  for (NarrowJob& j : jobs) {
-    const int64_t n = value_count(*j.src);
-    e = dev_malloc((void**)&j.val, (size_t)n * sizeof(float));
-    if (e != hipSuccess) break;
-    f32_convert_kernel<<<f32_grid(n), 256>>>(n, j.src->val, j.val);
-  }
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e == hipSuccess) e = null_sync();
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    undo();
-    *err = std::string("cycle storage: ") + hipGetErrorString(e);
-    return e == hipErrorOutOfMemory ? MAMG_ERR_NOMEM : MAMG_ERR_HIP;
-  }
-  // 3. the cached graphs hold the fp64 op list: dropped, the next apply captures anew
-  for (auto& g : h->graphs) {
-    if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    if (g.graph) (void)hipGraphDestroy(g.graph);
-  }
-  h->graphs.clear();
-  for (auto& g : h->pcgs) g.release();
-  h->pcgs.clear();
-  // 4. swap the arrays in; the fp64 originals go back except A_0's (the Krylov operator)
-  for (NarrowJob& j : jobs) {
-    void* old = j.src->val;
-    if (j.dst != j.src) *j.dst = *j.src;   // level 0: Ac shares Ab's index arrays
-    j.dst->val = reinterpret_cast<double*>(j.val);
-    j.dst->f32 = true;
-    h->allocs.push_back(j.val);
-    if (j.dst == j.src) release_owned(h, old);
-    h->L[j.level].storage |= j.bit;
-  }
+  // the fp64 originals go back except A_0's (the Krylov operator)
+  int rc = narrow_values(jobs, &h->allocs, drop_cached, [&](void* old) { release_owned(h, old); }, err);
+  if (rc) return rc;
+  for (size_t k = 0; k < jobs.size(); ++k) h->L[lev_bit[k].first].storage |= lev_bit[k].second;
   std::vector<Op> ops;
   apply_ops(h, h->hr, h->hz, &ops);
   h->apply_bytes = 0.0;
@@ -7199,66 +7277,6 @@ const Switches& dev_switches(const DeviceHandle* h) { return h->sw; }
 void dev_kregion(const DeviceHandle* h, std::vector<double>* ms, int* kept) {
   *ms = h->kregion_ms;
   *kept = h->kregion_best;
-}
-
-// MAMG_DEBUG_SUMS=1 (diagnosis): a 64-bit FNV-1a hash of every operator
-// array of the handle, per level, printed to stderr at the end of the upload
-// and before each apply, so two handles of one problem (which must hold the
-// same bytes wherever they live) name the array that differs
-void debug_sums(DeviceHandle* h, const char* stage, bool konly) {
-#if MAMG_DIAG
-  static const bool on = [] {
-    const char* e = std::getenv("MAMG_DEBUG_SUMS");
-    return e && std::atoi(e) != 0;
-  }();
-#else
-  constexpr bool on = false;   // diagnosis build only
-#endif
-  if (!on) return;
-  // no device-wide sync: the copies below are ordered on the null stream,
-  // as every layout-builder step is
-  auto hash = [](const void* p, size_t b) -> unsigned long long {
-    if (!p || !b) return 0ull;
-    std::vector<unsigned char> v(b);
-    if (hipMemcpy(v.data(), p, b, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return 1ull; }
-    unsigned long long x = 1469598103934665603ull;
-    for (unsigned char c : v) x = (x ^ c) * 1099511628211ull;
-    return x;
-  };
-  std::string line;
-  char buf[160];
-  if (konly) {   // level 0's K values and where they live (build-time trace)
-    const DBsr& K = h->L[0].KPb;
-    const int64_t slots = (K.sell || K.half) ? K.nbs : K.nb;
-    const int per = (K.sym || K.half) ? 3 : 4;
-    const bool ar = (char*)K.val >= h->arena0 && (char*)K.val < h->arena1;
-    std::fprintf(stderr, "[mamg sums] %s L0.K val %016llx at %p (%s, %lld B)\n", stage,
-                 hash(K.val, (size_t)slots * per * 8), (void*)K.val, ar ? "arena" : "own", (long long)(slots * per * 8));
-    return;
-  }
-  for (size_t l = 0; l < h->L.size(); ++l) {
-    const DLevel& L = h->L[l];
-    const std::pair<const char*, const DBsr*> ms[] = {{"A", &L.Ab}, {"K", &L.KPb}, {"PA", &L.PAb}, {"P", &L.Pb},
-                                                      {"R", &L.Rb}, {"G", &L.Gb}};
-    for (const auto& m : ms) {
-      const DBsr& M = *m.second;
-      if (!M.nr) continue;
-      const int per = (M.sym || M.half) ? 3 : 4;
-      const int64_t slots = (M.sell || M.half) ? M.nbs : M.nb;
-      std::snprintf(buf, sizeof buf, " L%zu.%s val %016llx col %016llx", l, m.first,
-                    hash(M.val, (size_t)slots * per * (M.f32 ? 4 : 8)), hash(M.col, (size_t)slots * 4));
-      line += buf;
-    }
-    if (L.Wd) {
-      std::snprintf(buf, sizeof buf, " L%zu.W %016llx", l, hash(L.Wd, (size_t)(L.n / 2) * 32));
-      line += buf;
-    }
-    if (L.Ainv) {
-      std::snprintf(buf, sizeof buf, " L%zu.Ainv %016llx", l, hash(L.Ainv, (size_t)L.n * L.n * 8));
-      line += buf;
-    }
-  }
-  std::fprintf(stderr, "[mamg sums] %s%s\n", stage, line.c_str());
 }
 
 int dev_apply(DeviceHandle* h, const double* d_r, double* d_z, void* stream, std::string* err) {
@@ -8198,8 +8216,6 @@ void halo_csr(const DistHandle* h, int l, double* x, const Op& op, bool split, s
     ops->push_back(wrap(b));
   }
 }
-
-void dcycle_csr(const DistHandle* h, int l, const double* b, double* xout, std::vector<DOp>* ops);
 
 // as dscale_ops: the dots over the owned rows, the scale over [owned | ghost]
 void dscale_csr(const DistHandle* h, int lc, std::vector<DOp>* ops) {
@@ -9731,15 +9747,7 @@ int dist_set_cycle_storage(DistHandle* h, int storage, std::string* err) {
     return MAMG_ERR_UNSUPPORTED;
   }
   HIPCHK(hipSetDevice(h->device));
-  struct Job {
-    DBsr* src;        // the operator whose fp64 values are read
-    DBsr* dst;        // the operator that reads the fp32 copy (src itself, or level 0's Ac)
-    bool ghost;       // the half-symmetric ghost part (gval) instead of the main array
-    float* val = nullptr;
-    const double* from() const { return ghost ? src->gval : src->val; }
-    int64_t count() const { return ghost ? ghost_value_count(*src) : value_count(*src); }
-  };
-  std::vector<Job> jobs;
+  std::vector<NarrowJob> jobs;
   auto add = [&](DBsr* src, DBsr* dst) {
     if (value_count(*src) > 0) jobs.push_back({src, dst, false});
     if (ghost_value_count(*src) > 0) jobs.push_back({src, dst, true});
@@ -9759,56 +9767,21 @@ int dist_set_cycle_storage(DistHandle* h, int storage, std::string* err) {
   if (h->last) HIPCHK(hipEventSynchronize(h->last));
   if (h->side) HIPCHK(hipStreamSynchronize(h->side));
   if (h->cap) HIPCHK(hipStreamSynchronize(h->cap));
-  // 1. every array checked before any is converted: the handle stays untouched on refusal
-  int* bad = nullptr;
-  HIPCHK(raw_malloc((void**)&bad, sizeof(int), "tmp"));
-  int hbad = 0;
-  hipError_t e = dev_memset(bad, 0, sizeof(int));
-  if (e == hipSuccess)
-    for (const Job& j : jobs) f32_check_kernel<<<f32_grid(j.count()), 256>>>(j.count(), j.from(), bad);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpy(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost);
-  (void)raw_free(bad);
-  HIPCHK(e);
-  if (hbad) {
-    *err = "cycle storage: an operator holds a finite value that is not representable in fp32";
-    return MAMG_ERR_UNSUPPORTED;
-  }
-  // 2. the fp32 arrays, all allocated and filled before any operator changes
-  for (Job& j : jobs) {
-    e = dev_malloc((void**)&j.val, (size_t)j.count() * sizeof(float));
-    if (e != hipSuccess) break;
-    f32_convert_kernel<<<f32_grid(j.count()), 256>>>(j.count(), j.from(), j.val);
-  }
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e == hipSuccess) e = null_sync();
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    for (Job& j : jobs)
-      if (j.val) (void)raw_free(j.val);
-    *err = std::string("cycle storage: ") + hipGetErrorString(e);
-    return e == hipErrorOutOfMemory ? MAMG_ERR_NOMEM : MAMG_ERR_HIP;
-  }
-  // 3. the cached graphs and PCG plans hold the fp64 op list: dropped, the next use captures anew
-  h->drop_graphs();
-  for (auto& q : h->pcgs) q.release();
-  h->pcgs.clear();
-  // 4. swap the arrays in; the fp64 originals go back except level 0's A_loc (the Krylov operator)
+  // the cached graphs and PCG plans hold the fp64 op list: dropped, the next use captures anew
+  auto drop_cached = [&]() {
+    h->drop_graphs();
+    for (auto& q : h->pcgs) q.release();
+    h->pcgs.clear();
+  };
+  // the fp64 originals go back except level 0's A_loc (the Krylov operator)
   auto release = [&](void* old) {
     auto it = std::find(h->allocs.begin(), h->allocs.end(), old);
     if (!old || it == h->allocs.end()) return;
     (void)raw_free(old);
     h->allocs.erase(it);
   };
-  if (!h->L.empty() && !h->L[0].coarsest) h->L[0].Ac = h->L[0].A;   // shares A's index arrays
-  for (Job& j : jobs) {
-    double*& slot = j.ghost ? j.dst->gval : j.dst->val;
-    void* old = slot;
-    slot = reinterpret_cast<double*>(j.val);
-    j.dst->f32 = true;
-    h->allocs.push_back(j.val);
-    if (j.dst == j.src) release(old);
-  }
+  int rc = narrow_values(jobs, &h->allocs, drop_cached, release, err);
+  if (rc) return rc;
   for (size_t l = 0; l < h->L.size(); ++l) h->L[l].storage = bits[l];
   std::vector<DOp> ops;
   dapply_ops(h, nullptr, nullptr, &ops);
@@ -9828,14 +9801,6 @@ int dist_mark(DistHandle* h, hipStream_t s, std::string* err) {
 // send / receive groups, c[2] point-to-point messages, c[3] all-reduces,
 // c[4] stream forks (interior rows on the side stream).  With P == 1 only
 // the kernels remain.
-static void count_launches(const DistHandle* h, const std::vector<DOp>& ops, int64_t c[5]);
-
-void dist_apply_launches(const DistHandle* h, int64_t c[5]) {
-  std::vector<DOp> ops;
-  dapply_ops(h, nullptr, nullptr, &ops);
-  count_launches(h, ops, c);
-}
-
 static void count_launches(const DistHandle* h, const std::vector<DOp>& ops, int64_t c[5]) {
   for (int k = 0; k < 5; ++k) c[k] = 0;
   const int P = h->nranks;
@@ -9871,6 +9836,12 @@ static void count_launches(const DistHandle* h, const std::vector<DOp>& ops, int
       }
     }
   }
+}
+
+void dist_apply_launches(const DistHandle* h, int64_t c[5]) {
+  std::vector<DOp> ops;
+  dapply_ops(h, nullptr, nullptr, &ops);
+  count_launches(h, ops, c);
 }
 
 int dist_apply(DistHandle* h, const double* d_r, double* d_z, void* stream, std::string* err) {
