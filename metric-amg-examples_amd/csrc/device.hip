@@ -3156,16 +3156,21 @@ struct PcgGraph {
 
 }  // namespace
 
-struct DeviceHandle {
-  mamg_params p;
+// The memory side of a handle, single-GPU or rank: all that dalloc and the
+// layout builders need of either.  The handle's destructor frees allocs.
+struct HandleMem {
   const Switches sw;               // the switches the handle was built with (opts.h)
-  explicit DeviceHandle(const Switches& s) : sw(s) {}
-  int device = 0;
-  bool bsr = false;
-  std::vector<DLevel> L;
   std::vector<void*> allocs;
   char* arena = nullptr;           // pre-reserved HBM, bump-allocated (dev_prereserve)
   size_t arena_left = 0;
+};
+
+struct DeviceHandle : HandleMem {
+  mamg_params p;
+  explicit DeviceHandle(const Switches& s) : HandleMem{s, {}, nullptr, 0} {}
+  int device = 0;
+  bool bsr = false;
+  std::vector<DLevel> L;
   char* arena0 = nullptr;          // the reservation's range [arena0, arena1)
   char* arena1 = nullptr;
   hipStream_t cap = nullptr;
@@ -3231,9 +3236,9 @@ inline void drained_free(void* p) { ordered_free(p); }
 // wait for the layout builder's queued work (all of it on the null stream)
 inline hipError_t null_sync() { return hipStreamSynchronize(nullptr); }
 
-// device allocation owned by a handle (single-GPU or multi-GPU: both keep `allocs`)
-template <class HT, class T>
-int dalloc(HT* h, T** p, int64_t count, std::string* err) {
+// device allocation owned by a handle (single-GPU or multi-GPU: HandleMem)
+template <class T>
+int dalloc(HandleMem* h, T** p, int64_t count, std::string* err) {
   *p = nullptr;
   if (count <= 0) return MAMG_OK;
   const size_t bytes = ((size_t)count * sizeof(T) + 4095) & ~(size_t)4095;
@@ -3313,8 +3318,7 @@ int pick_lanes_bsr(int64_t nr, int64_t nb) {
 }
 
 // SELL-64 copy of a BSR2 matrix (host packing: convert.cpp to_sell)
-template <class HT>
-int upload_sell(HT* h, const HBsr& B, DBsr* D, std::string* err) {
+int upload_sell(HandleMem* h, const HBsr& B, DBsr* D, std::string* err) {
   HSell S;
   const bool merged = (int64_t)B.ptr.size() == 2 * B.nr + 1;
   int rc = to_sell(B, D->sym, SELL_C, merged ? SELL_SIGMA : 1, &S, err);
@@ -3341,8 +3345,7 @@ int upload_sell(HT* h, const HBsr& B, DBsr* D, std::string* err) {
 }
 
 // (also uploads a merged [P | AP] matrix: then B.ptr has 2 nr + 1 entries)
-template <class HT>
-int upload_bsr(HT* h, const HBsr& B, DBsr* D, int lanes, std::string* err,
+int upload_bsr(HandleMem* h, const HBsr& B, DBsr* D, int lanes, std::string* err,
                bool sym = false) {
   const int64_t np = (int64_t)B.ptr.size();
   D->nr = B.nr;
@@ -3929,8 +3932,7 @@ std::vector<int32_t> band_sched(int64_t G, int64_t S, int nsub) {
   return sched;
 }
 
-template <class HT>
-int upload_sched(HT* h, const std::vector<int32_t>& sched, int32_t** d, int64_t* n, std::string* err) {
+int upload_sched(HandleMem* h, const std::vector<int32_t>& sched, int32_t** d, int64_t* n, std::string* err) {
   int rc;
   if ((rc = dalloc(h, d, (int64_t)sched.size(), err))) return rc;
   HIPCHK(hipMemcpy(*d, sched.data(), sched.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -3951,8 +3953,7 @@ int upload_sched(HT* h, const std::vector<int32_t>& sched, int32_t** d, int64_t*
 // which rows: every row is still summed by one lane in its own order, so the
 // result is bitwise that of any other order.  Unstructured or narrow-band
 // matrices (< 4 blocks per band) keep the row_block order.
-template <class HT>
-int build_band_sched(HT* h, const TBsr& B, DBsr* D, std::string* err) {
+int build_band_sched(HandleMem* h, const TBsr& B, DBsr* D, std::string* err) {
   const int64_t nr = B.nr, G = (nr + 255) / 256;
   if (h->sw.half_bands <= 0 || G < 64) return MAMG_OK;
   const int ns = 257;
@@ -3975,8 +3976,7 @@ int build_band_sched(HT* h, const TBsr& B, DBsr* D, std::string* err) {
 
 // the same for the launch over rows [r0, r1) only (block b covers rows
 // r0 + 256 b ..): the multi-GPU interior run
-template <class HT>
-int build_band_sched_range(HT* h, DBsr* D, int64_t r0, int64_t r1, std::string* err) {
+int build_band_sched_range(HandleMem* h, DBsr* D, int64_t r0, int64_t r1, std::string* err) {
   if (!D->half || D->band_stride <= 0 || r1 <= r0) return MAMG_OK;
   const std::vector<int32_t> sched = band_sched((r1 - r0 + 255) / 256, D->band_stride, h->sw.half_bands);
   if (sched.empty()) return MAMG_OK;
@@ -4041,8 +4041,7 @@ std::vector<int32_t> rest_band_sched(const std::vector<int32_t>& c0, int64_t Sf,
 
 // the schedule for D (a lane-group BSR, not SELL / merged) given the fine
 // plane stride Sf of its columns
-template <class HT>
-int build_rest_sched(HT* h, TmpPool* T, DBsr* D, int64_t Sf, std::string* err) {
+int build_rest_sched(HandleMem* h, TmpPool* T, DBsr* D, int64_t Sf, std::string* err) {
   if (h->sw.r_bands <= 0 || Sf <= 0 || D->sell || D->half || !D->ptr || D->lanes <= 0) return MAMG_OK;
   const int rpw = 256 / D->lanes;
   const int64_t G = (D->nr * (int64_t)D->lanes + 255) / 256;
@@ -4068,8 +4067,7 @@ int build_rest_sched(HT* h, TmpPool* T, DBsr* D, int64_t Sf, std::string* err) {
 // MAMG_OK with D->half false when a mirror is missing or differs, a row part
 // is too long, or the ELL padding would exceed ~30 % (the caller then builds
 // SELL-64); temporaries of a rejected attempt are freed with the pool.
-template <class HT>
-int try_half(HT* h, TmpPool* T, const TBsr& B, DBsr* D, std::string* err) {
+int try_half(HandleMem* h, TmpPool* T, const TBsr& B, DBsr* D, std::string* err) {
   int rc;
   const int64_t nr = B.nr, ns = (nr + SELL_C - 1) / SELL_C;
   int* wm = nullptr;   // [0] max upper, [1] max lower, [2] part too long, [3] not symmetric
@@ -4135,8 +4133,7 @@ int try_half(HT* h, TmpPool* T, const TBsr& B, DBsr* D, std::string* err) {
 // host BSR2 (multi-GPU rank-local level-0 A: owned rows, [owned | ghost]
 // columns) -> half-symmetric ELL-64 when its owned part is symmetric bitwise,
 // else upload_bsr (SELL-64 / lane groups)
-template <class HT>
-int upload_half_or_bsr(HT* h, const HBsr& B, DBsr* D, std::string* err) {
+int upload_half_or_bsr(HandleMem* h, const HBsr& B, DBsr* D, std::string* err) {
   const int64_t np = (int64_t)B.ptr.size();
   if (h->sw.half && B.nr >= h->sw.sell_min_rows && np == B.nr + 1 && blocks_symmetric(B)) {
     int rc;
@@ -4165,8 +4162,7 @@ int upload_half_or_bsr(HT* h, const HBsr& B, DBsr* D, std::string* err) {
 // final apply layout from a raw device BSR (the device-side counterpart of
 // upload_bsr): SELL-64 for large short-row plain matrices, symmetric-block
 // packing where every block has (0,1) == (1,0) bitwise, else 4 doubles/block
-template <class HT>
-int finalize_bsr(HT* h, TmpPool* T, TBsr& B, DBsr* D, int lanes, bool sym_ok, std::string* err,
+int finalize_bsr(HandleMem* h, TmpPool* T, TBsr& B, DBsr* D, int lanes, bool sym_ok, std::string* err,
                  bool allow_sell = true, bool allow_half = false, bool allow_msell = false) {
   int rc;
   const int64_t nr = B.nr, np = B.merged ? 2 * nr + 1 : nr + 1;
@@ -4241,8 +4237,7 @@ int finalize_bsr(HT* h, TmpPool* T, TBsr& B, DBsr* D, int lanes, bool sym_ok, st
 // stored blocks for the bidomain K.  Sorted, the rows sharing a line have equal
 // or neighbouring lengths (1.9 %).  Each row keeps its blocks and their order:
 // results are bitwise those of row order (test_k_row_sort_bitwise).
-template <class HT>
-int sort_sell_slices(HT* h, TmpPool* T, DBsr* D, std::string* err) {
+int sort_sell_slices(HandleMem* h, TmpPool* T, DBsr* D, std::string* err) {
   int rc;
   if (!D->sell || D->split || D->nr == 0) return MAMG_OK;
   const int64_t ns = (D->nr + SELL_C - 1) / SELL_C, per = D->sym ? 3 : 4;
@@ -4310,8 +4305,7 @@ __global__ __launch_bounds__(64) void sell_col16_kernel(int64_t nr, const int64_
   const int32_t b = cbase[s];
   for (int j = 0; j < len; ++j) c16[k + (int64_t)SELL_C * j] = (uint16_t)(col[k + (int64_t)SELL_C * j] - b);
 }
-template <class HT>
-int compress_sell_cols(HT* h, TmpPool* T, DBsr* D, std::string* err) {
+int compress_sell_cols(HandleMem* h, TmpPool* T, DBsr* D, std::string* err) {
   int rc;
   if (!D->sell || D->half || D->nr == 0 || D->nbs == 0) return MAMG_OK;
   const int64_t ns = (D->nr + SELL_C - 1) / SELL_C;
@@ -4437,8 +4431,7 @@ int gs_colour(TmpPool* T, const TBsr& B, int level, int8_t** ca_out, int* ncol_o
 // radix sort of the rows by colour (ascending row within a colour), the
 // permuted BSR2 copy, its block inverses (node blocks from W's pattern) and
 // the colour ranges (each colour padded to whole 64-row slices)
-template <class HT>
-int gs_layout(HT* h, TmpPool* T, const TBsr& B, const double* W, const int8_t* ca, int ncol, int level,
+int gs_layout(HandleMem* h, TmpPool* T, const TBsr& B, const double* W, const int8_t* ca, int ncol, int level,
               DBsr* Gb, int32_t** gperm, dv4** Gd, std::vector<int64_t>* gcs_out, std::vector<int64_t>* gbk,
               std::string* err) {
   int rc;
@@ -4508,8 +4501,7 @@ int gs_layout(HT* h, TmpPool* T, const TBsr& B, const double* W, const int8_t* c
 // Multicolour GS layout of one level from A_l's device BSR2 B and the
 // level's (scaled) smoother blocks W (only their pattern is used: a node
 // whose W block is diagonal has two 1x1 smoother blocks)
-template <class HT>
-int build_gs(HT* h, TmpPool* T, const TBsr& B, const double* W, int level, DLevel* D, std::string* err) {
+int build_gs(HandleMem* h, TmpPool* T, const TBsr& B, const double* W, int level, DLevel* D, std::string* err) {
   int8_t* ca = nullptr;
   int ncol = 0;
   int rc = gs_colour(T, B, level, &ca, &ncol, err);
@@ -4561,8 +4553,7 @@ inline int64_t csr_gs_small_rows() {
 // the colouring runs on *pattern instead, and only the rows with cov == 0
 // enter the colour lists and the permuted copy (G.ptr then has one entry per
 // listed row + 1; G.n stays the length of x).
-template <class HT>
-int build_gs_csr(HT* h, TmpPool* T, const DCsr& A, int level, int lanes, DLevel* D, std::string* err,
+int build_gs_csr(HandleMem* h, TmpPool* T, const DCsr& A, int level, int lanes, DLevel* D, std::string* err,
                  const TBsr* pattern = nullptr, const uint8_t* cov = nullptr) {
   int rc;
   const int64_t n = A.n;
@@ -6887,19 +6878,21 @@ void dev_prereserve_release() {
   g_pre_bytes = 0;
   g_pre_dev = -1;
 }
-template <class HT>
-void adopt_prereserve(HT* h) {
-  if (!g_pre || g_pre_dev != h->device) { dev_prereserve_release(); return; }
+void adopt_prereserve(HandleMem* h, int device) {
+  if (!g_pre || g_pre_dev != device) { dev_prereserve_release(); return; }
   h->allocs.push_back(g_pre);
   h->arena = (char*)g_pre;
   h->arena_left = g_pre_bytes;
-  if constexpr (std::is_same<HT, DeviceHandle>::value) {
-    h->arena0 = (char*)g_pre;
-    h->arena1 = (char*)g_pre + g_pre_bytes;
-  }
   g_pre = nullptr;
   g_pre_bytes = 0;
   g_pre_dev = -1;
+}
+// a DeviceHandle also keeps the adopted range [arena0, arena1) (release_owned,
+// rehome_array: arena memory stays with the reservation); none adopted: empty
+void adopt_prereserve(DeviceHandle* h) {
+  adopt_prereserve(static_cast<HandleMem*>(h), h->device);
+  h->arena0 = h->arena;
+  h->arena1 = h->arena + h->arena_left;
 }
 
 int dev_from_ghier(GHier* G, const DevMat& A0, const mamg_params& p, DeviceHandle** out,
@@ -7769,17 +7762,13 @@ inline const DBsr& dcyc_A(const DDLevel& D) { return D.Ac.f32 ? D.Ac : D.A; }
 
 }  // namespace
 
-struct DistHandle {
+struct DistHandle : HandleMem {
   mamg_params p;
-  const Switches sw;                   // the switches the handle was built with (opts.h)
-  explicit DistHandle(const Switches& s) : sw(s) {}
+  explicit DistHandle(const Switches& s) : HandleMem{s, {}, nullptr, 0} {}
   int rank = 0, nranks = 1, device = 0;
   int w = 2;                           // dofs per node: 2 nodal (BSR2), 1 scalar (CSR)
   ncclComm_t comm = nullptr;
   std::vector<DDLevel> L;
-  std::vector<void*> allocs;
-  char* arena = nullptr;
-  size_t arena_left = 0;
   double apply_bytes = 0.0;
   int64_t nv0 = 0, o0 = 0, o1 = 0;
   bool dry = false;                    // MAMG_DIST_TEST=dry: virtual rank skips its exchanges (timing only)
@@ -9519,7 +9508,7 @@ int dist_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, con
   h->nranks = nranks;
   h->w = plan.dofs;
   h->device = p.device;
-  adopt_prereserve(h.get());
+  adopt_prereserve(h.get(), h->device);
   HIPCHK(hipSetDevice(p.device));
   if (comm_id) {                         // RCCL communicator; NULL = virtual (tests)
     ncclUniqueId uid;

@@ -343,15 +343,15 @@ DEFAULT_OPTIONS = {
     'MAMG_TAIL_NODES': 'auto', 'MAMG_TAIL_VL': '4', 'MAMG_TAIL_LDS': '1', 'MAMG_TAIL_PROG_LDS': '0',
     'MAMG_TAIL_RES': '1', 'MAMG_HALF': '1', 'MAMG_HALF_BANDS': '1', 'MAMG_R_BANDS': '1', 'MAMG_K_SORT': '1',
     'MAMG_K_COL16': '1', 'MAMG_FUSE_RBD': '2',
-    'MAMG_CSR2BSR_FILL': '1',            # device.hip:3704 (on unless 0) and gsetup.hip:2280 (off when 0) agree
+    'MAMG_CSR2BSR_FILL': '1',            # opts.h default on, off only when 0; consumed in device.hip dev_csr_to_bsr and gsetup.hip (node graph)
     'MAMG_KREGION_TRIES': '4', 'MAMG_KREGION_BUDGET_MS': '200',
-    'MAMG_REHOME': '1',                  # device.hip:6357: off only when given as 0
-    'MAMG_PRERESERVE_B_PER_NNZ': '20',   # device.hip:6587: atof, default 20.0
+    'MAMG_REHOME': '1',                  # opts.h default on, off only when 0; consumed in device.hip rehome_operators
+    'MAMG_PRERESERVE_B_PER_NNZ': '20',   # opts.h default 20.0 (parsed in opts.cpp); consumed in device.hip dev_prereserve
     'MAMG_POISON': '0', 'MAMG_OVERLAP': '1', 'MAMG_DIST_TEST': '', 'MAMG_SPGEMM_PAIR': '1',
     'MAMG_SPGEMM_STAGE_GB': '16', 'MAMG_SPGEMM_STAGE_STRIDE': '128',
     'MAMG_MIS_STAGED': '1',              # gsetup.hip:2352: on unless given as 0
     'MAMG_UPLOAD_THREADS': '2',          # gsetup.hip:3304: default 2, clamped to [1, 16]
-    'MAMG_PATCH_INV': '3',               # device.hip:2335: 1 and 2 as given, anything else 3
+    'MAMG_PATCH_INV': '3',               # opts.cpp: 1 and 2 as given, anything else 3; consumed in device.hip launch_patch_inv
 }
 
 
