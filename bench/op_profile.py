@@ -5,7 +5,7 @@ device.hip dev_time_apply) for a smoother profile at nrefs N, on stderr.
     python bench/op_profile.py [--nrefs 6] [--profile jacobi|sgs|ref_family] [--reps 5]
 
 Op kinds: 0 CSR, 1 SCALE, 2 GEMV, 3 AXPY, 4 BSR, 5 BD, 6 POST, 7 ILV, 8 GS,
-9 ZERO, 10 DOT2, 11 CSCALE, 12 PATCH, 13 TAIL (device.hip OpKind); rows =
+9 ZERO, 10 DOT2, 11 CSCALE, 12 PATCH, 13 TAIL (device_int.h OpKind); rows =
 the operator's node rows (vector ops: their length).
 """
 import argparse

@@ -1,4 +1,5 @@
-// device.h -- device hierarchy interface (no HIP types; implemented in device.hip)
+// device.h -- device hierarchy interface (no HIP types; implemented in device.hip and, the
+// multi-GPU part, in dist_layout.hip and dist_apply.hip)
 #pragma once
 #include <mutex>
 #include <string>
@@ -59,7 +60,7 @@ int dev_time_apply(DeviceHandle* h, const double* d_r, double* d_z, int reps, in
                    double* ms, double* kernel_ms, double* class_bytes, void* stream,
                    std::string* err);
 
-// multi-GPU (device.hip, second half)
+// multi-GPU (dist_layout.hip: dist_check, dist_upload; dist_apply.hip: the rest)
 struct DistHandle;
 int dist_get_unique_id(void* id, std::string* err);
 // ghosts: precomputed ghost lists (ghier_download_rank), else nullptr; G / A0d:

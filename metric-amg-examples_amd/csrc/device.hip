@@ -25,25 +25,7 @@
 // a fused epilogue.  One apply = a fixed schedule of launches captured into a
 // hipGraph; each launch carries its algorithmic bytes (roofline from the
 // hierarchy, not from counters).
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <mutex>
-#include <map>
-#include <numeric>
-#include <vector>
-
-#include "device.h"
-#include "dmem.h"
-#include "opts.h"
-#include "rowstage.h"
+#include "device_int.h"
 
 #include <pthread.h>
 
@@ -104,30 +86,6 @@ hipError_t graph_instantiate(hipGraphExec_t* ex, hipGraph_t g) {
 }
 
 namespace {
-
-#define HIPCHK(expr)                                                                 \
-  do {                                                                               \
-    hipError_t e_ = (expr);                                                          \
-    if (e_ != hipSuccess) {                                                          \
-      *err = std::string(#expr) + ": " + hipGetErrorString(e_);                      \
-      return MAMG_ERR_HIP;                                                           \
-    }                                                                                \
-  } while (0)
-
-// epilogues: y = s | y = y0 + s | r = b - s | x' = x + w (b - s) (point) |
-// x' = x + W_I (b_I - s_I) (2x2 block, BSR only) |
-// z = x1_I + W_I r1_I + s_I with s = K e, K = P - W (A P) (BSR only: the
-// prolongation fused with the first post sweep through one operator)
-enum Epi { EPI_Y = 0, EPI_YADD = 1, EPI_RESID = 2, EPI_JACOBI = 3, EPI_BJAC = 4, EPI_KPOST = 5, EPI_YBD = 6 };
-// EPI_YBD (bsr2_kernel only): out = A x as EPI_Y, and the next level's first
-// sweep from x = 0 in the same pass, y <- W out (the restriction b_c = R r
-// writing x1_c = W_c b_c: one launch and one b_c read fewer per coarse level;
-// the same two products as bd2_kernel, so the same bits)
-
-typedef double dv4 __attribute__((ext_vector_type(4)));
-typedef double dv2 __attribute__((ext_vector_type(2)));
-
-constexpr int SCALE_BLOCKS = 256;   // partial-sum blocks of the coarse-scaling dots
 
 // ---------------------------------------------------------------------------
 // CSR kernels (general layout)
@@ -897,6 +855,15 @@ __global__ __launch_bounds__(256) void wscale_kernel(int64_t n, double w, const 
   if (i < n) out[i] = w * in[i];
 }
 
+}  // namespace
+
+// the rank layout's launch of wscale_kernel (dist_layout.hip), on the null stream
+void wscale(int64_t n, double w, const double* in, double* out) {
+  wscale_kernel<<<nblocks(n), 256>>>(n, w, in, out);
+}
+
+namespace {
+
 __global__ __launch_bounds__(256) void axpy_kernel(int64_t n, const double* __restrict__ e,
                                                    double* x) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -920,7 +887,6 @@ __global__ __launch_bounds__(256) void gemv_kernel(int64_t n, const double* __re
 }
 
 // ---- CG vector kernels ------------------------------------------------------
-constexpr int DOT_BLOCKS = 1024;
 
 __global__ __launch_bounds__(256) void dot_partial_kernel(int64_t n, const double* __restrict__ a,
                                                           const double* __restrict__ b,
@@ -935,15 +901,6 @@ __global__ __launch_bounds__(256) void dot_partial_kernel(int64_t n, const doubl
   __syncthreads();
   if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
-
-// ---- device-resident PCG state (dev_pcg): the scalars of cbc.block's
-// ConjGrad live in HBM, so an iteration is one replayable hipGraph and the
-// host only polls the state one iteration behind the GPU
-struct PcgState {
-  double rz, dq, alpha, beta, tol;
-  int it, maxiter, active, run, status;   // status: PCG_* below
-};
-enum { PCG_RUNNING = 0, PCG_STOPPED = 1, PCG_DQ_ZERO = 2, PCG_RZ_NEG = 3, PCG_NOT_POS = 4 };
 
 __device__ double block_sum256(double s) {   // 256 threads -> thread 0
   __shared__ double red[4];
@@ -1027,34 +984,6 @@ __global__ __launch_bounds__(256) void pcg_d_kernel(int64_t n, const PcgState* _
   if (st->status == PCG_RZ_NEG) x[i] = x[i] - st->alpha * d[i];
   else d[i] = z[i] + st->beta * d[i];
 }
-
-// ---- the same loop on N row-partitioned ranks (dist_pcg).  A
-// rank's dot is its block partials summed in a fixed order into ONE double,
-// written to slot [rank] of a P-vector whose other slots are zero; the
-// all-reduce of the P-vector only ever adds zeros to it (exact), so every
-// rank and every backend reads the same P doubles, and the alpha / beta
-// kernels add them in rank order: the same bits everywhere, whatever the
-// reduction tree.  rr / thr: ||r||^2 and stop_type 1's threshold tol ||b||.
-struct DPcgState {
-  double rz, dq, alpha, beta, tol, rr, thr;
-  int it, maxiter, active, run, status, stop;
-};
-
-// what the distributed PCG ops of one (x, maxiter, stop_type) plan work on
-// (device pointers; the struct itself lives on the host, owned by the plan)
-struct DPcgCtx {
-  DPcgState* st = nullptr;
-  int64_t n = 0;                  // w * nloc owned entries
-  int P = 1, rank = 0, stop = 0;
-  double *x = nullptr, *r = nullptr, *z = nullptr, *d = nullptr, *q = nullptr;
-  double* part = nullptr;         // 3 * DOT_BLOCKS block partials (dot 0, ||r||^2, ||b||^2)
-  double* pv = nullptr;           // 3 P-vectors
-  double *res = nullptr, *rn = nullptr, *al = nullptr, *be = nullptr;   // histories
-  // the solve in flight (start-up ops only; the iteration reads none of them)
-  const double* b = nullptr;
-  double tol = 0.0;
-  int relconv = 0, maxiter = 0;
-};
 
 __device__ __forceinline__ void block_part256(double s, double* __restrict__ out) {
   __shared__ double red[4];
@@ -1288,42 +1217,10 @@ __global__ __launch_bounds__(256) void gs2_kernel(
 // W-cycle (HEM ratio ~4, levels visited 2^l times, one launch per colour)
 // this replaces tens of thousands of ~5 us launches per apply.
 // ---------------------------------------------------------------------------
-enum TKind { T_BSR = 0, T_BD = 1, T_GEMV = 2, T_AXPY = 3, T_ZERO = 4, T_GS = 5, T_DOT2 = 6, T_CSCALE = 7,
-             T_COPY = 8, T_RLOAD = 9 };
-// LDS residency (tail_lds_plan): the program itself and every work vector of
-// the tail levels live in the workgroup's LDS for the whole launch; a vector
-// field of a TOp then holds (byte offset in the dynamic LDS) | 1 instead of a
-// global pointer (doubles are 8-aligned, so bit 0 tags it), resolved per op.
-// T_COPY ops at the ends move the vectors read before written in, and the
-// written ones out.  The colour steps' dependent chain becomes LDS op
-// descriptor (scalar loads) -> global (L2) row pointers, columns, values ->
-// LDS x gathers.
-// Register residency (tail_kernel RES, tail_res_plan): the rows of the tail
-// levels' operators are spread over the workgroup's threads, one row per
-// thread, and held in registers for the whole launch (T_RLOAD ops at the
-// start load them).  An op with res = 1 on such a matrix: thread t computes
-// row t - rbase if that lies in the op's (compact) row range [r0, r1), from
-// registers; ridx maps compact rows to the matrix's rows (a GS layout pads
-// each colour to whole 64-row slices).  A colour step is then LDS descriptor
-// -> LDS x gathers -> LDS store, with no global round trip.
-struct TOp {
-  int kind = 0, epi = 0, vl = 1, sym = 0, res = 0, rbase = 0;
-  int64_t n = 0, r0 = 0, r1 = 0, nb = 0;
-  const int64_t* ptr = nullptr;
-  const int32_t* col = nullptr;
-  const double* val = nullptr;
-  const double *x = nullptr, *y = nullptr, *b = nullptr, *w = nullptr;
-  const dv4* W = nullptr;
-  double* out = nullptr;
-  const int32_t* perm = nullptr;
-  double* part = nullptr;
-  const int32_t* ridx = nullptr;
-};
 // 512 threads: 256 VGPRs per lane (1024 would cap them at 128 and spill the
 // interpreter's loop state to scratch); the tail's ops hold a few hundred
 // rows x <= 4 lanes, so one or two passes either way
 constexpr int TAIL_THREADS = 512;
-
 
 // v + (v of the lane M away) inside groups of 4 lanes, by DPP quad
 // permutations (one VALU op per 32-bit half) instead of an LDS-routed
@@ -1978,7 +1875,6 @@ __global__ __launch_bounds__(256) void perm_len_kernel(int64_t nrp, const int32_
 // hops apart: no patch of a launch reads an x another one writes).
 // Oracle: mamg_oracle.Patches (colouring, inverses, sweep).
 // ---------------------------------------------------------------------------
-constexpr int PATCH_MAX_NODES = 16;
 constexpr int PATCH_WORDS = 4;          // 256 colours
 
 __device__ __forceinline__ uint64_t patch_key_dev(int64_t I) {
@@ -2532,6 +2428,8 @@ __global__ __launch_bounds__(256, 4) void patch_inv3_kernel(int64_t np, const in
   if (live && ok) patch_store(S, lane, 64, d, -1.0, U + i * ustride);
 }
 
+}  // namespace
+
 // version (MAMG_PATCH_INV): 1 the round-5 kernel (one patch per wave), 2 two
 // patches per wave (bitwise the same), default 3 the matrix-core block sweep
 void launch_patch_inv(int version, int64_t np, const int32_t* perm, const int64_t* ptr, const int32_t* col,
@@ -2547,6 +2445,8 @@ void launch_patch_inv(int version, int64_t np, const int32_t* perm, const int64_
     default: patch_inv3_kernel<<<(unsigned)((np + 3) / 4), 256>>>(np, perm, ptr, col, gcol, val, ustride, U, bad); break;
   }
 }
+
+namespace {
 
 // One colour of a patch sweep, one wave per patch (4 per workgroup), in place
 // on x (node-interleaved):  x|_p += Minv_p (b - A x)|_p.  The patch's node rows
@@ -2788,6 +2688,15 @@ __global__ __launch_bounds__(256) void ring_perm_inv_kernel(int64_t nb, const in
   }
 }
 
+}  // namespace
+
+// the rank layout's launch of ring_perm_inv_kernel (dist_layout.hip), on the null stream
+void ring_perm_inv(int64_t nb, const int32_t* ord, const int64_t* blen, const int64_t* sq, const double* inv, const int64_t* rio, double* rinv) {
+  ring_perm_inv_kernel<<<(unsigned)nb, 256>>>(nb, ord, blen, sq, inv, rio, rinv);
+}
+
+namespace {
+
 // the rest's GS (RINGS): node blocks with one covered dof become split
 // (diagonal) smoother blocks, so gs_layout inverts them as two 1x1 blocks;
 // cov[I]: bit f = dof f of node I lies in a seed block
@@ -2800,6 +2709,15 @@ __global__ __launch_bounds__(256) void rest_w_kernel(int64_t nv, const dv4* __re
   Wp[I] = (c == 1 || c == 2) ? dv4{w.x, 0.0, 0.0, w.w} : w;
 }
 
+}  // namespace
+
+// the rank layout's launch of rest_w_kernel (dist_layout.hip), on the null stream
+void rest_w(int64_t nv, const dv4* W, const uint8_t* cov, dv4* Wp) {
+  rest_w_kernel<<<nblocks(nv), 256>>>(nv, W, cov, Wp);
+}
+
+namespace {
+
 // ... and the covered dofs take no update: their rows / columns of D zeroed
 __global__ __launch_bounds__(256) void rest_mask_kernel(int64_t nr, const int32_t* __restrict__ perm,
                                                         const uint8_t* __restrict__ cov, dv4* __restrict__ D) {
@@ -2811,6 +2729,15 @@ __global__ __launch_bounds__(256) void rest_mask_kernel(int64_t nr, const int32_
   else if (c == 1) D[i] = dv4{0.0, 0.0, 0.0, d.w};
   else if (c == 2) D[i] = dv4{d.x, 0.0, 0.0, 0.0};
 }
+
+}  // namespace
+
+// the rank layout's launch of rest_mask_kernel (dist_layout.hip), on the null stream
+void rest_mask(int64_t nr, const int32_t* perm, const uint8_t* cov, dv4* D) {
+  rest_mask_kernel<<<nblocks(nr), 256>>>(nr, perm, cov, D);
+}
+
+namespace {
 
 // 2x2 Gauss-Jordan without pivoting in mamg_oracle.batched_inverse's
 // operation order (no contraction), on node I's diagonal block; the
@@ -2906,8 +2833,6 @@ __global__ __launch_bounds__(256) void cscale_kernel(int64_t n, int nb, const do
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) e[i] = a * e[i];
 }
 
-inline unsigned nblocks(int64_t work) { return (unsigned)((work + 255) / 256); }
-
 // Fixed by measurement (round 1 A/Bs; the variants
 // measured slower were removed in round 2): XCD-contiguous restriction rows,
 // SELL chunks of 8 blocks (K: 6), half-symmetric chunks of 4 with
@@ -2936,331 +2861,7 @@ void pack_sym(const HBsr& B, std::vector<double>* v3) {
   }
 }
 
-// ---------------------------------------------------------------------------
-// device structures
-// ---------------------------------------------------------------------------
-struct DCsr {
-  int64_t n = 0, m = 0, nnz = 0;
-  int64_t* ptr = nullptr;
-  int32_t* col = nullptr;
-  double* val = nullptr;
-  int lanes = 8;
-};
-
-struct DBsr {              // 2x2 blocks, node-major
-  int64_t nr = 0, nc = 0, nb = 0;
-  int64_t* ptr = nullptr;
-  int32_t* col = nullptr;
-  double* val = nullptr;   // 4 doubles per block, 3 if sym
-  int lanes = 8;
-  bool sym = false;        // symmetric-block format (every block has (0,1) == (1,0))
-  // SELL-64 storage (sell == true): ptr unused; soff per slice, meta per row,
-  // col / val hold nbs (>= nb, padded) slots
-  bool sell = false;
-  int split = 0;            // SELL general blocks as two 16-byte streams (1: two global streams,
-                            // 2: split inside each slot row; sell2_kernel / msell_kernel SPL)
-  int lpr = 1;              // SELL lanes per row: 1 sell2_kernel, > 1 msell_kernel
-  int64_t nbs = 0;
-  int64_t* soff = nullptr;
-  int32_t* meta = nullptr;
-  int32_t* perm = nullptr;  // SELL-C-sigma: row held by each slot (merged matrices)
-  bool lsort = false;       // SELL rows sorted by length inside each slice: meta is per slot,
-                            // length | (row - slice start) << 16 (sort_sell_slices)
-  // SELL columns as 16-bit offsets from a per-slice base (level-0 K, round
-  // 6: compress_sell_cols); col is kept for the layout code, the kernel reads
-  // col16 + cbase
-  uint16_t* col16 = nullptr;
-  int32_t* cbase = nullptr;
-  int kvar = 0;             // a K's kernel variant (launch_kvariant; 0 in the product build)
-  // half-symmetric ELL-64 (half == true, A symmetric bitwise): col / val hold
-  // the upper part I <= J < nr, hwu slots per row; lptr holds,
-  // per lower entry J < I, the slot of the mirror block (J, I) in the upper
-  // part, hwl slots per row; ghost columns (>= nr, multi-GPU rank-local A)
-  // in their own SELL-64 part (gsoff per slice, zero width where a slice has
-  // none); meta = upper length | lower length << 8 | ghost length << 16
-  bool half = false;
-  int hwu = 0, hwl = 0;
-  int64_t nlo = 0;          // lower entries (nb = upper + ghost entries + nlo)
-  int32_t* lptr = nullptr;
-  int64_t ngs = 0;          // ghost-part slots (0: no ghost part)
-  int64_t* gsoff = nullptr;
-  int32_t* gcol = nullptr;
-  double* gval = nullptr;
-  // band schedule of the half-symmetric kernel (full-range launches):
-  // workgroup b processes 256-row block sched[b] (nullptr: row_block order)
-  int32_t* sched = nullptr;
-  int64_t nsched = 0;
-  int64_t band_stride = 0;  // plane stride S in rows (0: no band schedule)
-  // band schedule of one sub-range launch [sr0, sr1) (multi-GPU interior rows)
-  int32_t* sched_r = nullptr;
-  int64_t nsched_r = 0, sr0 = 0, sr1 = 0;
-  // plane-band schedule of a lane-group BSR launch with rsched_vl lanes per
-  // row (the level-0 restriction): workgroup b processes row block rsched[b]
-  int32_t* rsched = nullptr;
-  int64_t nrsched = 0;
-  int rsched_vl = 0;
-  // values stored fp32 (dev_set_cycle_storage): val then points to a float
-  // array of the same element layout, read by the kernels' float side
-  bool f32 = false;
-};
-
-struct DLevel {
-  int64_t n = 0;           // dofs
-  bool coarsest = false;
-  DCsr A, P, R, WB;        // CSR layout
-  DBsr Ab, Pb, Rb;         // BSR2 layout
-  DBsr PAb;                // BSR2 post fusion: merged [P | AP] rows (ptr: 2 nr + 1)
-  DBsr KPb;                // BSR2 post fusion: K = P - W (A P), one operator (default)
-  // fp32 cycle storage (dev_set_cycle_storage), level 0 only: A_0 as the cycle
-  // reads it -- Ab's layout with fp32 copies of its value arrays (Ac.f32), the
-  // index arrays shared; Ab itself stays fp64 for the Krylov operator.  On the
-  // other narrowed levels Ab's values are replaced in place.
-  DBsr Ac;
-  int storage = 0;         // mamg_level_storage bits: 1 A, 2 K / P, 4 R stored fp32
-  dv4* Wd = nullptr;       // BSR2 layout: 2x2 smoother block per node
-  double* winv = nullptr;
-  // SMOOTHER_POLY: the step smoothers w_k W, k = 1..m (BSR2: Wk; CSR: WBk
-  // sharing WB's pattern, or winvk); empty for the Jacobi smoothers
-  std::vector<dv4*> Wk;
-  std::vector<DCsr> WBk;
-  std::vector<double*> winvk;
-  double* Ainv = nullptr;
-  double *b = nullptr, *x = nullptr, *t = nullptr, *t2 = nullptr, *r = nullptr,
-         *c = nullptr, *e = nullptr;
-  // multicolour Gauss-Seidel (SMOOTHER_SGS / SMOOTHER_GS, BSR2 layout): A_l's
-  // node rows permuted colour by colour (Gb, lane groups), the node of each
-  // permuted row (gperm), the unscaled smoother-block inverses in that order
-  // (Gd), colour c = permuted rows [gcs[c], gcs[c + 1])
-  DBsr Gb;
-  int32_t* gperm = nullptr;
-  dv4* Gd = nullptr;
-  std::vector<int64_t> gcs, gbk;     // colour row starts / block starts (+ end)
-  // point-wise multicolour GS (SMOOTHER_GS_POINT / SGS_POINT, CSR layout):
-  // A_l's rows permuted colour by colour (Gc; gperm = the row of each
-  // permuted row, gcs / gbk as above, unpadded), 1 / a_ii in that order
-  // (gdinv), the colour row starts on the device (gcs_d: the one-launch
-  // smoothing call of a small level, gsmall)
-  DCsr Gc;
-  double* gdinv = nullptr;
-  int64_t* gcs_d = nullptr;
-  bool gsmall = false;
-  // level-0 node-patch Schwarz (Schwarz_type PATCHES): A_0 as plain BSR2 in
-  // node order (Sptr, Scol, Sval: the patch rows), the patch centres colour by
-  // colour (pperm), colour c = patches [pcs[c], pcs[c + 1]), the packed upper
-  // triangles of the patch inverses (pu, stride pus doubles per patch)
-  int64_t* Sptr = nullptr;
-  int32_t* Scol = nullptr;
-  dv4* Sval = nullptr;
-  int64_t Snb = 0;
-  int32_t* pperm = nullptr;
-  double* pu = nullptr;
-  int64_t pus = 0;
-  std::vector<int64_t> pcs;
-  // level-0 seed-ring Schwarz (Schwarz_type RINGS): the blocks colour by
-  // colour (colour c = blocks [rcs[c], rcs[c + 1])), block k's members as
-  // node-interleaved dof indices 2 I + f at rmem[rmo[k] .. rmo[k + 1]), its
-  // Gauss-Jordan inverse transposed (column-major d x d) at rinv + rio[k];
-  // A_0's rows in Sptr / Scol / Sval; the rest's GS in Gb / gperm / Gd / gcs
-  // (covered dofs masked out of Gd)
-  int64_t* rmo = nullptr;
-  int32_t* rmem = nullptr;
-  int64_t* rio = nullptr;
-  double* rinv = nullptr;
-  std::vector<int64_t> rcs;
-  int64_t rnm = 0;          // members of all blocks
-  double rinv_n = 0.0;      // inverse entries of all blocks
-  // ... on the CSR layout (scalar systems, point smoothers): rmem holds plain
-  // dof indices, the member rows are A's, the rest's point-wise GS over the
-  // uncovered rows is in Gc / gperm / gdinv / gcs; per colour c the members,
-  // inverse entries and member-row entries of its blocks, as prefix sums
-  // (the byte count of a colour step)
-  std::vector<int64_t> rcm, rci, rce;
-  // coarse-grid correction scaling of the correction computed ON this level:
-  // q = A_l e, partial sums of <b, e>, <q, e>
-  double* q = nullptr;
-  double* part2 = nullptr;
-};
-
-enum OpKind { OP_CSR = 0, OP_SCALE = 1, OP_GEMV = 2, OP_AXPY = 3, OP_BSR = 4, OP_BD = 5, OP_POST = 6, OP_ILV = 7,
-              OP_GS = 8, OP_ZERO = 9, OP_DOT2 = 10, OP_CSCALE = 11, OP_PATCH = 12, OP_TAIL = 13, OP_RING = 14,
-              OP_CGS = 15,     // point-wise GS, one colour of a CSR level (csr_gs_kernel)
-              OP_CGSF = 16,    // point-wise GS, a small level's whole smoothing call (csr_gs_small_kernel)
-              OP_CRING = 17,   // one colour of a seed-ring sweep on the CSR layout (ring_csr_kernel)
-              OP_COPY = 18,    // out = x (n doubles): a rank's plain slice into its [owned | ghost] buffer
-              // the distributed PCG's kernels on Op::pcg (dpcg_*_kernel)
-              OP_PDOT = 19,    // block partials of <x, y> over the owned entries
-              OP_PSLOT = 20,   // n dots' partials -> slot [rank] of their P-vectors
-              OP_PR0 = 21,     // r = b - q (start-up)
-              OP_PINIT = 22, OP_PALPHA = 23, OP_PXR = 24, OP_PBETA = 25, OP_PD = 26 };
-// kernel classes (kernel_ms / class_bytes slots)
-enum Cls {
-  C_L0_RESID = 0,   // dominant: r = b - A0 x (once per apply)
-  C_L0_SMOOTH = 1,  // post-smooth SpMV on A0 (fused Jacobi / block Jacobi)
-  C_L0_WB = 2,      // level-0 smoother application outside an SpMV
-  C_L0_R = 3,       // level-0 restriction
-  C_L0_P = 4,       // level-0 prolongation
-  C_COARSE = 5,     // all SpMV-class launches on levels >= 1
-  C_DENSE = 6,      // coarsest dense solve
-  C_MISC = 7,       // W-cycle / maxit corrections
-  C_COMM = 8,       // multi-GPU: halo pack/unpack + RCCL exchanges
-  NCLS = 8
-};
-
-struct Op {
-  int kind = OP_CSR, epi = EPI_Y, cls = 0, tag = 1;
-  const DCsr* M = nullptr;
-  const DBsr* Mb = nullptr;
-  int64_t n = 0;
-  const double *x = nullptr, *y = nullptr, *b = nullptr, *w = nullptr;
-  const dv4* W = nullptr;
-  double* out = nullptr;
-  int64_t xs = 0, bs = 0, os = 0;   // BSR2 field strides (0 = node-major)
-  bool xfm = false;
-  int remap = 0;                    // XCD-contiguous row order (restriction ops)
-  int64_t r0 = 0, r1 = -1;          // row range [r0, r1) (half-symmetric ops, GS colours; r1 < 0: all rows)
-  const int32_t* perm = nullptr;    // GS: node of each permuted row
-  double* part = nullptr;           // DOT2 / CSCALE partial sums
-  const struct DLevel* lev = nullptr;   // PATCH: the level's patch data
-  const TOp* prog = nullptr;        // TAIL: the device op list (n ops)
-  int tail_pl = -1;                 // TAIL: the program's LDS byte offset (-1: read from global memory)
-  const DPcgCtx* pcg = nullptr;     // OP_P*: the distributed PCG plan's pointers
-  double bytes = 0.0;
-};
-
-inline int remap_of(const Op& o) { return o.remap; }
-
-struct Graph {
-  const double* r = nullptr;
-  double* z = nullptr;
-  hipGraphExec_t exec = nullptr;
-  hipGraph_t graph = nullptr;
-};
-
-// one PCG iteration captured for a solution vector x and a history length
-// (dev_pcg): reused by later solves into the same x (drivers, gamma sweeps)
-struct PcgGraph {
-  double* x = nullptr;
-  int maxiter = 0;
-  hipGraphExec_t exec = nullptr;
-  hipGraph_t graph = nullptr;
-  double* hist = nullptr;          // residuals[maxiter + 1], alphas[maxiter], betas[maxiter]
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  void release() {
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (graph) (void)hipGraphDestroy(graph);
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    if (hist) (void)raw_free(hist);
-    *this = PcgGraph();
-  }
-};
-
 }  // namespace
-
-// The memory side of a handle, single-GPU or rank: all that dalloc and the
-// layout builders need of either.  The handle's destructor frees allocs.
-struct HandleMem {
-  const Switches sw;               // the switches the handle was built with (opts.h)
-  std::vector<void*> allocs;
-  char* arena = nullptr;           // pre-reserved HBM, bump-allocated (dev_prereserve)
-  size_t arena_left = 0;
-};
-
-struct DeviceHandle : HandleMem {
-  mamg_params p;
-  explicit DeviceHandle(const Switches& s) : HandleMem{s, {}, nullptr, 0} {}
-  int device = 0;
-  bool bsr = false;
-  std::vector<DLevel> L;
-  char* arena0 = nullptr;          // the reservation's range [arena0, arena1)
-  char* arena1 = nullptr;
-  hipStream_t cap = nullptr;
-  std::vector<Graph> graphs;
-  std::vector<PcgGraph> pcgs;
-  // coarse tail (tail_kernel): first level run by it (0 = off) and the
-  // device op lists built so far, one per (b, x) entry of that level
-  int tail_level = 0;
-  std::vector<double> kregion_ms;  // select_k_region: K ms per candidate region, the one kept
-  int kregion_best = -1;
-  struct TailProg {
-    const double* b; double* x; TOp* prog; int n; double bytes; int64_t lds; bool xl; int prog_lds; bool res;
-    std::vector<int64_t> info;     // what the planner decided (dev_tail_info; mamg_test.h mamg_tail_info)
-  };
-  mutable std::vector<TailProg> tails;
-  mutable bool tail_refused = false;   // the last plan attempt met an op the tail cannot express (to_tail)
-  double* hr = nullptr;            // host-apply staging (device)
-  double* hz = nullptr;
-  double *cr = nullptr, *cz = nullptr, *cd = nullptr, *cq = nullptr;  // PCG
-  double* part = nullptr;
-  double* dres = nullptr;
-  double* hres = nullptr;          // pinned host scalar
-  double apply_bytes = 0.0;
-  double setup_ms[8] = {};         // GPU setup phase timings (dev_from_ghier)
-  double layout_ms[4] = {};        // apply-layout phases: build, K region trials, re-homing, finish (LT_*)
-  // every piece of work on the handle's scratch buffers (apply, host apply,
-  // spmv, PCG, timing) waits for this event on its stream and re-records it
-  // afterwards: work on one handle is serialized across streams
-  hipEvent_t last = nullptr;
-  ~DeviceHandle() {
-    if (last) (void)hipEventDestroy(last);
-    for (auto& g : graphs) {
-      if (g.exec) (void)hipGraphExecDestroy(g.exec);
-      if (g.graph) (void)hipGraphDestroy(g.graph);
-    }
-    for (auto& g : pcgs) g.release();
-    for (auto& t : tails) (void)raw_free(t.prog);
-    for (void* a : allocs) (void)raw_free(a);
-    if (hres) (void)hipHostFree(hres);
-    if (cap) (void)hipStreamDestroy(cap);
-  }
-};
-
-namespace {
-
-enum { LT_BUILD = 0, LT_KREGION = 1, LT_REHOME = 2, LT_FINISH = 3 };
-
-// MAMG_POISON=1 (tests): every double array a handle or the layout builder
-// allocates starts as NaN bytes instead of whatever the memory held, so a
-// read of a value nothing wrote shows in the result (index arrays are left
-// alone: a poisoned index would fault instead of showing)
-template <class T>
-void poison_doubles(const Switches& sw, T* p, size_t bytes) {
-  if constexpr (std::is_same<T, double>::value) {
-    if (sw.poison) (void)dev_memset(p, 0xff, bytes);
-  }
-}
-
-// free a handle-owned (hipMalloc) array replaced during the upload, behind
-// its last reader on the null stream (dmem.h ordered_free)
-inline void drained_free(void* p) { ordered_free(p); }
-
-// wait for the layout builder's queued work (all of it on the null stream)
-inline hipError_t null_sync() { return hipStreamSynchronize(nullptr); }
-
-// device allocation owned by a handle (single-GPU or multi-GPU: HandleMem)
-template <class T>
-int dalloc(HandleMem* h, T** p, int64_t count, std::string* err) {
-  *p = nullptr;
-  if (count <= 0) return MAMG_OK;
-  const size_t bytes = ((size_t)count * sizeof(T) + 4095) & ~(size_t)4095;
-  if (h->arena && bytes <= h->arena_left) {
-    *p = (T*)h->arena;
-    h->arena += bytes;
-    h->arena_left -= bytes;
-    poison_doubles(h->sw, *p, bytes);
-    return MAMG_OK;
-  }
-  void* q = nullptr;
-  // a very large long-lived array (the node patches' inverses: 63 GB at
-  // nrefs=6) is placed after the idle setup cache is released, so it is not
-  // laid out around the cached blocks (with them kept, the patch layout build
-  // took 2.2-2.8 s instead of 0.68 s, BENCH_r05 / profiles/r05_bench_g.json)
-  if ((size_t)count * sizeof(T) >= ((size_t)8 << 30)) tmp_trim();
-  HIPCHK(dev_malloc(&q, (size_t)count * sizeof(T)));
-  h->allocs.push_back(q);
-  *p = (T*)q;
-  poison_doubles(h->sw, *p, (size_t)count * sizeof(T));
-  return MAMG_OK;
-}
 
 // lanes per row: ~3 entries per lane (bench/spmv_micro.hip: 8 lanes best for
 // the ~30 nnz CSR rows and the ~15 block BSR rows of the level-0 operator)
@@ -3270,6 +2871,8 @@ int pick_lanes(int64_t n, int64_t nnz) {
   while (l < 64 && 3.0 * (2 * l) <= avg + 1e-9) l *= 2;
   return l;
 }
+
+namespace {
 
 int upload_csr(DeviceHandle* h, const CsrView& M, DCsr* D, int lanes, std::string* err) {
   D->n = M.n;
@@ -3306,6 +2909,8 @@ int adopt_csr(DeviceHandle* h, const DevMat& M, DCsr* D, int lanes, std::string*
   return MAMG_OK;
 }
 
+}  // namespace
+
 // lanes per node row for 2x2 blocks: ~2 blocks per lane (VL = 8 for the
 // ~15-block level-0 rows: 1.87 ms vs 2.00 ms at VL = 4, bench/spmv_micro.hip;
 // round 3 at nrefs=6: 1/4, 1/2 and 2x these lanes on the coarse levels were
@@ -3316,6 +2921,8 @@ int pick_lanes_bsr(int64_t nr, int64_t nb) {
   while (l < 64 && 2.0 * (2 * l) <= 2.0 * avg) l *= 2;
   return l;
 }
+
+namespace {
 
 // SELL-64 copy of a BSR2 matrix (host packing: convert.cpp to_sell)
 int upload_sell(HandleMem* h, const HBsr& B, DBsr* D, std::string* err) {
@@ -3344,9 +2951,11 @@ int upload_sell(HandleMem* h, const HBsr& B, DBsr* D, std::string* err) {
   return MAMG_OK;
 }
 
+}  // namespace
+
 // (also uploads a merged [P | AP] matrix: then B.ptr has 2 nr + 1 entries)
 int upload_bsr(HandleMem* h, const HBsr& B, DBsr* D, int lanes, std::string* err,
-               bool sym = false) {
+               bool sym) {
   const int64_t np = (int64_t)B.ptr.size();
   D->nr = B.nr;
   D->nc = B.nc;
@@ -3377,6 +2986,8 @@ int upload_bsr(HandleMem* h, const HBsr& B, DBsr* D, int lanes, std::string* err
   }
   return MAMG_OK;
 }
+
+namespace {
 
 // ---------------------------------------------------------------------------
 // Device-side layout construction: field-major CSR already in HBM (GPU setup
@@ -3507,6 +3118,15 @@ __global__ __launch_bounds__(256) void sym_check_kernel(int64_t nb, const dv4* _
     d |= __double_as_longlong(v[k].y) != __double_as_longlong(v[k].z);
   if (__syncthreads_or(d) && threadIdx.x == 0) atomicOr(bad, 1);
 }
+
+}  // namespace
+
+// the rank layout's launch of sym_check_kernel (dist_layout.hip), on the null stream
+void sym_check(int64_t nb, const dv4* v, int* bad) {
+  sym_check_kernel<<<std::min(nblocks(nb), SYM_CHECK_BLOCKS), 256>>>(nb, v, bad);
+}
+
+namespace {
 
 __global__ __launch_bounds__(256) void pack_sym_kernel(int64_t nb, const dv4* __restrict__ v,
                                                        double* __restrict__ out) {
@@ -3798,42 +3418,7 @@ __global__ __launch_bounds__(256) void permute_dense_kernel(int64_t n, const dou
   out[(2 * (i % nv) + i / nv) * n + (2 * (j % nv) + j / nv)] = in[t];
 }
 
-// raw device BSR2 (4 doubles per block); merged: ptr has 2 nr + 1 entries
-struct TBsr {
-  int64_t nr = 0, nc = 0, nb = 0;
-  bool merged = false;
-  int64_t* ptr = nullptr;
-  int32_t* col = nullptr;
-  dv4* val = nullptr;
-};
-
-// scoped temporaries of the layout builder, null-stream ordered (dmem.h):
-// the layout kernels that read them are queued on the null stream, and a
-// block handed out again is used only by work queued behind them
-struct TmpPool {
-  const Switches& sw;   // the owning handle's
-  std::vector<void*> v;
-  explicit TmpPool(const Switches& s) : sw(s) {}
-  ~TmpPool() {
-    for (void* p : v) tmp_free(p);
-  }
-  template <class T>
-  int alloc(T** p, int64_t count, std::string* err) {
-    void* q = nullptr;
-    HIPCHK(tmp_malloc(&q, (size_t)std::max<int64_t>(count, 1) * sizeof(T)));
-    v.push_back(q);
-    *p = (T*)q;
-    poison_doubles(sw, *p, (size_t)std::max<int64_t>(count, 1) * sizeof(T));
-    return MAMG_OK;
-  }
-  void release(void* p) {
-    for (auto& q : v)
-      if (q == p) {
-        tmp_free(q);
-        q = nullptr;
-      }
-  }
-};
+}  // namespace
 
 int dev_csr_to_bsr(TmpPool* T, const DevMat& M, int64_t nr, int64_t nc, TBsr* B, std::string* err) {
   int rc;
@@ -3899,6 +3484,8 @@ int dev_kmerge(TmpPool* T, const TBsr& P, const TBsr& Q, const double* W, TBsr* 
   HIPCHK(hipGetLastError());
   return MAMG_OK;
 }
+
+namespace {
 
 // the schedule of G 256-row blocks for plane stride S (empty: keep row order)
 std::vector<int32_t> band_sched(int64_t G, int64_t S, int nsub) {
@@ -3974,6 +3561,8 @@ int build_band_sched(HandleMem* h, const TBsr& B, DBsr* D, std::string* err) {
   return upload_sched(h, sched, &D->sched, &D->nsched, err);
 }
 
+}  // namespace
+
 // the same for the launch over rows [r0, r1) only (block b covers rows
 // r0 + 256 b ..): the multi-GPU interior run
 int build_band_sched_range(HandleMem* h, DBsr* D, int64_t r0, int64_t r1, std::string* err) {
@@ -3984,6 +3573,8 @@ int build_band_sched_range(HandleMem* h, DBsr* D, int64_t r0, int64_t r1, std::s
   D->sr1 = r1;
   return upload_sched(h, sched, &D->sched_r, &D->nsched_r, err);
 }
+
+namespace {
 
 // first column of the first non-empty row of each group of rpw rows (-1: none)
 __global__ void wg_first_col_kernel(int64_t G, int rpw, int64_t nr, const int64_t* __restrict__ ptr,
@@ -4060,6 +3651,8 @@ int build_rest_sched(HandleMem* h, TmpPool* T, DBsr* D, int64_t Sf, std::string*
   D->rsched_vl = D->lanes;
   return MAMG_OK;
 }
+
+}  // namespace
 
 // half-symmetric ELL-64 for a symmetric-block A whose owned part (columns
 // < nr) is symmetric bitwise; columns >= nr (ghosts of a rank-local A) go to
@@ -4163,7 +3756,7 @@ int upload_half_or_bsr(HandleMem* h, const HBsr& B, DBsr* D, std::string* err) {
 // upload_bsr): SELL-64 for large short-row plain matrices, symmetric-block
 // packing where every block has (0,1) == (1,0) bitwise, else 4 doubles/block
 int finalize_bsr(HandleMem* h, TmpPool* T, TBsr& B, DBsr* D, int lanes, bool sym_ok, std::string* err,
-                 bool allow_sell = true, bool allow_half = false, bool allow_msell = false) {
+                 bool allow_sell, bool allow_half, bool allow_msell) {
   int rc;
   const int64_t nr = B.nr, np = B.merged ? 2 * nr + 1 : nr + 1;
   D->nr = nr;
@@ -4261,6 +3854,8 @@ int sort_sell_slices(HandleMem* h, TmpPool* T, DBsr* D, std::string* err) {
   return MAMG_OK;
 }
 
+namespace {
+
 // SELL columns as 16-bit offsets from a per-slice base (round 6, level-0 K:
 // MAMG_K_COL16, default on).  K's columns are coarse node ids; the 64 rows of
 // a slice reach the aggregates of a few neighbouring planes, so every slice's
@@ -4329,26 +3924,6 @@ int compress_sell_cols(HandleMem* h, TmpPool* T, DBsr* D, std::string* err) {
   D->cbase = base;
   return MAMG_OK;
 }
-
-// one BSR2 level from device-resident field-major CSRs (AP.n == 0: no fusion)
-struct LevelSrc {
-  DevMat A, P, AP, R;
-  const double* W = nullptr;      // 4 nv node blocks (device)
-  const double* Ainv = nullptr;   // coarsest: n x n dof order (device)
-  const std::vector<int32_t>* seeds = nullptr;   // level 0, SCHWARZ_RINGS
-};
-
-inline bool gs_smoother(const mamg_params& p) {
-  return p.smoother == MAMG_SMOOTHER_SGS || p.smoother == MAMG_SMOOTHER_GS;
-}
-
-// smoothing step s of a sweep sequence: the Jacobi smoothers take W every
-// step; SMOOTHER_POLY takes w_1 W .. w_m W before the coarse correction and
-// w_m W .. w_1 W after it (mamg_oracle.Hierarchy.cycle), repeated per sweep
-inline int step_index(int m, int s, bool pre) {
-  const int k = s % m;
-  return pre ? k : m - 1 - k;
-}
 const dv4* step_wd(const DLevel& L, int s, bool pre) {
   return L.Wk.empty() ? L.Wd : L.Wk[step_index((int)L.Wk.size(), s, pre)];
 }
@@ -4373,6 +3948,8 @@ int poly_scaled(DeviceHandle* h, const double* W, int64_t n, std::vector<double*
   }
   return MAMG_OK;
 }
+
+}  // namespace
 
 // Jones-Plassmann colouring of the node graph of B (every node of the level;
 // jp_round_kernel rounds, one 8-byte readback each): *ca (TmpPool-owned, nr
@@ -4497,6 +4074,8 @@ int gs_layout(HandleMem* h, TmpPool* T, const TBsr& B, const double* W, const in
     T->release(q);
   return MAMG_OK;
 }
+
+namespace {
 
 // Multicolour GS layout of one level from A_l's device BSR2 B and the
 // level's (scaled) smoother blocks W (only their pattern is used: a node
@@ -4698,9 +4277,7 @@ __global__ __launch_bounds__(256) void unsplit_blocks_kernel(int64_t nbs, const 
   out[k] = dv4{a.x, a.y, b.x, b.y};
 }
 
-inline bool patch_schwarz(const mamg_params& p) {
-  return p.Schwarz_levels >= 1 && p.Schwarz_type == MAMG_SCHWARZ_PATCHES;
-}
+}  // namespace
 
 // the distance-3 colouring of the node graph of B (c[I], device, from T), its
 // colour count bound check and the longest row (node patches: <= 16 nodes)
@@ -4768,6 +4345,8 @@ int patch_colour(TmpPool* T, const TBsr& B, int16_t** cout, int* maxlen, std::st
   return MAMG_OK;
 }
 
+namespace {
+
 // Node-patch Schwarz data of level 0 from A_0's device BSR2 B: the distance-3
 // colouring (patch_colour), patches sorted by colour (stable radix sort,
 // ascending centre within a colour), A_0 kept as plain BSR2 for the patch
@@ -4820,10 +4399,6 @@ int build_patches(DeviceHandle* h, TmpPool* T, const TBsr& B, DLevel* D, std::st
   HIPCHK(hipMemcpy(hf, flags, 4 * sizeof(int), hipMemcpyDeviceToHost));
   if (hf[2]) { *err = "node patches: a patch matrix is not SPD (non-positive Gauss-Jordan pivot)"; return MAMG_ERR_SETUP; }
   return MAMG_OK;
-}
-
-inline bool rings_schwarz(const mamg_params& p) {
-  return p.Schwarz_levels >= 1 && p.Schwarz_type == MAMG_SCHWARZ_RINGS;
 }
 
 // The layout-independent half of the seed-ring Schwarz data of level 0
@@ -5078,6 +4653,8 @@ double bsr_bytes(const DBsr& M, int epi) {
   return b;
 }
 
+}  // namespace
+
 Op csr_op(const DCsr& M, int epi, int cls, int tag, const double* x, const double* y,
           const double* b, const double* w, double* out) {
   Op o;
@@ -5106,6 +4683,8 @@ Op post_op(const DBsr& M, const double* r1, const dv4* W, int cls, int tag, cons
   return o;
 }
 
+namespace {
+
 Op gemv_op(const DLevel& L, const double* b, double* out) {
   Op o;
   o.kind = OP_GEMV; o.cls = C_DENSE; o.n = L.n; o.x = b; o.w = L.Ainv; o.out = out;
@@ -5113,11 +4692,15 @@ Op gemv_op(const DLevel& L, const double* b, double* out) {
   return o;
 }
 
+}  // namespace
+
 Op axpy_op(int64_t n, const double* e, double* x) {
   Op o;
   o.kind = OP_AXPY; o.cls = C_MISC; o.n = n; o.x = e; o.out = x; o.bytes = 24.0 * n;
   return o;
 }
+
+namespace {
 
 void scale_ops(const DeviceHandle* h, int lc, std::vector<Op>* ops);
 
@@ -5313,22 +4896,10 @@ void cycle_ops_csr(const DeviceHandle* h, int l, const double* b, double* xout, 
   }
 }
 
+}  // namespace
+
 // ---- BSR2 layout.  b / xout of level 0 are the caller's field-major vectors
 // (stride nv0); all other vectors are node-interleaved (stride 0).
-// one multicolour GS sweep (colours ascending if fwd, else descending) in place on x
-template <class LV>
-Op gs_op(const LV& L, int c, double* x, const double* b, int64_t bs, int cls) {
-  Op o;
-  o.kind = OP_GS; o.cls = cls; o.Mb = &L.Gb; o.perm = L.gperm; o.W = L.Gd;
-  o.x = x; o.out = x; o.b = b; o.bs = bs;
-  o.r0 = L.gcs[c]; o.r1 = L.gcs[c + 1]; o.n = o.r1 - o.r0;
-  const double rows = (double)o.n, ncol = (double)(L.gcs.size() - 1);
-  // blocks + pointers + perm + D + b + own x read/write + the gathered x
-  // (every node's pair once per sweep, spread over the colours)
-  o.bytes = (L.Gb.sym ? 28.0 : 36.0) * (double)(L.gbk[c + 1] - L.gbk[c]) + 8.0 * (rows + 1) + 4.0 * rows +
-            32.0 * rows + 16.0 * rows + 32.0 * rows + 16.0 * (double)L.Gb.nc / ncol;
-  return o;
-}
 
 // one colour of a node-patch sweep: per patch its packed inverse, its node
 // rows (blocks + pointers), b and x read/write for its dofs, the gathered x
@@ -5357,6 +4928,8 @@ Op ring_op(const DLevel& L, int c, double* x, const double* b, int64_t bs, int c
   o.bytes = frac * 8.0 * L.rinv_n + m * (bpr * 36.0 + 16.0 + 4.0 + 8.0 + 16.0 + bpr * 16.0) + 16.0 * o.n;
   return o;
 }
+
+namespace {
 
 void ring_sweep_ops(const DLevel& L, bool fwd, double* x, const double* b, int64_t bs, int cls, std::vector<Op>* ops) {
   const int nc = (int)L.rcs.size() - 1;
@@ -5433,9 +5006,6 @@ void cycle_ops_bsr(const DeviceHandle* h, int l, const double* b, int64_t bs, do
                    int64_t os, std::vector<Op>* ops, bool tail_ok = true, bool x1_ready = false);
 
 static_assert(sizeof(TOp) % 8 == 0, "TOp is copied into LDS as 8-byte words");
-// mamg_tail_info's values (include/mamg_test.h): the header, then (n, matrix in LDS) per T_GEMV
-enum TailInfo { TI_PROGS = 0, TI_LEVEL, TI_OPS, TI_LDS, TI_XL, TI_RES, TI_PROG_LDS, TI_ROWS, TI_NOV, TI_VEC_LDS,
-                TI_VEC_GLOBAL, TI_REFUSED, TI_GEMVS, TI_OPS_RES, TI_OPS_BSR, TI_MAX_VL, TI_REPLANNED, TAIL_INFO_HEAD };
 constexpr int64_t TAIL_LDS_MAX = 160 * 1024 - 1024;   // gfx950: 160 KB per workgroup, minus the static arrays
 
 // LDS residency of a coarse-tail program (see T_COPY): every work vector of
@@ -6090,12 +5660,16 @@ bool launch_kvariant(const Op& o, hipStream_t s) {
   }
 }
 
+}  // namespace
+
 // whether the level-0 K launch honours an op's row range [r0, r1) (the
 // multi-lane SELL and lane-group kernels do; launch_sell_u, reached only with
 // the diagnosis build's MAMG_K_VARIANT=1 on a K not split in two streams,
 // does not): the distributed apply splits K around the coarse halo only then
 // 
 bool k_ranges_ok(const DBsr& K) { return !K.sell || !(K.kvar == 1 && K.split != 2); }
+
+namespace {
 
 template <bool XFM, bool SYM, int TAG, class VT = double>
 void launch_sell_x(const Op& o, hipStream_t s) {
@@ -6274,6 +5848,8 @@ void launch_cgs(const Op& o, hipStream_t s) {
   }
 }
 
+}  // namespace
+
 void launch(const Op& o, hipStream_t s) {
   switch (o.kind) {
     case OP_CGS:
@@ -6374,6 +5950,8 @@ void launch(const Op& o, hipStream_t s) {
       break;
   }
 }
+
+namespace {
 
 // handle ordering (DeviceHandle::last)
 int order_begin(DeviceHandle* h, hipStream_t s, std::string* err) {
@@ -7067,6 +6645,8 @@ int dev_level_format(const DeviceHandle* h, int level) {
          (L.KPb.col16 ? MAMG_FMT_K_COL16 : 0);
 }
 
+namespace {
+
 // ---------------------------------------------------------------------------
 // fp32 storage of the operators the cycle streams (mamg_set_cycle_storage,
 // DESIGN.md section 4.7).  The fp32 arrays keep the element layout of the fp64
@@ -7074,7 +6654,6 @@ int dev_level_format(const DeviceHandle* h, int level) {
 // pair of kernels serves every value-array shape: general, SYM, half-symmetric
 // upper part, SELL padding and both split layouts.
 // ---------------------------------------------------------------------------
-namespace {
 
 constexpr unsigned F32_BLOCKS = 4096;   // grid-stride passes over a value array
 
@@ -7098,25 +6677,7 @@ __global__ __launch_bounds__(256) void f32_convert_kernel(int64_t n, const doubl
 
 inline unsigned f32_grid(int64_t n) { return (unsigned)std::min<int64_t>(F32_BLOCKS, (n + 255) / 256); }
 
-// stored values of an operator's main array (rehome_bsr's count)
-inline int64_t value_count(const DBsr& M) {
-  if (M.nr == 0 || !M.val) return 0;
-  const int64_t slots = (M.sell || M.half) ? M.nbs : M.nb;
-  return slots * ((M.sym || M.half) ? 3 : 4);
-}
-// stored values of a half-symmetric operator's ghost part (gval: the diagonal
-// pairs of its ngs slots, then their off-diagonals)
-inline int64_t ghost_value_count(const DBsr& M) { return (M.half && M.gval) ? 3 * M.ngs : 0; }
-
-// one value array to store fp32 (narrow_values)
-struct NarrowJob {
-  DBsr* src;        // the operator whose fp64 values are read
-  DBsr* dst;        // the operator that reads the fp32 copy (src itself, or level 0's Ac)
-  bool ghost;       // the half-symmetric ghost part (gval) instead of the main array
-  float* val = nullptr;
-  const double* from() const { return ghost ? src->gval : src->val; }
-  int64_t count() const { return ghost ? ghost_value_count(*src) : value_count(*src); }
-};
+}  // namespace
 
 // fp32 copies of the jobs' value arrays (either handle type).  1. every array
 // is checked before any is converted: a refusal leaves the handle untouched;
@@ -7124,9 +6685,8 @@ struct NarrowJob {
 // 3. drop_cached(): the caller drops what holds the fp64 op list; 4. the copies
 // are swapped in (a dst other than its src first takes src's layout: level 0's
 // Ac shares A's index arrays); release() gets each replaced original.
-template <class Drop, class Release>
-int narrow_values(std::vector<NarrowJob>& jobs, std::vector<void*>* allocs, Drop drop_cached, Release release,
-                  std::string* err) {
+int narrow_values(std::vector<NarrowJob>& jobs, std::vector<void*>* allocs, const std::function<void()>& drop_cached,
+                  const std::function<void(void*)>& release, std::string* err) {
   int* bad = nullptr;
   HIPCHK(raw_malloc((void**)&bad, sizeof(int), "tmp"));
   int hbad = 0;
@@ -7169,6 +6729,8 @@ int narrow_values(std::vector<NarrowJob>& jobs, std::vector<void*>* allocs, Drop
   }
   return MAMG_OK;
 }
+
+namespace {
 
 // a handle-owned array that nothing reads any more (the caller has waited)
 void release_owned(DeviceHandle* h, void* old) {
@@ -7307,7 +6869,6 @@ int dev_spmv(DeviceHandle* h, const double* d_x, double* d_y, void* stream, std:
   HIPCHK(hipGetLastError());
   return order_end(h, (hipStream_t)stream, err);
 }
-
 
 int dev_pcg(DeviceHandle* h, const double* d_b, double* d_x, double tol, int maxiter,
             int relativeconv, double* residuals, double* alphas, double* betas, int* niters,
@@ -7592,26 +7153,7 @@ int dev_time_apply(DeviceHandle* h, const double* d_r, double* d_z, int reps, in
   return MAMG_OK;
 }
 
-}  // namespace mamg
-
-// ===========================================================================
-// Multi-GPU V-cycle (row-partitioned, RCCL over xGMI).  Plan: dist.cpp.
-// ===========================================================================
-#include <rccl/rccl.h>
-
-#include "dist.h"
-
-namespace mamg {
 namespace {
-
-#define NCCLCHK(expr)                                                                \
-  do {                                                                               \
-    ncclResult_t r_ = (expr);                                                        \
-    if (r_ != ncclSuccess) {                                                         \
-      *err = std::string(#expr) + ": " + ncclGetErrorString(r_);                     \
-      return MAMG_ERR_HIP;                                                           \
-    }                                                                                \
-  } while (0)
 
 __global__ __launch_bounds__(256) void pack2_kernel(int64_t n, const int64_t* __restrict__ idx,
                                                     const double* __restrict__ x,
@@ -7665,2351 +7207,28 @@ __global__ __launch_bounds__(256) void addidx1_kernel(int64_t n, const int64_t* 
   }
 }
 
+}  // namespace
+
 // the exchange kernels of a handle with w dofs per node (2: the double2
 // kernels of the nodal path, 1: the scalar ones)
-inline void pack_w(int w, int64_t n, const int64_t* idx, const double* x, double* buf, hipStream_t s) {
+void pack_w(int w, int64_t n, const int64_t* idx, const double* x, double* buf, hipStream_t s) {
   if (w == 2) pack2_kernel<<<nblocks(n), 256, 0, s>>>(n, idx, x, buf);
   else pack1_kernel<<<nblocks(n), 256, 0, s>>>(n, idx, x, buf);
 }
-inline void unpack_w(int w, int64_t n, const int64_t* idx, int64_t nloc, const double* buf, double* x, hipStream_t s) {
+void unpack_w(int w, int64_t n, const int64_t* idx, int64_t nloc, const double* buf, double* x, hipStream_t s) {
   if (w == 2) unpack2_kernel<<<nblocks(n), 256, 0, s>>>(n, idx, nloc, buf, x);
   else unpack1_kernel<<<nblocks(n), 256, 0, s>>>(n, idx, nloc, buf, x);
 }
-inline void addidx_w(int w, int64_t n, const int64_t* idx, const double* buf, double* x, hipStream_t s) {
+void addidx_w(int w, int64_t n, const int64_t* idx, const double* buf, double* x, hipStream_t s) {
   if (w == 2) addidx2_kernel<<<nblocks(n), 256, 0, s>>>(n, idx, buf, x);
   else addidx1_kernel<<<nblocks(n), 256, 0, s>>>(n, idx, buf, x);
 }
 
-struct DDLevel {
-  int64_t nv = 0, nloc = 0, ng = 0;
-  bool replicated = false, coarsest = false;
-  DBsr A, P, R;
-  // fp32 cycle storage (dist_set_cycle_storage), level 0 only: A_loc as the
-  // cycle reads it -- A's layout with fp32 copies of val and, half-symmetric,
-  // gval (Ac.f32), the index arrays shared; A itself stays fp64 for the Krylov
-  // operator (dspmv_ops).  On the other narrowed levels A's values are
-  // replaced in place.
-  DBsr Ac;
-  int storage = 0;         // mamg_dist_level_storage bits: 1 A, 2 K / P, 4 R stored fp32
-  // scalar (CSR) level: A_loc, P_loc, Rp_loc, on level 0 with seed blocks the
-  // owned rows of WB (else the winv slice); POLY: the step smoothers w_k WB
-  // (sharing WB's pattern) or w_k winv; vectors hold nloc + ng doubles
-  DCsr cA, cP, cR, cWB;
-  std::vector<DCsr> cWBk;
-  double* winv = nullptr;
-  std::vector<double*> winvk;
-  double* gb = nullptr;    // level 0 with WB: b over [owned | ghost] (X = WB_loc b reads b's ghosts)
-  DBsr PA;                 // post fusion: merged [P_loc | AP_loc]
-  DBsr K;                  // post fusion: K_loc = P_loc - W (AP)_loc (default)
-  dv4* W = nullptr;
-  std::vector<dv4*> Wk;    // SMOOTHER_POLY step smoothers w_k W (empty: Jacobi)
-  double* Ainv = nullptr;
-  double *b = nullptr, *x = nullptr, *t = nullptr, *t2 = nullptr, *r = nullptr;
-  double *c = nullptr, *e = nullptr;     // W-cycle: second visit's right-hand side / correction
-  double *q = nullptr, *part2 = nullptr; // coarse scaling of this level's correction: A e, dot partials
-  double* spx = nullptr;   // level 0: [owned | ghost] operand of the standalone SpMV
-  int64_t ib0 = 0, ib1 = 0;  // longest run of A_loc rows without ghost columns
-  int64_t kb0 = 0, kb1 = 0;  // the same for K (coarse ghost columns), bounds multiples of K_ROWS_ALIGN or nloc
-  int64_t* send_idx = nullptr;
-  double *sendbuf = nullptr, *recvbuf = nullptr;
-  std::vector<int64_t> send_off, ghost_off;
-  // multicolour GS (SMOOTHER_GS / SGS): the owned rows permuted colour by
-  // colour (gs_layout; the level's global colouring, so every rank has the
-  // same colours), and each colour's halo: its send nodes and ghost slots per
-  // peer, offsets cs_off / cg_off[c (P + 1) + q]
-  DBsr Gb;
-  int32_t* gperm = nullptr;
-  dv4* Gd = nullptr;
-  std::vector<int64_t> gcs, gbk;
-  int64_t *csend_idx = nullptr, *cghost_idx = nullptr;
-  std::vector<int64_t> cs_off, cg_off;
-  // level-0 node-patch Schwarz on N ranks (dist_patches): the ghost region is
-  // the 3-hop ball of the owned nodes; the rank computes every patch centred
-  // within 1 hop of its nodes (pl: the patch rows of the nodes within 2 hops,
-  // columns local in the global column order, centres colour by colour,
-  // inverses); cs_off / cg_off above hold each colour's halo of the nodes
-  // its patches write; pb = b interleaved over [owned | ghost]
-  bool patches = false;
-  DLevel pl;
-  int32_t* Sgcol = nullptr;
-  double* pb = nullptr;
-  // level-0 seed-ring Schwarz on N ranks (dist_rings): the rank's blocks
-  // (rl: rcs, rmo, rmem, rio, rinv; the block rows Sptr / Scol / Sval over
-  // the local nodes), the ring colours' halos at cs_off / cg_off indices
-  // [0, nrc), the rest GS's colours at [nrc, nrc + gcs.size() - 1)
-  bool rings = false;
-  int nrc = 0;
-  DLevel rl;
-  uint8_t* rcov = nullptr;   // covered dofs of the owned nodes (bit f)
-};
-
-// D_CHALO: the forward halo of one colour's nodes (after that colour's GS step)
-enum DKind { D_OP = 0, D_HALO = 1, D_REVERSE = 2, D_ALLREDUCE = 3, D_OVERLAP = 4, D_CHALO = 5 };
-
-struct DOp {
-  int dk = D_OP;
-  Op op;
-  int level = 0;
-  int colour = 0;            // D_CHALO
-  double* buf = nullptr;
-  int64_t count = 0;
-  double bytes = 0.0;
-  int cls = 0;
-};
-
-// A_loc as the cycle reads it: level 0's fp32 copy once the rank is narrowed
-inline const DBsr& dcyc_A(const DDLevel& D) { return D.Ac.f32 ? D.Ac : D.A; }
-
-}  // namespace
-
-struct DistHandle : HandleMem {
-  mamg_params p;
-  explicit DistHandle(const Switches& s) : HandleMem{s, {}, nullptr, 0} {}
-  int rank = 0, nranks = 1, device = 0;
-  int w = 2;                           // dofs per node: 2 nodal (BSR2), 1 scalar (CSR)
-  ncclComm_t comm = nullptr;
-  std::vector<DDLevel> L;
-  double apply_bytes = 0.0;
-  int64_t nv0 = 0, o0 = 0, o1 = 0;
-  bool dry = false;                    // MAMG_DIST_TEST=dry: virtual rank skips its exchanges (timing only)
-  hipStream_t side = nullptr;          // stream of the interior rows
-  hipEvent_t ev_in = nullptr, ev_out = nullptr;
-  hipEvent_t last = nullptr;           // recorded after every apply / spmv / timing (dist_destroy waits)
-  // host-staged exchange backend (mamg_dist_set_exchange): pinned staging
-  // per level (sends, ghost payloads, receives of the reverse-add) and one
-  // all-reduce buffer
-  bool host_ex = false;
-  mamg_exchange ex{};
-  std::vector<double*> hsend, hghost, hrecv;
-  double* hred = nullptr;
-  std::vector<void*> pinned;
-  // the apply replayed as a hipGraph (dist_apply_graph): one per (r, z) pair,
-  // captured on `cap` with the RCCL calls inside; graph_err set when a
-  // capture failed (the handle then stays eager)
-  struct Graph {
-    const double* r;
-    double* z;
-    hipGraph_t g;
-    hipGraphExec_t e;
-  };
-  std::vector<Graph> graphs;
-  hipStream_t cap = nullptr;
-  std::string graph_err;
-  void drop_graphs() {
-    for (auto& g : graphs) {
-      (void)hipGraphExecDestroy(g.e);
-      (void)hipGraphDestroy(g.g);
-    }
-    graphs.clear();
-  }
-  // device-resident PCG (dist_pcg): r, z, d, q of w * nloc
-  // doubles, the dots' block partials and P-vectors, the state with its
-  // pinned mirror (two slots per rank whose state is read here), and one
-  // plan per (x, maxiter, stop_type): histories, the ops' context and, on
-  // an RCCL or single-rank handle, the captured iteration
-  double *cr = nullptr, *cz = nullptr, *cd = nullptr, *cq = nullptr, *ppart = nullptr, *pv = nullptr;
-  DPcgState* pst = nullptr;
-  DPcgState* hst = nullptr;
-  int hst_ranks = 0;
-  struct PcgPlan {
-    std::unique_ptr<DPcgCtx> c;
-    double* hist = nullptr;            // residuals, ||r||, alphas, betas
-    hipGraph_t g = nullptr;
-    hipGraphExec_t e = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    void release() {
-      if (e) (void)hipGraphExecDestroy(e);
-      if (g) (void)hipGraphDestroy(g);
-      for (hipEvent_t v : ev) if (v) (void)hipEventDestroy(v);
-      if (hist) (void)raw_free(hist);
-      e = nullptr; g = nullptr; hist = nullptr; ev[0] = ev[1] = nullptr;
-    }
-  };
-  std::vector<PcgPlan> pcgs;
-  std::string pcg_graph_err;           // why the iteration runs eagerly on this handle
-  ~DistHandle() {
-    if (last) (void)hipEventSynchronize(last);
-    drop_graphs();
-    for (auto& q : pcgs) q.release();
-    if (hst) (void)hipHostFree(hst);
-    if (cap) (void)hipStreamDestroy(cap);
-    for (void* q : pinned) (void)hipHostFree(q);
-    if (ev_in) (void)hipEventDestroy(ev_in);
-    if (ev_out) (void)hipEventDestroy(ev_out);
-    if (last) (void)hipEventDestroy(last);
-    if (side) (void)hipStreamDestroy(side);
-    for (void* a : allocs) (void)raw_free(a);
-    if (comm) (void)ncclCommDestroy(comm);
-  }
-};
-
-namespace {
-
-template <class T>
-int ddalloc(DistHandle* h, T** p, int64_t count, std::string* err) {
-  *p = nullptr;
-  if (count <= 0) return MAMG_OK;
-  void* q = nullptr;
-  HIPCHK(dev_malloc(&q, (size_t)count * sizeof(T)));
-  HIPCHK(dev_memset(q, 0, (size_t)count * sizeof(T)));
-  h->allocs.push_back(q);
-  *p = (T*)q;
-  return MAMG_OK;
-}
-
-
-DOp wrap(const Op& o) {
-  DOp d;
-  d.dk = D_OP; d.op = o; d.bytes = o.bytes; d.cls = o.cls;
-  return d;
-}
-
-DOp halo_op(int level, double* x, const DDLevel& D, int cls) {
-  DOp d;
-  d.dk = D_HALO; d.level = level; d.buf = x; d.cls = cls;
-  const int64_t ns = D.send_off.empty() ? 0 : D.send_off.back();
-  d.bytes = 8.0 * ns + 16.0 * ns * 2 + 16.0 * D.ng;   // idx, pack r/w, ghost writes
-  return d;
-}
-
-// forward halo of x followed by the SpMV `op` on A_loc: with the
-// half-symmetric A, the ghost-free row run [ib0, ib1) (maybe empty) runs on the
-// side stream while the halo is in flight (one D_OVERLAP), the rest after it.
-// Every row is computed by the same kernel code either way (same bits).
-void halo_residual(const DistHandle* h, int l, double* x, const Op& op, std::vector<DOp>* ops) {
-  const DDLevel& D = h->L[l];
-  if (!(h->sw.overlap && D.A.half)) {
-    ops->push_back(halo_op(l, x, D, C_COMM));
-    ops->push_back(wrap(op));
-    return;
-  }
-  const double f = (double)(D.ib1 - D.ib0) / (double)std::max<int64_t>(D.nloc, 1);
-  DOp ov = halo_op(l, x, D, op.cls);   // timed and counted with the SpMV's class
-  ov.dk = D_OVERLAP;
-  ov.op = op;
-  ov.op.r0 = D.ib0;
-  ov.op.r1 = D.ib1;
-  ov.op.bytes = op.bytes * f;
-  ov.bytes += ov.op.bytes;
-  ops->push_back(ov);
-  const int64_t lo[2] = {0, D.ib1}, hi[2] = {D.ib0, D.nloc};
-  for (int k = 0; k < 2; ++k) {   // both always emitted (possibly empty): one schedule on every rank
-    Op b = op;
-    b.r0 = lo[k];
-    b.r1 = hi[k];
-    b.bytes = op.bytes * (double)std::max<int64_t>(hi[k] - lo[k], 0) / (double)std::max<int64_t>(D.nloc, 1);
-    ops->push_back(wrap(b));
-  }
-}
-
-// coarse-grid correction scaling of level lc's correction C.x against C.b on
-// N ranks: halo of C.x (distributed level), q = A_c x on the owned rows,
-// partial sums of <b, x>, <q, x> over the owned rows, one all-reduce of the
-// partials (distributed level), alpha = num / den on every rank, x <- alpha x
-// on the owned rows and the ghosts (so the post step needs no second halo)
-void dscale_ops(const DistHandle* h, int lc, std::vector<DOp>* ops) {
-  const DDLevel& C = h->L[lc];
-  const Op q = bsr_op(C.A, EPI_Y, C_MISC, 1, C.x, 0, nullptr, nullptr, 0, nullptr, C.q, 0);
-  if (C.replicated) ops->push_back(wrap(q)); else halo_residual(h, lc, C.x, q, ops);
-  Op d;
-  d.kind = OP_DOT2; d.cls = C_MISC; d.n = 2 * C.nloc; d.b = C.b; d.x = C.x; d.y = C.q; d.part = C.part2;
-  d.bytes = 24.0 * d.n;
-  ops->push_back(wrap(d));
-  if (!C.replicated) {
-    DOp a;
-    a.dk = D_ALLREDUCE; a.cls = C_COMM; a.buf = C.part2; a.count = 2 * SCALE_BLOCKS; a.bytes = 16.0 * SCALE_BLOCKS;
-    ops->push_back(a);
-  }
-  Op sc;
-  sc.kind = OP_CSCALE; sc.cls = C_MISC; sc.n = 2 * (C.nloc + C.ng); sc.part = C.part2; sc.out = C.x;
-  sc.bytes = 16.0 * sc.n;
-  ops->push_back(wrap(sc));
-}
-
-void dcycle_ops(const DistHandle* h, int l, const double* b, int64_t bs, double* xout, int64_t os,
-                std::vector<DOp>* ops);
-
-// coarse-grid correction of level l from its residual D.r: partial
-// restriction, reverse-add (or all-reduce into a replicated level), the
-// coarse cycle (W: twice), scaling, and the halo of the correction C.x
-// (left to the caller when defer_halo: it overlaps that halo with K)
-void dcoarse_ops(const DistHandle* h, int l, std::vector<DOp>* ops, bool defer_halo = false) {
-  const DDLevel& D = h->L[l];
-  const DDLevel& C = h->L[l + 1];
-  const bool l0 = l == 0;
-  const int tagA = l0 ? 0 : 1;
-  ops->push_back(wrap(bsr_op(D.R, EPI_Y, l0 ? C_L0_R : C_COARSE, tagA, D.r, 0, nullptr, nullptr, 0,
-                             nullptr, C.b, 0)));
-  ops->back().op.remap = 1;
-  if (!D.replicated) {
-    DOp d;
-    d.cls = C_COMM;
-    if (C.replicated) {
-      d.dk = D_ALLREDUCE; d.buf = C.b; d.count = 2 * C.nv; d.bytes = 16.0 * C.nv * 2;
-    } else {
-      d.dk = D_REVERSE; d.level = l + 1; d.buf = C.b;
-      const int64_t ns = C.send_off.back();
-      d.bytes = 16.0 * C.ng + 16.0 * ns * 3 + 8.0 * ns;
-    }
-    ops->push_back(d);
-  }
-  dcycle_ops(h, l + 1, C.b, 0, C.x, 0, ops);
-  if (h->p.cycle_type == MAMG_W_CYCLE && !C.coarsest) {   // second visit on the updated residual
-    const Op res = bsr_op(C.A, EPI_RESID, C_MISC, 1, C.x, 0, nullptr, C.b, 0, nullptr, C.c, 0);
-    if (C.replicated) ops->push_back(wrap(res)); else halo_residual(h, l + 1, C.x, res, ops);
-    dcycle_ops(h, l + 1, C.c, 0, C.e, 0, ops);
-    ops->push_back(wrap(axpy_op(2 * C.nloc, C.e, C.x)));
-  }
-  if (h->p.coarse_scaling) dscale_ops(h, l + 1, ops);      // ghosts of C.x scaled too
-  else if (!C.replicated && !defer_halo) ops->push_back(halo_op(l + 1, C.x, C, C_COMM));
-}
-
-// level 0's K with the coarse-e halo in flight: rows [kb0, kb1) (no coarse
-// ghost columns) on the side stream during the halo (one D_OVERLAP), the
-// rest after it; the same kernel code computes every row either way
-void k_overlap(const DistHandle* h, const Op& k, std::vector<DOp>* ops) {
-  const DDLevel& D = h->L[0];
-  const DDLevel& C = h->L[1];
-  const double n = (double)std::max<int64_t>(D.nloc, 1);
-  DOp ov = halo_op(1, C.x, C, k.cls);   // timed and counted with K's class
-  ov.dk = D_OVERLAP;
-  ov.op = k;
-  ov.op.r0 = D.kb0;
-  ov.op.r1 = D.kb1;
-  ov.op.bytes = k.bytes * (double)(D.kb1 - D.kb0) / n;
-  ov.bytes += ov.op.bytes;
-  ops->push_back(ov);
-  const int64_t lo[2] = {0, D.kb1}, hi[2] = {D.kb0, D.nloc};
-  for (int q = 0; q < 2; ++q) {   // both always emitted (possibly empty): one schedule on every rank
-    Op b = k;
-    b.r0 = lo[q];
-    b.r1 = hi[q];
-    b.bytes = k.bytes * (double)std::max<int64_t>(hi[q] - lo[q], 0) / n;
-    ops->push_back(wrap(b));
-  }
-}
-
-DOp chalo_op(int level, int c, double* x, const DDLevel& D, int P) {
-  DOp d;
-  d.dk = D_CHALO; d.level = level; d.colour = c; d.buf = x; d.cls = C_COMM;
-  const int64_t ns = D.cs_off[(size_t)(c + 1) * (P + 1) - 1] - D.cs_off[(size_t)c * (P + 1)];
-  const int64_t ng = D.cg_off[(size_t)(c + 1) * (P + 1) - 1] - D.cg_off[(size_t)c * (P + 1)];
-  d.bytes = 8.0 * ns + 32.0 * ns + 8.0 * ng + 32.0 * ng;   // indices, pack, unpack
-  return d;
-}
-
-// one multicolour GS sweep on the owned rows, each colour's step followed by
-// that colour's halo so the next colour reads current ghosts; every rank
-// emits the same exchanges, also for colours it has no rows of
-void dgs_sweep(const DistHandle* h, int l, bool fwd, double* x, const double* b, int64_t bs, int cls,
-               std::vector<DOp>* ops) {
-  const DDLevel& D = h->L[l];
-  const int nc = (int)D.gcs.size() - 1;
-  for (int k = 0; k < nc; ++k) {
-    const int c = fwd ? k : nc - 1 - k;
-    ops->push_back(wrap(gs_op(D, c, x, b, bs, cls)));   // empty here: not launched (same schedule on every rank)
-    if (!D.replicated) ops->push_back(chalo_op(l, c, x, D, h->nranks));
-  }
-}
-
-// multi-GPU cycle with multicolour GS / SGS (cycle_ops_bsr's GS branch): from
-// x = 0, pre sweeps, residual (ghosts current), coarse correction, x += P e,
-// halo, post sweeps; X holds [owned | ghost]
-void dcycle_gs(const DistHandle* h, int l, const double* b, int64_t bs, double* xout, int64_t os,
-               std::vector<DOp>* ops) {
-  const DDLevel& D = h->L[l];
-  const DDLevel& C = h->L[l + 1];
-  const bool l0 = l == 0;
-  const int tagA = l0 ? 0 : 1;
-  const int clsS = l0 ? C_L0_SMOOTH : C_COARSE;
-  const int clsW = l0 ? C_L0_WB : C_COARSE;
-  const bool sgs = h->p.smoother == MAMG_SMOOTHER_SGS;
-  double* X = os == 0 ? xout : D.t;
-  {
-    Op z;
-    z.kind = OP_ZERO; z.cls = clsW; z.n = 2 * (D.nloc + D.ng); z.out = X; z.bytes = 8.0 * z.n;
-    ops->push_back(wrap(z));
-  }
-  for (int s = 0; s < h->p.presmooth_iter; ++s) {
-    dgs_sweep(h, l, true, X, b, bs, clsS, ops);
-    if (sgs) dgs_sweep(h, l, false, X, b, bs, clsS, ops);
-  }
-  ops->push_back(wrap(bsr_op(D.A, EPI_RESID, l0 ? C_L0_RESID : C_COARSE, tagA, X, 0, nullptr, b, bs, nullptr,
-                             D.r, 0)));
-  dcoarse_ops(h, l, ops);
-  ops->push_back(wrap(bsr_op(D.P, EPI_YADD, l0 ? C_L0_P : C_COARSE, tagA, C.x, 0, X, nullptr, 0, nullptr, X, 0)));
-  if (!D.replicated) ops->push_back(halo_op(l, X, D, C_COMM));
-  for (int s = 0; s < h->p.postsmooth_iter; ++s) {
-    if (sgs) dgs_sweep(h, l, true, X, b, bs, clsS, ops);
-    dgs_sweep(h, l, false, X, b, bs, clsS, ops);
-  }
-  if (X != xout) {
-    Op o;
-    o.kind = OP_ILV; o.epi = 1; o.cls = clsW; o.n = D.nloc; o.b = X; o.out = xout; o.os = os;
-    o.bytes = 32.0 * D.nloc;
-    ops->push_back(wrap(o));
-  }
-}
-
-// one node-patch sweep of level 0 on N ranks: per colour the rank's patches
-// of that colour, then that colour's halo (the written nodes within 3 hops);
-// every rank emits every colour's exchange, also without patches of its own
-void dpatch_sweep(const DistHandle* h, bool fwd, double* x, std::vector<DOp>* ops) {
-  const DDLevel& D = h->L[0];
-  const int nc = (int)D.pl.pcs.size() - 1;
-  for (int k = 0; k < nc; ++k) {
-    const int c = fwd ? k : nc - 1 - k;
-    ops->push_back(wrap(patch_op(D.pl, c, x, D.pb, 0, C_L0_SMOOTH)));   // empty: not launched
-    ops->push_back(chalo_op(0, c, x, D, h->nranks));
-  }
-}
-
-// multi-GPU level-0 cycle with the node-patch Schwarz (cycle_ops_bsr's
-// patch branch): b interleaved over [owned | ghost] + its halo; x = 0; pre
-// sweeps forward then backward; residual (ghosts current); the coarse
-// correction; x += P e and its halo; post sweeps forward then backward
-void dcycle_patch(const DistHandle* h, const double* b, int64_t bs, double* xout, int64_t os,
-                  std::vector<DOp>* ops) {
-  const DDLevel& D = h->L[0];
-  const DDLevel& C = h->L[1];
-  double* X = D.t;
-  {
-    Op o;
-    o.kind = OP_ILV; o.cls = C_L0_WB; o.n = D.nloc; o.b = b; o.bs = bs; o.out = D.pb;
-    o.bytes = 32.0 * D.nloc;
-    ops->push_back(wrap(o));
-    ops->push_back(halo_op(0, D.pb, D, C_COMM));
-    Op z;
-    z.kind = OP_ZERO; z.cls = C_L0_WB; z.n = 2 * (D.nloc + D.ng); z.out = X; z.bytes = 8.0 * z.n;
-    ops->push_back(wrap(z));
-  }
-  for (int s = 0; s < h->p.presmooth_iter; ++s) {
-    dpatch_sweep(h, true, X, ops);
-    dpatch_sweep(h, false, X, ops);
-  }
-  ops->push_back(wrap(bsr_op(D.A, EPI_RESID, C_L0_RESID, 0, X, 0, nullptr, b, bs, nullptr, D.r, 0)));
-  dcoarse_ops(h, 0, ops);
-  ops->push_back(wrap(bsr_op(D.P, EPI_YADD, C_L0_P, 0, C.x, 0, X, nullptr, 0, nullptr, X, 0)));
-  ops->push_back(halo_op(0, X, D, C_COMM));
-  for (int s = 0; s < h->p.postsmooth_iter; ++s) {
-    dpatch_sweep(h, true, X, ops);
-    dpatch_sweep(h, false, X, ops);
-  }
-  Op o;
-  o.kind = OP_ILV; o.epi = 1; o.cls = C_L0_WB; o.n = D.nloc; o.b = X; o.out = xout; o.os = os;
-  o.bytes = 32.0 * D.nloc;
-  ops->push_back(wrap(o));
-}
-
-// one symmetric level-0 seed-ring step on N ranks (the single-GPU sweep of
-// cycle_ops_bsr, mamg_oracle.rings_step): forward = ring colours ascending,
-// then the rest's GS colours ascending; backward = the rest descending, then
-// the rings descending; each colour's step followed by its halo (every rank
-// emits every exchange, also for colours it has no work in)
-void dring_sweep(const DistHandle* h, bool fwd, double* x, std::vector<DOp>* ops) {
-  const DDLevel& D = h->L[0];
-  const int nrc = D.nrc, ngc = (int)D.gcs.size() - 1, P = h->nranks;
-  auto rings = [&](bool f) {
-    for (int k = 0; k < nrc; ++k) {
-      const int c = f ? k : nrc - 1 - k;
-      ops->push_back(wrap(ring_op(D.rl, c, x, D.pb, 0, C_L0_SMOOTH)));   // empty: not launched
-      ops->push_back(chalo_op(0, c, x, D, P));
-    }
-  };
-  auto rest = [&](bool f) {
-    for (int k = 0; k < ngc; ++k) {
-      const int c = f ? k : ngc - 1 - k;
-      ops->push_back(wrap(gs_op(D, c, x, D.pb, 0, C_L0_SMOOTH)));
-      ops->push_back(chalo_op(0, nrc + c, x, D, P));
-    }
-  };
-  if (fwd) { rings(true); rest(true); } else { rest(false); rings(false); }
-}
-
-// multi-GPU level-0 cycle with the seed-ring Schwarz (cycle_ops_bsr's ring
-// branch): b interleaved over [owned | ghost] + its halo; x = 0; pre steps
-// forward then backward; residual; the coarse correction; x += P e and its
-// halo; post steps forward then backward
-void dcycle_rings(const DistHandle* h, const double* b, int64_t bs, double* xout, int64_t os,
-                  std::vector<DOp>* ops) {
-  const DDLevel& D = h->L[0];
-  const DDLevel& C = h->L[1];
-  double* X = D.t;
-  {
-    Op o;
-    o.kind = OP_ILV; o.cls = C_L0_WB; o.n = D.nloc; o.b = b; o.bs = bs; o.out = D.pb;
-    o.bytes = 32.0 * D.nloc;
-    ops->push_back(wrap(o));
-    ops->push_back(halo_op(0, D.pb, D, C_COMM));
-    Op z;
-    z.kind = OP_ZERO; z.cls = C_L0_WB; z.n = 2 * (D.nloc + D.ng); z.out = X; z.bytes = 8.0 * z.n;
-    ops->push_back(wrap(z));
-  }
-  for (int s = 0; s < h->p.presmooth_iter; ++s) {
-    dring_sweep(h, true, X, ops);
-    dring_sweep(h, false, X, ops);
-  }
-  ops->push_back(wrap(bsr_op(D.A, EPI_RESID, C_L0_RESID, 0, X, 0, nullptr, b, bs, nullptr, D.r, 0)));
-  dcoarse_ops(h, 0, ops);
-  ops->push_back(wrap(bsr_op(D.P, EPI_YADD, C_L0_P, 0, C.x, 0, X, nullptr, 0, nullptr, X, 0)));
-  ops->push_back(halo_op(0, X, D, C_COMM));
-  for (int s = 0; s < h->p.postsmooth_iter; ++s) {
-    dring_sweep(h, true, X, ops);
-    dring_sweep(h, false, X, ops);
-  }
-  Op o;
-  o.kind = OP_ILV; o.epi = 1; o.cls = C_L0_WB; o.n = D.nloc; o.b = X; o.out = xout; o.os = os;
-  o.bytes = 32.0 * D.nloc;
-  ops->push_back(wrap(o));
-}
-
-// ---- scalar (CSR) hierarchies on N ranks: cycle_ops_csr restated with
-// exchanges.  Vectors are [owned | ghost] doubles;
-// every rank emits the same schedule whatever it owns.
-DOp halo_op1(int level, double* x, const DDLevel& D, int cls) {
-  DOp d;
-  d.dk = D_HALO; d.level = level; d.buf = x; d.cls = cls;
-  const int64_t ns = D.send_off.empty() ? 0 : D.send_off.back();
-  d.bytes = 8.0 * ns + 8.0 * ns * 2 + 8.0 * D.ng;   // idx, pack r/w, ghost writes
-  return d;
-}
-
-// forward halo of x, then the SpMV `op` on the rank-local operator.  With
-// `split` (the level-0 residual and the standalone SpMV) the longest run of
-// rows without ghost columns [ib0, ib1) (maybe empty) runs on the side stream
-// while the halo is in flight (one D_OVERLAP) and the rest after it; the same
-// kernel computes every row either way (same bits).
-void halo_csr(const DistHandle* h, int l, double* x, const Op& op, bool split, std::vector<DOp>* ops) {
-  const DDLevel& D = h->L[l];
-  if (D.replicated) { ops->push_back(wrap(op)); return; }
-  if (!(split && h->sw.overlap)) {
-    ops->push_back(halo_op1(l, x, D, C_COMM));
-    ops->push_back(wrap(op));
-    return;
-  }
-  const double n = (double)std::max<int64_t>(D.nloc, 1);
-  DOp ov = halo_op1(l, x, D, op.cls);   // timed and counted with the SpMV's class
-  ov.dk = D_OVERLAP;
-  ov.op = op;
-  ov.op.r0 = D.ib0;
-  ov.op.r1 = D.ib1;
-  ov.op.bytes = op.bytes * (double)(D.ib1 - D.ib0) / n;
-  ov.bytes += ov.op.bytes;
-  ops->push_back(ov);
-  const int64_t lo[2] = {0, D.ib1}, hi[2] = {D.ib0, D.nloc};
-  for (int k = 0; k < 2; ++k) {   // both always emitted (possibly empty): one schedule on every rank
-    Op b = op;
-    b.r0 = lo[k];
-    b.r1 = hi[k];
-    b.bytes = op.bytes * (double)std::max<int64_t>(hi[k] - lo[k], 0) / n;
-    ops->push_back(wrap(b));
-  }
-}
-
-// as dscale_ops: the dots over the owned rows, the scale over [owned | ghost]
-void dscale_csr(const DistHandle* h, int lc, std::vector<DOp>* ops) {
-  const DDLevel& C = h->L[lc];
-  halo_csr(h, lc, C.x, csr_op(C.cA, EPI_Y, C_MISC, 1, C.x, nullptr, nullptr, nullptr, C.q), false, ops);
-  Op d;
-  d.kind = OP_DOT2; d.cls = C_MISC; d.n = C.nloc; d.b = C.b; d.x = C.x; d.y = C.q; d.part = C.part2;
-  d.bytes = 24.0 * d.n;
-  ops->push_back(wrap(d));
-  if (!C.replicated) {
-    DOp a;
-    a.dk = D_ALLREDUCE; a.cls = C_COMM; a.buf = C.part2; a.count = 2 * SCALE_BLOCKS; a.bytes = 16.0 * SCALE_BLOCKS;
-    ops->push_back(a);
-  }
-  Op sc;
-  sc.kind = OP_CSCALE; sc.cls = C_MISC; sc.n = C.nloc + C.ng; sc.part = C.part2; sc.out = C.x;
-  sc.bytes = 16.0 * sc.n;
-  ops->push_back(wrap(sc));
-}
-
-// one smoothing step of a scalar level from the iterate X (not the first from
-// x = 0): halo of X, then x + w_s winv (b - A X) in one pass, or with the
-// sparse block smoother r = b - A X, halo of r, x + w_s WB_loc r
-void dsmooth_csr(const DistHandle* h, int l, const double* b, double* X, double* out, int s, bool pre,
-                 std::vector<DOp>* ops) {
-  const DDLevel& D = h->L[l];
-  const bool l0 = l == 0;
-  const int tagA = l0 ? 0 : 1, clsS = l0 ? C_L0_SMOOTH : C_COARSE, clsW = l0 ? C_L0_WB : C_COARSE;
-  const int m = smoother_steps(h->p);
-  if (D.cWB.n > 0) {
-    const DCsr& wb = D.cWBk.empty() ? D.cWB : D.cWBk[step_index(m, s, pre)];
-    halo_csr(h, l, X, csr_op(D.cA, EPI_RESID, clsS, tagA, X, nullptr, b, nullptr, D.r), false, ops);
-    halo_csr(h, l, D.r, csr_op(wb, EPI_YADD, clsW, tagA, D.r, X, nullptr, nullptr, out), false, ops);
-  } else {
-    const double* wv = D.winvk.empty() ? D.winv : D.winvk[step_index(m, s, pre)];
-    halo_csr(h, l, X, csr_op(D.cA, EPI_JACOBI, clsS, tagA, X, X, b, wv, out), false, ops);
-  }
-}
-
-void dcycle_csr(const DistHandle* h, int l, const double* b, double* xout, std::vector<DOp>* ops) {
-  const DDLevel& D = h->L[l];
-  const mamg_params& p = h->p;
-  const bool l0 = l == 0;
-  if (D.coarsest) {
-    Op o;
-    o.kind = OP_GEMV; o.cls = C_DENSE; o.n = D.nv; o.x = b; o.w = D.Ainv; o.out = xout;
-    o.bytes = 8.0 * o.n * o.n + 16.0 * o.n;
-    ops->push_back(wrap(o));
-    return;
-  }
-  const DDLevel& C = h->L[l + 1];
-  const int tagA = l0 ? 0 : 1, clsW = l0 ? C_L0_WB : C_COARSE;
-  const int m = smoother_steps(p);
-  const int npre = p.presmooth_iter * m, npost = p.postsmooth_iter * m;
-  double* X = D.t;
-  double* X2 = D.t2;
-  if (D.cWB.n > 0) {   // X = WB_loc b: b's ghosts first (b copied into its [owned | ghost] buffer)
-    const DCsr& wb = D.cWBk.empty() ? D.cWB : D.cWBk[step_index(m, 0, true)];
-    Op c;
-    c.kind = OP_COPY; c.cls = clsW; c.n = D.nloc; c.x = b; c.out = D.gb; c.bytes = 16.0 * D.nloc;
-    ops->push_back(wrap(c));
-    halo_csr(h, l, D.gb, csr_op(wb, EPI_Y, clsW, tagA, D.gb, nullptr, nullptr, nullptr, X), false, ops);
-  } else {
-    Op o;
-    o.kind = OP_SCALE; o.cls = clsW; o.n = D.nloc; o.w = D.winvk.empty() ? D.winv : D.winvk[step_index(m, 0, true)];
-    o.x = b; o.out = X; o.bytes = 24.0 * D.nloc;
-    ops->push_back(wrap(o));
-  }
-  for (int s = 1; s < npre; ++s) {
-    dsmooth_csr(h, l, b, X, X2, s, true, ops);
-    std::swap(X, X2);
-  }
-  halo_csr(h, l, X, csr_op(D.cA, EPI_RESID, l0 ? C_L0_RESID : C_COARSE, tagA, X, nullptr, b, nullptr, D.r), l0, ops);
-  // partial restriction, then the ghost partials to their owners (added in
-  // rank order) or the sum over the ranks into a replicated level
-  ops->push_back(wrap(csr_op(D.cR, EPI_Y, l0 ? C_L0_R : C_COARSE, tagA, D.r, nullptr, nullptr, nullptr, C.b)));
-  if (!D.replicated) {
-    DOp d;
-    d.cls = C_COMM;
-    if (C.replicated) {
-      d.dk = D_ALLREDUCE; d.buf = C.b; d.count = C.nv; d.bytes = 16.0 * C.nv;
-    } else {
-      d.dk = D_REVERSE; d.level = l + 1; d.buf = C.b;
-      const int64_t ns = C.send_off.back();
-      d.bytes = 8.0 * C.ng + 8.0 * ns * 3 + 8.0 * ns;
-    }
-    ops->push_back(d);
-  }
-  dcycle_csr(h, l + 1, C.b, C.x, ops);
-  if (p.cycle_type == MAMG_W_CYCLE && !C.coarsest) {   // second visit on the updated residual
-    halo_csr(h, l + 1, C.x, csr_op(C.cA, EPI_RESID, C_MISC, 1, C.x, nullptr, C.b, nullptr, C.c), false, ops);
-    dcycle_csr(h, l + 1, C.c, C.e, ops);
-    ops->push_back(wrap(axpy_op(C.nloc, C.e, C.x)));
-  }
-  if (p.coarse_scaling) dscale_csr(h, l + 1, ops);      // ghosts of C.x scaled too
-  else if (!C.replicated) ops->push_back(halo_op1(l + 1, C.x, C, C_COMM));
-  ops->push_back(wrap(csr_op(D.cP, EPI_YADD, l0 ? C_L0_P : C_COARSE, tagA, C.x, X, nullptr, nullptr, X)));
-  for (int s = 0; s < npost; ++s) {
-    double* out = s == npost - 1 ? xout : X2;
-    dsmooth_csr(h, l, b, X, out, s, false, ops);
-    if (out == X2) std::swap(X, X2);
-  }
-}
-
-// multi-GPU cycle from x = 0 (V or W, nu1 / nu2 sweeps, optional coarse-grid
-// scaling): see dist.cpp / dist_ref.py
-void dcycle_ops(const DistHandle* h, int l, const double* b, int64_t bs, double* xout, int64_t os,
-                std::vector<DOp>* ops) {
-  if (l == 0 && h->L[0].patches) { dcycle_patch(h, b, bs, xout, os, ops); return; }
-  if (l == 0 && h->L[0].rings) { dcycle_rings(h, b, bs, xout, os, ops); return; }
-  if (!h->L[l].coarsest && h->L[l].gcs.size() > 1) { dcycle_gs(h, l, b, bs, xout, os, ops); return; }
-  const DDLevel& D = h->L[l];
-  const bool l0 = l == 0;
-  const int tagA = l0 ? 0 : 1;
-  if (D.coarsest) {
-    Op o;
-    o.kind = OP_GEMV; o.cls = C_DENSE; o.n = 2 * D.nv; o.x = b; o.w = D.Ainv; o.out = xout;
-    o.bytes = 8.0 * o.n * o.n + 16.0 * o.n;
-    ops->push_back(wrap(o));
-    return;
-  }
-  const DDLevel& C = h->L[l + 1];
-  const int m = smoother_steps(h->p);   // steps per smoothing (POLY: Chebyshev degree)
-  const int npre = h->p.presmooth_iter * m, npost = h->p.postsmooth_iter * m;
-  auto wk = [&](int s, bool pre) -> const dv4* { return D.Wk.empty() ? D.W : D.Wk[step_index(m, s, pre)]; };
-  const int clsS = l0 ? C_L0_SMOOTH : C_COARSE;
-  double* X = D.t;
-  double* X2 = D.t2;
-  {
-    Op o;
-    o.kind = OP_BD; o.cls = l0 ? C_L0_WB : C_COARSE; o.n = D.nloc; o.W = wk(0, true); o.b = b; o.bs = bs;
-    o.out = X; o.bytes = 64.0 * D.nloc;
-    ops->push_back(wrap(o));
-  }
-  for (int s = 1; s < npre; ++s) {   // further pre steps: halo of X, then x + w_s W (b - A x)
-    const Op bj = bsr_op(dcyc_A(D), EPI_BJAC, clsS, tagA, X, 0, X, b, bs, wk(s, true), X2, 0);
-    if (D.replicated) ops->push_back(wrap(bj)); else halo_residual(h, l, X, bj, ops);
-    std::swap(X, X2);
-  }
-  {
-    const Op res = bsr_op(dcyc_A(D), EPI_RESID, l0 ? C_L0_RESID : C_COARSE, tagA, X, 0, nullptr, b, bs, nullptr, D.r, 0);
-    if (D.replicated) {
-      ops->push_back(wrap(res));
-    } else {
-      halo_residual(h, l, X, res, ops);
-    }
-  }
-  // K on its ghost-free rows while the coarse-e halo is in flight (level 0,
-  // no coarse scaling); the schedule's shape is the same on every rank (the
-  // overlap and both remainder launches are emitted, maybe empty)
-  const bool kov = l == 0 && h->sw.overlap && D.K.nr > 0 && !C.replicated && !h->p.coarse_scaling && npost >= 1 &&
-                   k_ranges_ok(D.K);
-  dcoarse_ops(h, l, ops, kov);
-  int s0 = 0;
-  if (D.K.nr > 0 || D.PA.nr > 0) {   // fused first post step (K built with its smoother), operands local
-    const bool last = npost == 1;
-    if (D.K.nr > 0) { // X + W r + K e
-      const Op k = bsr_op(D.K, EPI_KPOST, clsS, tagA, C.x, 0, X, D.r, 0, wk(0, false), last ? xout : X2,
-                          last ? os : 0);
-      if (kov) k_overlap(h, k, ops); else ops->push_back(wrap(k));
-    } else            // X + P e + W (r - AP e)
-      ops->push_back(wrap(post_op(D.PA, D.r, wk(0, false), clsS, tagA, C.x, X, last ? xout : X2,
-                                  last ? os : 0)));
-    if (last) return;
-    std::swap(X, X2);
-    s0 = 1;
-  } else {
-    ops->push_back(wrap(bsr_op(D.P, EPI_YADD, l0 ? C_L0_P : C_COARSE, tagA, C.x, 0, X, nullptr, 0,
-                               nullptr, X, 0)));
-  }
-  for (int s = s0; s < npost; ++s) {   // halo of the iterate, then x + w W (b - A x)
-    const bool last = s == npost - 1;
-    const Op bj = bsr_op(dcyc_A(D), EPI_BJAC, clsS, tagA, X, 0, X, b, bs, wk(s, false), last ? xout : X2,
-                         last ? os : 0);
-    if (D.replicated) ops->push_back(wrap(bj)); else halo_residual(h, l, X, bj, ops);
-    std::swap(X, X2);
-  }
-}
-
-// one exchange through the host callbacks: device payloads staged in pinned
-// memory around the callback (stream synchronised first), the same pack /
-// unpack / rank-ordered reverse-add kernels as the RCCL branch of run_dop
-int run_dop_host(DistHandle* h, const DOp& d, hipStream_t s, std::string* err) {
-  const int P = h->nranks, w = h->w;
-  std::vector<double*> snd(P, nullptr), rcv(P, nullptr);
-  std::vector<int64_t> sc(P, 0), rc(P, 0);
-  if (d.dk == D_ALLREDUCE) {
-    HIPCHK(hipMemcpyAsync(h->hred, d.buf, d.count * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (h->ex.allreduce(h->ex.ctx, h->hred, d.count)) { *err = "exchange allreduce callback failed"; return MAMG_ERR_HIP; }
-    HIPCHK(hipMemcpyAsync(d.buf, h->hred, d.count * sizeof(double), hipMemcpyHostToDevice, s));
-    return MAMG_OK;
-  }
-  const DDLevel& D = h->L[d.level];
-  const int64_t ns = D.send_off.back();
-  if (d.dk == D_OVERLAP) {   // interior rows on the side stream, host halo on s, join
-    HIPCHK(hipEventRecord(h->ev_in, s));
-    HIPCHK(hipStreamWaitEvent(h->side, h->ev_in, 0));
-    launch(d.op, h->side);
-    HIPCHK(hipEventRecord(h->ev_out, h->side));
-    DOp hd = d;
-    hd.dk = D_HALO;
-    int r = run_dop_host(h, hd, s, err);
-    HIPCHK(hipStreamWaitEvent(s, h->ev_out, 0));
-    return r;
-  }
-  double* hs = h->hsend[d.level];
-  double* hg = h->hghost[d.level];
-  double* hr = h->hrecv[d.level];
-  if (d.dk == D_CHALO) {
-    const size_t b0 = (size_t)d.colour * (P + 1);
-    const int64_t s0 = D.cs_off[b0], s1 = D.cs_off[b0 + P], g0 = D.cg_off[b0], g1 = D.cg_off[b0 + P];
-    for (int q = 0; q < P; ++q) {
-      if (q == h->rank) continue;
-      snd[q] = hs + w * D.cs_off[b0 + q]; sc[q] = w * (D.cs_off[b0 + q + 1] - D.cs_off[b0 + q]);
-      rcv[q] = hg + w * D.cg_off[b0 + q]; rc[q] = w * (D.cg_off[b0 + q + 1] - D.cg_off[b0 + q]);
-    }
-    if (s1 > s0) {
-      pack_w(w, s1 - s0, D.csend_idx + s0, d.buf, D.sendbuf + w * s0, s);
-      HIPCHK(hipMemcpyAsync(hs + w * s0, D.sendbuf + w * s0, w * (s1 - s0) * sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    if (h->ex.sendrecv(h->ex.ctx, P, snd.data(), sc.data(), rcv.data(), rc.data())) {
-      *err = "exchange sendrecv callback failed";
-      return MAMG_ERR_HIP;
-    }
-    if (g1 > g0) {
-      HIPCHK(hipMemcpyAsync(D.recvbuf + w * g0, hg + w * g0, w * (g1 - g0) * sizeof(double), hipMemcpyHostToDevice, s));
-      unpack_w(w, g1 - g0, D.cghost_idx + g0, D.nloc, D.recvbuf + w * g0, d.buf, s);
-    }
-    return MAMG_OK;
-  }
-  for (int q = 0; q < P; ++q) {
-    if (q == h->rank) continue;
-    const int64_t sq = D.send_off[q + 1] - D.send_off[q], gq = D.ghost_off[q + 1] - D.ghost_off[q];
-    if (d.dk == D_HALO) {   // my owned values they ghost -> their ghosts of mine
-      snd[q] = hs + w * D.send_off[q]; sc[q] = w * sq;
-      rcv[q] = hg + w * D.ghost_off[q]; rc[q] = w * gq;
-    } else {                // D_REVERSE: my ghost partials -> their owned rows
-      snd[q] = hg + w * D.ghost_off[q]; sc[q] = w * gq;
-      rcv[q] = hr + w * D.send_off[q]; rc[q] = w * sq;
-    }
-  }
-  if (d.dk == D_HALO) {
-    if (ns) {
-      pack_w(w, ns, D.send_idx, d.buf, D.sendbuf, s);
-      HIPCHK(hipMemcpyAsync(hs, D.sendbuf, w * ns * sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    if (h->ex.sendrecv(h->ex.ctx, P, snd.data(), sc.data(), rcv.data(), rc.data())) {
-      *err = "exchange sendrecv callback failed";
-      return MAMG_ERR_HIP;
-    }
-    if (D.ng)
-      HIPCHK(hipMemcpyAsync(d.buf + w * D.nloc, hg, w * D.ng * sizeof(double), hipMemcpyHostToDevice, s));
-    return MAMG_OK;
-  }
-  // D_REVERSE
-  if (D.ng) HIPCHK(hipMemcpyAsync(hg, d.buf + w * D.nloc, w * D.ng * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (h->ex.sendrecv(h->ex.ctx, P, snd.data(), sc.data(), rcv.data(), rc.data())) {
-    *err = "exchange sendrecv callback failed";
-    return MAMG_ERR_HIP;
-  }
-  if (ns) HIPCHK(hipMemcpyAsync(D.recvbuf, hr, w * ns * sizeof(double), hipMemcpyHostToDevice, s));
-  for (int q = 0; q < P; ++q) {
-    const int64_t sq = D.send_off[q + 1] - D.send_off[q];
-    if (q == h->rank || !sq) continue;
-    addidx_w(w, sq, D.send_idx + D.send_off[q], D.recvbuf + w * D.send_off[q], d.buf, s);
-  }
-  return MAMG_OK;
-}
-
-int run_dop(DistHandle* h, const DOp& d, hipStream_t s, std::string* err) {
-  if (d.dk == D_OP) {
-    launch(d.op, s);
-    return MAMG_OK;
-  }
-  const int w = h->w;
-  if (h->nranks == 1 && !h->comm) {     // no peers: halos empty, sums over one rank
-    if (d.dk == D_OVERLAP) launch(d.op, s);
-    return MAMG_OK;
-  }
-  // (a 1-rank RCCL communicator takes the RCCL path below: empty send /
-  // receive groups, an all-reduce over one rank, the side-stream fork; the
-  // one-GPU tests exercise those calls, eager and inside a graph capture)
-  if (!h->comm && h->dry) {            // compute-only timing of one rank (results meaningless)
-    if (d.dk == D_OVERLAP) launch(d.op, s);
-    return MAMG_OK;
-  }
-  if (!h->comm && h->host_ex) return run_dop_host(h, d, s, err);
-  if (!h->comm) {
-    *err = "virtual rank handle (no communicator): use mamg_dist_virtual_apply / _spmv";
-    return MAMG_ERR_ARG;
-  }
-  if (d.dk == D_ALLREDUCE) {
-    NCCLCHK(ncclAllReduce(d.buf, d.buf, d.count, ncclDouble, ncclSum, h->comm, s));
-    return MAMG_OK;
-  }
-  const DDLevel& D = h->L[d.level];
-  const int64_t ns = D.send_off.back();
-  if (d.dk == D_OVERLAP) {   // interior rows on the side stream, halo on s, join
-    HIPCHK(hipEventRecord(h->ev_in, s));
-    HIPCHK(hipStreamWaitEvent(h->side, h->ev_in, 0));
-    launch(d.op, h->side);
-    HIPCHK(hipEventRecord(h->ev_out, h->side));
-    DOp hd = d;
-    hd.dk = D_HALO;
-    int rc = run_dop(h, hd, s, err);
-    HIPCHK(hipStreamWaitEvent(s, h->ev_out, 0));
-    return rc;
-  }
-  if (d.dk == D_CHALO) {      // one colour's nodes: pack, send / receive, unpack into the ghost slots
-    const int P = h->nranks;
-    const size_t b0 = (size_t)d.colour * (P + 1);
-    const int64_t s0 = D.cs_off[b0], s1 = D.cs_off[b0 + P], g0 = D.cg_off[b0], g1 = D.cg_off[b0 + P];
-    if (s1 > s0) pack_w(w, s1 - s0, D.csend_idx + s0, d.buf, D.sendbuf + w * s0, s);
-    NCCLCHK(ncclGroupStart());
-    for (int q = 0; q < P; ++q) {
-      if (q == h->rank) continue;
-      const int64_t sc = D.cs_off[b0 + q + 1] - D.cs_off[b0 + q], gc = D.cg_off[b0 + q + 1] - D.cg_off[b0 + q];
-      if (sc) NCCLCHK(ncclSend(D.sendbuf + w * D.cs_off[b0 + q], w * sc, ncclDouble, q, h->comm, s));
-      if (gc) NCCLCHK(ncclRecv(D.recvbuf + w * D.cg_off[b0 + q], w * gc, ncclDouble, q, h->comm, s));
-    }
-    NCCLCHK(ncclGroupEnd());
-    if (g1 > g0) unpack_w(w, g1 - g0, D.cghost_idx + g0, D.nloc, D.recvbuf + w * g0, d.buf, s);
-    return MAMG_OK;
-  }
-  if (d.dk == D_HALO) {
-    if (ns) pack_w(w, ns, D.send_idx, d.buf, D.sendbuf, s);
-    NCCLCHK(ncclGroupStart());
-    for (int q = 0; q < h->nranks; ++q) {
-      if (q == h->rank) continue;
-      const int64_t sc = D.send_off[q + 1] - D.send_off[q];
-      const int64_t gc = D.ghost_off[q + 1] - D.ghost_off[q];
-      if (sc) NCCLCHK(ncclSend(D.sendbuf + w * D.send_off[q], w * sc, ncclDouble, q, h->comm, s));
-      if (gc) NCCLCHK(ncclRecv(d.buf + w * (D.nloc + D.ghost_off[q]), w * gc, ncclDouble, q, h->comm, s));
-    }
-    NCCLCHK(ncclGroupEnd());
-    return MAMG_OK;
-  }
-  // D_REVERSE: ghost partials -> owners; owners add in rank order
-  NCCLCHK(ncclGroupStart());
-  for (int q = 0; q < h->nranks; ++q) {
-    if (q == h->rank) continue;
-    const int64_t sc = D.send_off[q + 1] - D.send_off[q];
-    const int64_t gc = D.ghost_off[q + 1] - D.ghost_off[q];
-    if (gc) NCCLCHK(ncclSend(d.buf + w * (D.nloc + D.ghost_off[q]), w * gc, ncclDouble, q, h->comm, s));
-    if (sc) NCCLCHK(ncclRecv(D.recvbuf + w * D.send_off[q], w * sc, ncclDouble, q, h->comm, s));
-  }
-  NCCLCHK(ncclGroupEnd());
-  for (int q = 0; q < h->nranks; ++q) {
-    const int64_t sc = D.send_off[q + 1] - D.send_off[q];
-    if (q == h->rank || !sc) continue;
-    addidx_w(w, sc, D.send_idx + D.send_off[q], D.recvbuf + w * D.send_off[q], d.buf, s);
-  }
-  return MAMG_OK;
-}
-
-void dapply_ops(const DistHandle* h, const double* r, double* z, std::vector<DOp>* ops) {
-  ops->clear();
-  const int64_t nloc = h->L[0].nloc;
-  if (h->w == 1) { dcycle_csr(h, 0, r, z, ops); return; }   // scalar: the rank's plain slices
-  dcycle_ops(h, 0, r, nloc, z, nloc, ops);
-}
-
-// y = A x on the rank's rows (field-major local slices): interleave x into
-// the [owned | ghost] buffer, forward halo, SpMV with A_loc (PCG operator)
-void dspmv_ops(const DistHandle* h, const double* x, double* y, std::vector<DOp>* ops) {
-  ops->clear();
-  const DDLevel& D = h->L[0];
-  if (h->w == 1) {   // scalar: x copied into the [owned | ghost] buffer, halo, A_loc (interior rows meanwhile)
-    Op c;
-    c.kind = OP_COPY; c.cls = C_MISC; c.n = D.nloc; c.x = x; c.out = D.spx; c.bytes = 16.0 * D.nloc;
-    ops->push_back(wrap(c));
-    halo_csr(h, 0, D.spx, csr_op(D.cA, EPI_Y, C_L0_RESID, 0, D.spx, nullptr, nullptr, nullptr, y), true, ops);
-    return;
-  }
-  Op o;
-  o.kind = OP_ILV; o.cls = C_MISC; o.n = D.nloc; o.b = x; o.bs = D.nloc; o.out = D.spx;
-  o.bytes = 32.0 * D.nloc;
-  ops->push_back(wrap(o));
-  const Op mv = bsr_op(D.A, EPI_Y, C_L0_RESID, 0, D.spx, 0, nullptr, nullptr, 0, nullptr, y, D.nloc);
-  if (D.replicated) ops->push_back(wrap(mv)); else halo_residual(h, 0, D.spx, mv, ops);
-}
-
-}  // namespace
-
 void device_warm(void* stream) {
   warm_kernel<<<1, 64, 0, (hipStream_t)stream>>>();
+  dist_layout_warm((hipStream_t)stream);
   (void)hipGetLastError();
 }
-
-int dist_get_unique_id(void* id, std::string* err) {
-  ncclUniqueId u;
-  NCCLCHK(ncclGetUniqueId(&u));
-  std::memcpy(id, &u, sizeof(u));
-  return MAMG_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Rank-local operators built in HBM from the GPU hierarchy (mamg_setup_dist's
-// default): the device restatement of build_dist_plan's conversions, so no
-// matrix of the hierarchy crosses PCIe.  Row slices are gathered from the
-// field-major CSRs, converted by the single-GPU csr2bsr kernel, and their
-// columns renumbered [owned | ghost] (owned first, each part in global order:
-// dist.cpp remap_cols); K by kmerge_kernel, the partial restriction from R's
-// rows (R = P^T exactly, so its blocks are transpose_bsr's).  Bitwise the
-// host plan's operators (tests/test_gpu_dist.py::test_rank_slice_download_bitwise).
-// ---------------------------------------------------------------------------
-namespace {
-
-// rows f m + i of the gathered CSR = rows f nvr + row(i) of M, row(i) =
-// rows[i] or r0 + i
-__global__ __launch_bounds__(256) void rowlen_gather_kernel(int64_t m, int64_t nvr, const int64_t* __restrict__ rows,
-                                                            int64_t r0, const int64_t* __restrict__ ptr,
-                                                            int64_t* __restrict__ len) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= 2 * m) return;
-  const int64_t f = i / m, k = i - f * m;
-  const int64_t src = f * nvr + (rows ? rows[k] : r0 + k);
-  len[i + 1] = ptr[src + 1] - ptr[src];
-}
-
-__global__ __launch_bounds__(256) void rowcopy_gather_kernel(int64_t m, int64_t nvr, const int64_t* __restrict__ rows,
-                                                             int64_t r0, const int64_t* __restrict__ ptr,
-                                                             const int32_t* __restrict__ col,
-                                                             const double* __restrict__ val,
-                                                             const int64_t* __restrict__ optr,
-                                                             int32_t* __restrict__ ocol, double* __restrict__ oval) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= 2 * m) return;
-  const int64_t f = i / m, k = i - f * m;
-  const int64_t src = f * nvr + (rows ? rows[k] : r0 + k);
-  int64_t o = optr[i];
-  for (int64_t q = ptr[src]; q < ptr[src + 1]; ++q, ++o) {
-    ocol[o] = col[q];
-    oval[o] = val[q];
-  }
-}
-
-// node columns -> local [owned | ghost] numbering: owned blocks first, then
-// ghosts, each in the row's (global) order
-__global__ __launch_bounds__(256) void map_part_kernel(int64_t nr, const int64_t* __restrict__ ptr,
-                                                       const int32_t* __restrict__ col, const dv4* __restrict__ val,
-                                                       const int32_t* __restrict__ map, int32_t nown,
-                                                       int32_t* __restrict__ ocol, dv4* __restrict__ oval) {
-  const int64_t I = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (I >= nr) return;
-  int64_t o = ptr[I];
-  for (int part = 0; part < 2; ++part)
-    for (int64_t k = ptr[I]; k < ptr[I + 1]; ++k) {
-      const int32_t c = map[col[k]];
-      if ((c < nown) == (part == 0)) { ocol[o] = c; oval[o] = val[k]; ++o; }
-    }
-}
-
-// keep the blocks whose column lies in [w0, w1), renumbered from w0
-__global__ __launch_bounds__(256) void window_len_kernel(int64_t nr, const int64_t* __restrict__ ptr,
-                                                         const int32_t* __restrict__ col, int64_t w0, int64_t w1,
-                                                         int64_t* __restrict__ len) {
-  const int64_t I = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (I >= nr) return;
-  int64_t c = 0;
-  for (int64_t k = ptr[I]; k < ptr[I + 1]; ++k) c += col[k] >= w0 && col[k] < w1;
-  len[I + 1] = c;
-}
-
-__global__ __launch_bounds__(256) void window_fill_kernel(int64_t nr, const int64_t* __restrict__ ptr,
-                                                          const int32_t* __restrict__ col,
-                                                          const dv4* __restrict__ val, int64_t w0, int64_t w1,
-                                                          const int64_t* __restrict__ optr,
-                                                          int32_t* __restrict__ ocol, dv4* __restrict__ oval) {
-  const int64_t I = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (I >= nr) return;
-  int64_t o = optr[I];
-  for (int64_t k = ptr[I]; k < ptr[I + 1]; ++k)
-    if (col[k] >= w0 && col[k] < w1) { ocol[o] = (int32_t)(col[k] - w0); oval[o] = val[k]; ++o; }
-}
-
-__global__ __launch_bounds__(256) void map_fill_kernel(int64_t n, int64_t first, int32_t base,
-                                                       const int64_t* __restrict__ ids, int32_t* __restrict__ map) {
-  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (k >= n) return;
-  map[ids ? ids[k] : first + k] = base + (int32_t)k;
-}
-
-__global__ __launch_bounds__(256) void ghost_row_kernel(int64_t nr, const int64_t* __restrict__ ptr,
-                                                        const int32_t* __restrict__ col, int32_t nown,
-                                                        uint8_t* __restrict__ flag) {
-  const int64_t I = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (I >= nr) return;
-  uint8_t g = 0;
-  for (int64_t k = ptr[I]; k < ptr[I + 1]; ++k) g |= col[k] >= nown;
-  flag[I] = g;
-}
-
-// a node split by seed blocks keeps the two diagonal entries of its block
-__global__ __launch_bounds__(256) void unjoin_kernel(int64_t n, const uint8_t* __restrict__ joined, dv4* W) {
-  const int64_t I = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (I < n && !joined[I]) { W[I].y = 0.0; W[I].z = 0.0; }
-}
-
-// rows of a field-major CSR (node rows r0 + i, or rows[i]) as a BSR2 with
-// global node columns
-int dev_rows_to_bsr(TmpPool* T, const DevMat& M, int64_t nvr, int64_t nvc, int64_t m, const int64_t* rows,
-                    int64_t r0, TBsr* B, std::string* err) {
-  int rc;
-  DevMat S;
-  S.n = 2 * m;
-  S.m = M.m;
-  if ((rc = T->alloc(&S.ptr, 2 * m + 1, err))) return rc;
-  HIPCHK(dev_memset(S.ptr, 0, sizeof(int64_t)));
-  if (m) rowlen_gather_kernel<<<nblocks(2 * m), 256>>>(m, nvr, rows, r0, M.ptr, S.ptr);
-  HIPCHK(hipGetLastError());
-  if ((rc = dscan_incl_i64(S.ptr, S.ptr, 2 * m + 1, nullptr, err))) return rc;
-  HIPCHK(hipMemcpy(&S.nnz, S.ptr + 2 * m, sizeof(int64_t), hipMemcpyDeviceToHost));
-  if ((rc = T->alloc(&S.col, S.nnz, err))) return rc;
-  if ((rc = T->alloc(&S.val, S.nnz, err))) return rc;
-  if (m) rowcopy_gather_kernel<<<nblocks(2 * m), 256>>>(m, nvr, rows, r0, M.ptr, M.col, M.val, S.ptr, S.col, S.val);
-  HIPCHK(hipGetLastError());
-  return dev_csr_to_bsr(T, S, m, nvc, B, err);
-}
-
-// column map of a distributed level: owned J -> J - o0, ghost g_k -> nloc + k
-int dev_col_map(TmpPool* T, const DistLevel& L, int32_t** map, std::string* err) {
-  int rc;
-  if ((rc = T->alloc(map, L.nv, err))) return rc;
-  HIPCHK(dev_memset(*map, 0xff, L.nv * sizeof(int32_t)));
-  if (L.nloc) map_fill_kernel<<<nblocks(L.nloc), 256>>>(L.nloc, L.o0, 0, nullptr, *map);
-  const int64_t ng = (int64_t)L.ghosts.size();
-  if (ng) {
-    int64_t* g = nullptr;
-    if ((rc = T->alloc(&g, ng, err))) return rc;
-    HIPCHK(hipMemcpy(g, L.ghosts.data(), ng * sizeof(int64_t), hipMemcpyHostToDevice));
-    map_fill_kernel<<<nblocks(ng), 256>>>(ng, 0, (int32_t)L.nloc, g, *map);
-  }
-  HIPCHK(hipGetLastError());
-  return MAMG_OK;
-}
-
-// BSR2 columns renumbered by map, [owned | ghost] order; nc = local columns
-int dev_map_cols(TmpPool* T, const TBsr& B, const int32_t* map, int64_t nown, int64_t nc, TBsr* O,
-                 std::string* err) {
-  int rc;
-  *O = B;
-  O->nc = nc;
-  if ((rc = T->alloc(&O->col, B.nb, err))) return rc;
-  if ((rc = T->alloc(&O->val, B.nb, err))) return rc;
-  if (B.nr) map_part_kernel<<<nblocks(B.nr), 256>>>(B.nr, B.ptr, B.col, B.val, map, (int32_t)nown, O->col, O->val);
-  HIPCHK(hipGetLastError());
-  return MAMG_OK;
-}
-
-int dev_window_cols(TmpPool* T, const TBsr& B, int64_t w0, int64_t w1, TBsr* O, std::string* err) {
-  int rc;
-  O->nr = B.nr; O->nc = w1 - w0; O->merged = false;
-  if ((rc = T->alloc(&O->ptr, B.nr + 1, err))) return rc;
-  HIPCHK(dev_memset(O->ptr, 0, sizeof(int64_t)));
-  if (B.nr) window_len_kernel<<<nblocks(B.nr), 256>>>(B.nr, B.ptr, B.col, w0, w1, O->ptr);
-  HIPCHK(hipGetLastError());
-  if ((rc = dscan_incl_i64(O->ptr, O->ptr, B.nr + 1, nullptr, err))) return rc;
-  HIPCHK(hipMemcpy(&O->nb, O->ptr + B.nr, sizeof(int64_t), hipMemcpyDeviceToHost));
-  if ((rc = T->alloc(&O->col, O->nb, err))) return rc;
-  if ((rc = T->alloc(&O->val, O->nb, err))) return rc;
-  if (B.nr) window_fill_kernel<<<nblocks(B.nr), 256>>>(B.nr, B.ptr, B.col, B.val, w0, w1, O->ptr, O->col, O->val);
-  HIPCHK(hipGetLastError());
-  return MAMG_OK;
-}
-
-// ---- node patches on N ranks (dist_patches) --------------------------------
-// hop distance of every node from the owned range (0 owned, 1..3, 127 beyond)
-__global__ __launch_bounds__(256) void hop_init_kernel(int64_t nv, int64_t o0, int64_t o1, int8_t* __restrict__ d) {
-  const int64_t I = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (I < nv) d[I] = (I >= o0 && I < o1) ? 0 : 127;
-}
-__global__ __launch_bounds__(256) void hop_step_kernel(int64_t nv, const int64_t* __restrict__ ptr,
-                                                       const int32_t* __restrict__ col, const int8_t* __restrict__ din,
-                                                       int8_t* __restrict__ dout, int k) {
-  const int64_t I = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (I >= nv) return;
-  int8_t v = din[I];
-  if (v == 127)
-    for (int64_t q = ptr[I]; q < ptr[I + 1]; ++q)
-      if (din[col[q]] == k - 1) { v = (int8_t)k; break; }
-  dout[I] = v;
-}
-// global id of local node li ([owned | ghost])
-__device__ __forceinline__ int64_t local_gid(int64_t li, int64_t nloc, int64_t o0, const int64_t* gh) {
-  return li < nloc ? o0 + li : gh[li - nloc];
-}
-// the rank's patch / ring-block rows: local row li = B's row of its global
-// node when that node is within hmax hops of the owned range, else empty
-// (len[li + 1])
-__global__ __launch_bounds__(256) void srow_len_kernel(int64_t nl, int64_t nloc, int64_t o0, const int64_t* __restrict__ gh,
-                                                       const int8_t* __restrict__ hop, const int64_t* __restrict__ bptr,
-                                                       int64_t* __restrict__ len, int hmax) {
-  const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (li >= nl) return;
-  const int64_t g = local_gid(li, nloc, o0, gh);
-  len[li + 1] = hop[g] <= hmax ? bptr[g + 1] - bptr[g] : 0;
-}
-// ... its blocks in B's (global) column order: local columns (map) and the
-// global ids (the inverse kernel's search keys)
-__global__ __launch_bounds__(256) void srow_fill_kernel(int64_t nl, int64_t nloc, int64_t o0, const int64_t* __restrict__ gh,
-                                                        const int64_t* __restrict__ bptr, const int32_t* __restrict__ bcol,
-                                                        const dv4* __restrict__ bval, const int32_t* __restrict__ map,
-                                                        const int64_t* __restrict__ sptr, int32_t* __restrict__ scol,
-                                                        int32_t* __restrict__ sgcol, dv4* __restrict__ sval) {
-  const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (li >= nl || sptr[li + 1] == sptr[li]) return;
-  const int64_t g = local_gid(li, nloc, o0, gh);
-  int64_t o = sptr[li];
-  for (int64_t k = bptr[g]; k < bptr[g + 1]; ++k, ++o) {
-    scol[o] = map[bcol[k]];
-    sgcol[o] = bcol[k];
-    sval[o] = bval[k];
-  }
-}
-// per local node: its hop distance and colour (for the centre list)
-__global__ __launch_bounds__(256) void local_hop_colour_kernel(int64_t nl, int64_t nloc, int64_t o0,
-                                                               const int64_t* __restrict__ gh,
-                                                               const int8_t* __restrict__ hop,
-                                                               const int16_t* __restrict__ c, int8_t* __restrict__ lh,
-                                                               int16_t* __restrict__ lc) {
-  const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (li >= nl) return;
-  const int64_t g = local_gid(li, nloc, o0, gh);
-  lh[li] = hop[g];
-  lc[li] = c[g];
-}
-// colours of the patches that write node J (the centres in J's closed
-// neighbourhood), -1 padded: PATCH_MAX_NODES + 1 slots per node
-__global__ __launch_bounds__(256) void cover_kernel(int64_t cnt, const int64_t* __restrict__ nodes,
-                                                    const int64_t* __restrict__ bptr, const int32_t* __restrict__ bcol,
-                                                    const int16_t* __restrict__ c, int16_t* __restrict__ out) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= cnt) return;
-  const int64_t J = nodes[t];
-  int16_t* o = out + t * (PATCH_MAX_NODES + 1);
-  int k = 0;
-  bool self = false;
-  for (int64_t q = bptr[J]; q < bptr[J + 1] && k < PATCH_MAX_NODES + 1; ++q) {
-    self |= bcol[q] == J;
-    o[k++] = c[bcol[q]];
-  }
-  if (!self && k < PATCH_MAX_NODES + 1) o[k++] = c[J];
-  for (; k < PATCH_MAX_NODES + 1; ++k) o[k] = -1;
-}
-
-// Level-0 node patches of a rank: the global distance-3
-// colouring (every rank colours the whole level-0 graph, as the single-GPU
-// build_patches, so all ranks hold the same colours); the centres within 1
-// hop of the owned nodes (their patches write owned nodes; the owner of
-// every written node computes the same patch from the same x, so its bits
-// agree); their rows (nodes within 2 hops) with the global column order kept
-// (the patch's local dof order, hence its Gauss-Jordan, equals the single
-// GPU's); the inverses; and per colour the halo of the nodes its patches
-// write (send: owned nodes in a peer's 3-hop region, receive: ghosts), so
-// that the ghosts within 3 hops are current before the next colour.
-int dist_patches(DistHandle* h, const DevMat& A0d, const DistLevel& P, DDLevel* D, std::string* err) {
-  int rc;
-  TmpPool T(h->sw);
-  const int64_t nv = P.nv, nloc = P.nloc, ng = (int64_t)P.ghosts.size(), nl = nloc + ng;
-  const int R = h->nranks;
-  TBsr B;
-  if ((rc = dev_csr_to_bsr(&T, A0d, nv, nv, &B, err))) return rc;
-  int16_t* c = nullptr;
-  int maxlen = 0;
-  if ((rc = patch_colour(&T, B, &c, &maxlen, err))) return rc;
-  int16_t hcol_max = 0;
-  {
-    std::vector<int16_t> hc(nv);
-    HIPCHK(hipMemcpy(hc.data(), c, nv * sizeof(int16_t), hipMemcpyDeviceToHost));
-    for (int16_t v : hc) hcol_max = std::max(hcol_max, v);
-  }
-  const int ncol = hcol_max + 1;
-  int8_t *hop = nullptr, *hop2 = nullptr;
-  if ((rc = T.alloc(&hop, nv, err)) || (rc = T.alloc(&hop2, nv, err))) return rc;
-  hop_init_kernel<<<nblocks(nv), 256>>>(nv, P.o0, P.o1, hop);
-  for (int k = 1; k <= 3; ++k) {
-    hop_step_kernel<<<nblocks(nv), 256>>>(nv, B.ptr, B.col, hop, hop2, k);
-    std::swap(hop, hop2);
-  }
-  HIPCHK(hipGetLastError());
-  int64_t* gh = nullptr;
-  if ((rc = T.alloc(&gh, std::max<int64_t>(ng, 1), err))) return rc;
-  if (ng) HIPCHK(hipMemcpy(gh, P.ghosts.data(), ng * sizeof(int64_t), hipMemcpyHostToDevice));
-  int32_t* map = nullptr;
-  if ((rc = dev_col_map(&T, P, &map, err))) return rc;
-  // the patch rows
-  DLevel& L = D->pl;
-  if ((rc = ddalloc(h, &L.Sptr, nl + 1, err))) return rc;
-  if (nl) srow_len_kernel<<<nblocks(nl), 256>>>(nl, nloc, P.o0, gh, hop, B.ptr, L.Sptr, 2);
-  HIPCHK(hipGetLastError());
-  if ((rc = dscan_incl_i64(L.Sptr, L.Sptr, nl + 1, nullptr, err))) return rc;
-  HIPCHK(hipMemcpy(&L.Snb, L.Sptr + nl, sizeof(int64_t), hipMemcpyDeviceToHost));
-  if ((rc = ddalloc(h, &L.Scol, std::max<int64_t>(L.Snb, 1), err))) return rc;
-  if ((rc = ddalloc(h, &D->Sgcol, std::max<int64_t>(L.Snb, 1), err))) return rc;
-  if ((rc = ddalloc(h, &L.Sval, std::max<int64_t>(L.Snb, 1), err))) return rc;
-  if (nl) srow_fill_kernel<<<nblocks(nl), 256>>>(nl, nloc, P.o0, gh, B.ptr, B.col, B.val, map, L.Sptr, L.Scol, D->Sgcol,
-                                                 L.Sval);
-  HIPCHK(hipGetLastError());
-  // the centres (within 1 hop), colour by colour, ascending global id inside a colour
-  std::vector<int8_t> lh(nl);
-  std::vector<int16_t> lc(nl);
-  {
-    int8_t* dlh = nullptr;
-    int16_t* dlc = nullptr;
-    if ((rc = T.alloc(&dlh, std::max<int64_t>(nl, 1), err)) || (rc = T.alloc(&dlc, std::max<int64_t>(nl, 1), err)))
-      return rc;
-    if (nl) local_hop_colour_kernel<<<nblocks(nl), 256>>>(nl, nloc, P.o0, gh, hop, c, dlh, dlc);
-    HIPCHK(hipGetLastError());
-    if (nl) {
-      HIPCHK(hipMemcpy(lh.data(), dlh, nl, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(lc.data(), dlc, nl * sizeof(int16_t), hipMemcpyDeviceToHost));
-    }
-  }
-  std::vector<std::pair<int64_t, int64_t>> cen;   // (colour << 40 | global id, local id)
-  for (int64_t li = 0; li < nl; ++li)
-    if (lh[li] <= 1) {
-      const int64_t g = li < nloc ? P.o0 + li : P.ghosts[li - nloc];
-      cen.push_back({((int64_t)lc[li] << 40) | g, li});
-    }
-  std::sort(cen.begin(), cen.end());
-  const int64_t np = (int64_t)cen.size();
-  L.pcs.assign(ncol + 1, 0);
-  std::vector<int32_t> perm(np);
-  for (int64_t i = 0; i < np; ++i) {
-    perm[i] = (int32_t)cen[i].second;
-    ++L.pcs[(cen[i].first >> 40) + 1];
-  }
-  for (int k = 0; k < ncol; ++k) L.pcs[k + 1] += L.pcs[k];
-  L.n = 2 * np;
-  if ((rc = ddalloc(h, &L.pperm, std::max<int64_t>(np, 1), err))) return rc;
-  if (np) HIPCHK(hipMemcpy(L.pperm, perm.data(), np * sizeof(int32_t), hipMemcpyHostToDevice));
-  // inverses
-  const int64_t dmax = 2 * (int64_t)maxlen;
-  L.pus = dmax * (dmax + 1) / 2;
-  if ((rc = ddalloc(h, &L.pu, std::max<int64_t>(np * L.pus, 1), err))) return rc;
-  int* bad = nullptr;
-  if ((rc = T.alloc(&bad, 1, err))) return rc;
-  HIPCHK(dev_memset(bad, 0, sizeof(int)));
-  launch_patch_inv(h->sw.patch_inv, np, L.pperm, L.Sptr, L.Scol, D->Sgcol, L.Sval, L.pus, L.pu, bad);
-  HIPCHK(hipGetLastError());
-  int hb = 0;
-  HIPCHK(hipMemcpy(&hb, bad, sizeof(int), hipMemcpyDeviceToHost));
-  if (hb) { *err = "node patches: a patch matrix is not SPD (non-positive Gauss-Jordan pivot)"; return MAMG_ERR_SETUP; }
-  // each colour's halo: the listed nodes its patches write
-  const int64_t ns = P.send_off.empty() ? 0 : P.send_off.back();
-  std::vector<int64_t> lst(ns + ng);
-  for (int64_t t = 0; t < ns; ++t) lst[t] = P.o0 + P.send_idx[t];
-  for (int64_t g = 0; g < ng; ++g) lst[ns + g] = P.ghosts[g];
-  constexpr int CW = PATCH_MAX_NODES + 1;
-  std::vector<int16_t> cov((size_t)(ns + ng) * CW);
-  if (ns + ng) {
-    int64_t* dl = nullptr;
-    int16_t* dc = nullptr;
-    if ((rc = T.alloc(&dl, ns + ng, err)) || (rc = T.alloc(&dc, (ns + ng) * CW, err))) return rc;
-    HIPCHK(hipMemcpy(dl, lst.data(), (ns + ng) * sizeof(int64_t), hipMemcpyHostToDevice));
-    cover_kernel<<<nblocks(ns + ng), 256>>>(ns + ng, dl, B.ptr, B.col, c, dc);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(cov.data(), dc, cov.size() * sizeof(int16_t), hipMemcpyDeviceToHost));
-  }
-  auto covers = [&](int64_t t, int col) {
-    for (int k = 0; k < CW; ++k)
-      if (cov[(size_t)t * CW + k] == col) return true;
-    return false;
-  };
-  std::vector<int64_t> cs, cg;
-  D->cs_off.assign((size_t)ncol * (R + 1), 0);
-  D->cg_off.assign((size_t)ncol * (R + 1), 0);
-  for (int col = 0; col < ncol; ++col) {
-    for (int q = 0; q < R; ++q) {
-      D->cs_off[(size_t)col * (R + 1) + q] = (int64_t)cs.size();
-      D->cg_off[(size_t)col * (R + 1) + q] = (int64_t)cg.size();
-      for (int64_t t = P.send_off[q]; t < P.send_off[q + 1]; ++t)
-        if (covers(t, col)) cs.push_back(P.send_idx[t]);
-      for (int64_t g = P.ghost_off[q]; g < P.ghost_off[q + 1]; ++g)
-        if (covers(ns + g, col)) cg.push_back(g);
-    }
-    D->cs_off[(size_t)col * (R + 1) + R] = (int64_t)cs.size();
-    D->cg_off[(size_t)col * (R + 1) + R] = (int64_t)cg.size();
-  }
-  if (!cs.empty()) {
-    if ((rc = ddalloc(h, &D->csend_idx, (int64_t)cs.size(), err))) return rc;
-    HIPCHK(hipMemcpy(D->csend_idx, cs.data(), cs.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-  }
-  if (!cg.empty()) {
-    if ((rc = ddalloc(h, &D->cghost_idx, (int64_t)cg.size(), err))) return rc;
-    HIPCHK(hipMemcpy(D->cghost_idx, cg.data(), cg.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-  }
-  D->patches = true;
-  if (h->p.print_level >= 2)
-    std::fprintf(stderr, "[mamg] rank %d/%d node patches: %d colours, %lld centres (%lld owned), %lld ghost nodes "
-                 "(3 hops), colour halos %lld sends / %lld receives in all\n", h->rank, R, ncol, (long long)np,
-                 (long long)nloc, (long long)ng, (long long)cs.size(), (long long)cg.size());
-  return MAMG_OK;
-}
-
-// Level-0 seed-ring Schwarz of a rank (SCHWARZ_RINGS on N GPUs, DESIGN.md
-// 6.4): every rank builds the global blocks, inverses and
-// conflict colouring (ring_blocks_dev + ring_colouring, the single-GPU
-// build_rings' steps, so every rank holds the same blocks and colours) and
-// keeps the blocks with a member node it owns -- the owner of every written
-// node computes every block that writes it, from the same x, so its bits agree
-// with one GPU's.  A block's members lie within 2 maxlvl hops of an owned node
-// and its rows read x within 2 maxlvl + 1 hops: the ghost region.  The rest's
-// multicolour GS runs on the owned rows with the covered dofs masked
-// (dev_rank_ops, from *cov_owned).  One colour table serves both: ring colour
-// c at index c (the nodes its blocks write), GS colour g at nrc + g (the nodes
-// of that colour), each with the halo of those nodes in the send / ghost
-// lists, so the exchange code is the multicolour GS's.
-int dist_rings(DistHandle* h, const DevMat& A0d, const DistLevel& P, const std::vector<int32_t>& seeds,
-               const int8_t* gcol, int ngc, DDLevel* D, uint8_t** cov_owned, std::string* err) {
-  int rc;
-  TmpPool T(h->sw);
-  const mamg_params& p = h->p;
-  const int64_t nv = P.nv, nloc = P.nloc, ng = (int64_t)P.ghosts.size(), nl = nloc + ng, n = A0d.n;
-  const int R = h->nranks, L = p.Schwarz_maxlvl;
-  const int64_t ns = (int64_t)seeds.size();
-  if (ns <= 0) { *err = "seed rings: no seeds"; return MAMG_ERR_ARG; }
-  // the global blocks and their conflict colouring (build_rings)
-  RingBlocks RB;
-  if ((rc = ring_blocks_dev(A0d, seeds.data(), ns, L, p.Schwarz_mmsize, &RB, err))) return rc;
-  struct Guard { RingBlocks* r; ~Guard() { ring_blocks_free(r); } } guard{&RB};
-  const int mm = RB.mm;
-  std::vector<int32_t> blk((size_t)ns * mm);
-  std::vector<int64_t> blen(ns);
-  HIPCHK(hipMemcpy(blk.data(), RB.blk, blk.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(blen.data(), RB.blen, ns * sizeof(int64_t), hipMemcpyDeviceToHost));
-  std::vector<int64_t> bptr(ns + 1, 0);
-  for (int64_t k = 0; k < ns; ++k) bptr[k + 1] = bptr[k] + blen[k];
-  std::vector<int32_t> mem(bptr[ns]);
-  for (int64_t k = 0; k < ns; ++k) std::copy(blk.begin() + k * mm, blk.begin() + k * mm + blen[k], mem.begin() + bptr[k]);
-  std::vector<int32_t>().swap(blk);
-  std::vector<int32_t> colour;
-  {
-    std::vector<int64_t> aptr(n + 1);
-    std::vector<int32_t> acol(A0d.nnz);
-    HIPCHK(hipMemcpy(aptr.data(), A0d.ptr, (n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(acol.data(), A0d.col, A0d.nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
-    CsrView Av;
-    Av.n = Av.m = n; Av.ptr = aptr.data(); Av.col = acol.data();
-    ring_colouring(Av, bptr, mem, &colour);
-  }
-  int nrc = 0;
-  for (int32_t c : colour) nrc = std::max(nrc, c + 1);
-  std::vector<int32_t> ord(ns);
-  std::iota(ord.begin(), ord.end(), 0);
-  std::stable_sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) { return colour[a] < colour[b]; });
-  // local node ids (owned first, then ghosts), covered dofs, the colours
-  // writing each node (one bit per ring colour)
-  std::vector<int32_t> loc(nv, -1);
-  for (int64_t i = 0; i < nloc; ++i) loc[P.o0 + i] = (int32_t)i;
-  for (int64_t g = 0; g < ng; ++g) loc[P.ghosts[g]] = (int32_t)(nloc + g);
-  const int CW = (nrc + 63) / 64;
-  std::vector<uint64_t> wr((size_t)nv * std::max(CW, 1), 0);
-  std::vector<uint8_t> cov(nv, 0);
-  for (int64_t k = 0; k < ns; ++k)
-    for (int64_t t = bptr[k]; t < bptr[k + 1]; ++t) {
-      const int64_t gd = mem[t], I = gd % nv, f = gd / nv;
-      cov[I] |= (uint8_t)(1u << f);
-      wr[(size_t)I * CW + colour[k] / 64] |= 1ull << (colour[k] % 64);
-    }
-  // the rank's blocks: a member node owned, colour by colour (seed order inside)
-  DLevel& RL = D->rl;
-  RL.rcs.assign(nrc + 1, 0);
-  std::vector<int32_t> mine;
-  std::vector<int64_t> mo(1, 0), io(1, 0);
-  std::vector<int32_t> rm;
-  for (int64_t j = 0; j < ns; ++j) {
-    const int32_t k = ord[j];
-    bool own = false;
-    for (int64_t t = bptr[k]; t < bptr[k + 1] && !own; ++t) {
-      const int64_t I = mem[t] % nv;
-      own = I >= P.o0 && I < P.o1;
-    }
-    if (!own) continue;
-    for (int64_t t = bptr[k]; t < bptr[k + 1]; ++t) {
-      const int64_t gd = mem[t], I = gd % nv, f = gd / nv;
-      if (loc[I] < 0) {
-        *err = "multi-GPU seed rings: a block member outside the rank's " + std::to_string(2 * L + 1) +
-               "-hop ghost region";
-        return MAMG_ERR_SETUP;
-      }
-      rm.push_back(2 * loc[I] + (int32_t)f);
-    }
-    mine.push_back(k);
-    mo.push_back(mo.back() + blen[k]);
-    io.push_back(io.back() + blen[k] * blen[k]);
-    ++RL.rcs[colour[k] + 1];
-  }
-  for (int c = 0; c < nrc; ++c) RL.rcs[c + 1] += RL.rcs[c];
-  const int64_t nb = (int64_t)mine.size();
-  RL.n = 2 * nl;
-  RL.rnm = mo.back();
-  RL.rinv_n = (double)io.back();
-  if ((rc = ddalloc(h, &RL.rmo, nb + 1, err)) || (rc = ddalloc(h, &RL.rio, nb + 1, err)) ||
-      (rc = ddalloc(h, &RL.rmem, std::max<int64_t>(RL.rnm, 1), err)) ||
-      (rc = ddalloc(h, &RL.rinv, std::max<int64_t>(io.back(), 1), err)))
-    return rc;
-  HIPCHK(hipMemcpy(RL.rmo, mo.data(), (nb + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(RL.rio, io.data(), (nb + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-  if (RL.rnm) HIPCHK(hipMemcpy(RL.rmem, rm.data(), rm.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  if (nb) {
-    int32_t* dmine = nullptr;
-    if ((rc = T.alloc(&dmine, nb, err))) return rc;
-    HIPCHK(hipMemcpy(dmine, mine.data(), nb * sizeof(int32_t), hipMemcpyHostToDevice));
-    ring_perm_inv_kernel<<<(unsigned)nb, 256>>>(nb, dmine, RB.blen, RB.sq, RB.inv, RL.rio, RL.rinv);
-    HIPCHK(hipGetLastError());
-  }
-  // the block rows: A_0's node rows of the local nodes within 2 L hops,
-  // local columns (the ring kernel reads x through them)
-  TBsr B;
-  if ((rc = dev_csr_to_bsr(&T, A0d, nv, nv, &B, err))) return rc;
-  int8_t *hop = nullptr, *hop2 = nullptr;
-  if ((rc = T.alloc(&hop, nv, err)) || (rc = T.alloc(&hop2, nv, err))) return rc;
-  hop_init_kernel<<<nblocks(nv), 256>>>(nv, P.o0, P.o1, hop);
-  for (int k = 1; k <= 2 * L; ++k) {
-    hop_step_kernel<<<nblocks(nv), 256>>>(nv, B.ptr, B.col, hop, hop2, k);
-    std::swap(hop, hop2);
-  }
-  HIPCHK(hipGetLastError());
-  int64_t* gh = nullptr;
-  if ((rc = T.alloc(&gh, std::max<int64_t>(ng, 1), err))) return rc;
-  if (ng) HIPCHK(hipMemcpy(gh, P.ghosts.data(), ng * sizeof(int64_t), hipMemcpyHostToDevice));
-  int32_t* map = nullptr;
-  if ((rc = dev_col_map(&T, P, &map, err))) return rc;
-  if ((rc = ddalloc(h, &RL.Sptr, nl + 1, err))) return rc;
-  if (nl) srow_len_kernel<<<nblocks(nl), 256>>>(nl, nloc, P.o0, gh, hop, B.ptr, RL.Sptr, 2 * L);
-  HIPCHK(hipGetLastError());
-  if ((rc = dscan_incl_i64(RL.Sptr, RL.Sptr, nl + 1, nullptr, err))) return rc;
-  HIPCHK(hipMemcpy(&RL.Snb, RL.Sptr + nl, sizeof(int64_t), hipMemcpyDeviceToHost));
-  int32_t* sg = nullptr;
-  if ((rc = ddalloc(h, &RL.Scol, std::max<int64_t>(RL.Snb, 1), err)) ||
-      (rc = T.alloc(&sg, std::max<int64_t>(RL.Snb, 1), err)) ||
-      (rc = ddalloc(h, &RL.Sval, std::max<int64_t>(RL.Snb, 1), err)))
-    return rc;
-  if (nl) srow_fill_kernel<<<nblocks(nl), 256>>>(nl, nloc, P.o0, gh, B.ptr, B.col, B.val, map, RL.Sptr, RL.Scol, sg,
-                                                 RL.Sval);
-  HIPCHK(hipGetLastError());
-  // the covered dofs of the owned nodes (the rest's GS masks them)
-  if ((rc = ddalloc(h, cov_owned, std::max<int64_t>(nloc, 1), err))) return rc;
-  if (nloc) HIPCHK(hipMemcpy(*cov_owned, cov.data() + P.o0, nloc, hipMemcpyHostToDevice));
-  // the colour table: ring colours, then the rest GS's node colours
-  std::vector<int8_t> hc(nv);
-  if (nv) HIPCHK(hipMemcpy(hc.data(), gcol, nv, hipMemcpyDeviceToHost));
-  auto in = [&](int64_t I, int idx) {
-    return idx < nrc ? ((wr[(size_t)I * CW + idx / 64] >> (idx % 64)) & 1ull) != 0 : hc[I] == idx - nrc;
-  };
-  const int nct = nrc + ngc;
-  std::vector<int64_t> cs, cg;
-  D->cs_off.assign((size_t)nct * (R + 1), 0);
-  D->cg_off.assign((size_t)nct * (R + 1), 0);
-  for (int idx = 0; idx < nct; ++idx) {
-    for (int q = 0; q < R; ++q) {
-      D->cs_off[(size_t)idx * (R + 1) + q] = (int64_t)cs.size();
-      D->cg_off[(size_t)idx * (R + 1) + q] = (int64_t)cg.size();
-      for (int64_t t = P.send_off[q]; t < P.send_off[q + 1]; ++t)
-        if (in(P.o0 + P.send_idx[t], idx)) cs.push_back(P.send_idx[t]);
-      for (int64_t g = P.ghost_off[q]; g < P.ghost_off[q + 1]; ++g)
-        if (in(P.ghosts[g], idx)) cg.push_back(g);
-    }
-    D->cs_off[(size_t)idx * (R + 1) + R] = (int64_t)cs.size();
-    D->cg_off[(size_t)idx * (R + 1) + R] = (int64_t)cg.size();
-  }
-  if (!cs.empty()) {
-    if ((rc = ddalloc(h, &D->csend_idx, (int64_t)cs.size(), err))) return rc;
-    HIPCHK(hipMemcpy(D->csend_idx, cs.data(), cs.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-  }
-  if (!cg.empty()) {
-    if ((rc = ddalloc(h, &D->cghost_idx, (int64_t)cg.size(), err))) return rc;
-    HIPCHK(hipMemcpy(D->cghost_idx, cg.data(), cg.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-  }
-  D->rings = true;
-  D->nrc = nrc;
-  if (p.print_level >= 2)
-    std::fprintf(stderr, "[mamg] rank %d/%d seed rings: %lld of %lld blocks, %d ring colours + %d GS colours, "
-                 "%lld ghost nodes (%d hops), colour halos %lld sends / %lld receives in all\n", h->rank, R,
-                 (long long)nb, (long long)ns, nrc, ngc, (long long)ng, 2 * L + 1, (long long)cs.size(),
-                 (long long)cg.size());
-  return MAMG_OK;
-}
-
-// each colour's halo of a distributed level: colour c's nodes in every send
-// list and ghost list, in list order (so the sender's subset and the
-// receiver's subset match), offsets per (colour, peer); gcol = the level's
-// global colouring on the device
-int colour_halo_lists(DistHandle* h, const DistLevel& P, const int8_t* gcol, int ncol, DDLevel* D,
-                      std::string* err) {
-  const int R = h->nranks;
-  std::vector<int8_t> hc(P.nv);
-  if (P.nv) HIPCHK(hipMemcpy(hc.data(), gcol, P.nv, hipMemcpyDeviceToHost));
-  std::vector<int64_t> cs, cg;
-  D->cs_off.assign((size_t)ncol * (R + 1), 0);
-  D->cg_off.assign((size_t)ncol * (R + 1), 0);
-  for (int c = 0; c < ncol; ++c) {
-    for (int q = 0; q < R; ++q) {
-      D->cs_off[(size_t)c * (R + 1) + q] = (int64_t)cs.size();
-      D->cg_off[(size_t)c * (R + 1) + q] = (int64_t)cg.size();
-      for (int64_t t = P.send_off[q]; t < P.send_off[q + 1]; ++t)
-        if (hc[P.o0 + P.send_idx[t]] == c) cs.push_back(P.send_idx[t]);
-      for (int64_t g = P.ghost_off[q]; g < P.ghost_off[q + 1]; ++g)
-        if (hc[P.ghosts[g]] == c) cg.push_back(g);
-    }
-    D->cs_off[(size_t)c * (R + 1) + R] = (int64_t)cs.size();
-    D->cg_off[(size_t)c * (R + 1) + R] = (int64_t)cg.size();
-  }
-  int rc;
-  if (!cs.empty()) {
-    if ((rc = ddalloc(h, &D->csend_idx, (int64_t)cs.size(), err))) return rc;
-    HIPCHK(hipMemcpy(D->csend_idx, cs.data(), cs.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-  }
-  if (!cg.empty()) {
-    if ((rc = ddalloc(h, &D->cghost_idx, (int64_t)cg.size(), err))) return rc;
-    HIPCHK(hipMemcpy(D->cghost_idx, cg.data(), cg.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-  }
-  return MAMG_OK;
-}
-
-// the longest run [*r0, *r1) of M's rows whose columns are all < nown (owned:
-// no ghost), for the launches during a halo
-constexpr int64_t K_ROWS_ALIGN = 256;   // launch_msell row ranges: whole workgroups of every LPR
-int ghost_free_run(TmpPool* T, const TBsr& M, int64_t nown, int64_t* r0, int64_t* r1, std::string* err) {
-  int rc;
-  const int64_t n = M.nr;
-  uint8_t* fl = nullptr;
-  if ((rc = T->alloc(&fl, n, err))) return rc;
-  if (n) ghost_row_kernel<<<nblocks(n), 256>>>(n, M.ptr, M.col, (int32_t)nown, fl);
-  HIPCHK(hipGetLastError());
-  std::vector<uint8_t> hf(n);
-  if (n) HIPCHK(hipMemcpy(hf.data(), fl, n, hipMemcpyDeviceToHost));
-  int64_t best0 = 0, best1 = 0, run0 = 0;
-  for (int64_t I = 0; I <= n; ++I)
-    if (I == n || hf[I]) {
-      if (I - run0 > best1 - best0) { best0 = run0; best1 = I; }
-      run0 = I + 1;
-    }
-  *r0 = best0;
-  *r1 = best1;
-  return MAMG_OK;
-}
-
-// level l's A_loc (+ overlap window, band schedule), K / [P | AP] / P, R_loc
-// and W from the GPU hierarchy (the operator block of dist_upload)
-int dev_rank_ops(DistHandle* h, const GHier& G, const DevMat& A0d, const DistPlan& plan, int l, double kw,
-                 const int8_t* gcol, int ncol, std::string* err) {
-  int rc;
-  const DistLevel& P = plan.levels[l];
-  const GLevel& g = G.levels[l];
-  DDLevel& D = h->L[l];
-  const int64_t nv = P.nv, nloc = P.nloc, nc = nloc + (int64_t)P.ghosts.size();
-  TmpPool T(h->sw);
-  int32_t* map = nullptr;
-  if (!P.replicated && (rc = dev_col_map(&T, P, &map, err))) return rc;
-  // W (node blocks of the owned rows)
-  if ((rc = ddalloc(h, &D.W, nloc, err))) return rc;
-  if (nloc) {
-    HIPCHK(dev_copy(D.W, reinterpret_cast<const dv4*>(g.W) + P.o0, nloc * sizeof(dv4)));
-    if (g.joined) unjoin_kernel<<<nblocks(nloc), 256>>>(nloc, g.joined + P.o0, D.W);
-    HIPCHK(hipGetLastError());
-  }
-  // A_loc (+ the multicolour GS layout of its rows, colours of the level's
-  // global colouring gcol)
-  {
-    TBsr raw, tA;
-    const DevMat& Am = l == 0 ? A0d : g.A;
-    if ((rc = dev_rows_to_bsr(&T, Am, nv, nv, nloc, nullptr, P.o0, &raw, err))) return rc;
-    if (P.replicated) tA = raw;
-    else if ((rc = dev_map_cols(&T, raw, map, nloc, nc, &tA, err))) return rc;
-    if (!P.replicated && (rc = ghost_free_run(&T, tA, nloc, &D.ib0, &D.ib1, err)))   // overlap window
-      return rc;
-    bool half = false;
-    if (l == 0 && h->sw.half && tA.nr >= h->sw.sell_min_rows && tA.nb > 0) {   // upload_half_or_bsr
-      int* bad = nullptr;
-      if ((rc = T.alloc(&bad, 1, err))) return rc;
-      HIPCHK(dev_memset(bad, 0, sizeof(int)));
-      sym_check_kernel<<<std::min(nblocks(tA.nb), SYM_CHECK_BLOCKS), 256>>>(tA.nb, tA.val, bad);
-      int hb = 1;
-      HIPCHK(hipMemcpy(&hb, bad, sizeof(int), hipMemcpyDeviceToHost));
-      if (hb == 0) {
-        D.A.nr = tA.nr; D.A.nc = tA.nc; D.A.nb = tA.nb;
-        D.A.lanes = pick_lanes_bsr(tA.nr, tA.nb);
-        D.A.sym = true;
-        if ((rc = try_half(h, &T, tA, &D.A, err))) return rc;
-        half = D.A.half;
-      }
-    }
-    if (!half && (rc = finalize_bsr(h, &T, tA, &D.A, 0, true, err))) return rc;
-    if (l == 0 && (rc = build_band_sched_range(h, &D.A, D.ib0, D.ib1, err))) return rc;
-    if (gcol) {
-      // seed rings: the rest's GS, covered dofs masked (build_rings' rest_w /
-      // rest_mask on the owned rows)
-      const double* Wg = reinterpret_cast<const double*>(D.W);
-      if (D.rcov && nloc) {
-        dv4* Wp = nullptr;
-        if ((rc = T.alloc(&Wp, nloc, err))) return rc;
-        rest_w_kernel<<<nblocks(nloc), 256>>>(nloc, D.W, D.rcov, Wp);
-        HIPCHK(hipGetLastError());
-        Wg = reinterpret_cast<const double*>(Wp);
-      }
-      if ((rc = gs_layout(h, &T, tA, Wg, gcol + P.o0, ncol, l, &D.Gb, &D.gperm, &D.Gd, &D.gcs, &D.gbk, err)))
-        return rc;
-      const int64_t nrp = D.gcs.empty() ? 0 : D.gcs.back();
-      if (D.rcov && nrp) rest_mask_kernel<<<nblocks(nrp), 256>>>(nrp, D.gperm, D.rcov, D.Gd);
-      HIPCHK(hipGetLastError());
-    }
-  }
-  // prolongation side (level l+1 numbering)
-  const DistLevel& C = plan.levels[l + 1];
-  const int64_t cnc = C.replicated ? C.nv : C.nloc + (int64_t)C.ghosts.size();
-  int32_t* cmap = nullptr;
-  if (!C.replicated && (rc = dev_col_map(&T, C, &cmap, err))) return rc;
-  auto rows_c = [&](const DevMat& M, TBsr* O) -> int {   // rows [o0, o1) of a fine x coarse CSR
-    TBsr raw;
-    int r = dev_rows_to_bsr(&T, M, nv, C.nv, nloc, nullptr, P.o0, &raw, err);
-    if (r) return r;
-    if (C.replicated) { *O = raw; return MAMG_OK; }
-    return dev_map_cols(&T, raw, cmap, C.nloc, cnc, O, err);
-  };
-  TBsr tP;
-  if ((rc = rows_c(g.P, &tP))) return rc;
-  if (plan.fuse) {
-    TBsr tAP, tK;
-    if ((rc = rows_c(g.AP, &tAP))) return rc;
-    if (plan.kpost) {
-      const double* Wk = reinterpret_cast<const double*>(D.W);
-      if (kw != 1.0 && nloc) {
-        double* q = nullptr;
-        if ((rc = T.alloc(&q, 4 * nloc, err))) return rc;
-        wscale_kernel<<<nblocks(4 * nloc), 256>>>(4 * nloc, kw, Wk, q);
-        HIPCHK(hipGetLastError());
-        Wk = q;
-      }
-      if ((rc = dev_kmerge(&T, tP, tAP, Wk, &tK, err))) return rc;
-      if ((rc = finalize_bsr(h, &T, tK, &D.K, 0, false, err))) return rc;
-      D.K.kvar = h->sw.k_variant;
-      if (l == 0 && h->sw.k_sort && D.K.sell && D.K.lpr <= 1)   // rows sorted inside slices (section 4.1)
-        if ((rc = sort_sell_slices(h, &T, &D.K, err))) return rc;
-      // K's rows without coarse ghost columns, run while the coarse-e halo is
-      // in flight (level 0's SELL K: launch_msell takes row ranges)
-      if (l == 0 && !P.replicated && !C.replicated) {
-        int64_t k0 = 0, k1 = 0;
-        if ((rc = ghost_free_run(&T, tK, C.nloc, &k0, &k1, err))) return rc;
-        k0 = (k0 + K_ROWS_ALIGN - 1) / K_ROWS_ALIGN * K_ROWS_ALIGN;
-        k1 = k1 == nloc ? nloc : k1 / K_ROWS_ALIGN * K_ROWS_ALIGN;
-        if (k1 > k0) { D.kb0 = k0; D.kb1 = k1; }
-      }
-    } else {
-      if ((rc = dev_merge_rows(&T, tP, tAP, &tK, err))) return rc;
-      if ((rc = finalize_bsr(h, &T, tK, &D.PA, 0, false, err))) return rc;
-    }
-  } else if ((rc = finalize_bsr(h, &T, tP, &D.P, 0, false, err))) {
-    return rc;
-  }
-  // partial restriction R_loc = P_loc^T: R's rows of the local coarse nodes
-  // ([owned | ghost], or all when replicated), columns in [o0, o1)
-  {
-    std::vector<int64_t> rows;
-    rows.reserve(cnc);
-    if (C.replicated) {
-      for (int64_t J = 0; J < C.nv; ++J) rows.push_back(J);
-    } else {
-      for (int64_t J = C.o0; J < C.o1; ++J) rows.push_back(J);
-      rows.insert(rows.end(), C.ghosts.begin(), C.ghosts.end());
-    }
-    int64_t* drows = nullptr;
-    if ((rc = T.alloc(&drows, cnc, err))) return rc;
-    if (cnc) HIPCHK(hipMemcpy(drows, rows.data(), cnc * sizeof(int64_t), hipMemcpyHostToDevice));
-    TBsr raw, tR;
-    if ((rc = dev_rows_to_bsr(&T, g.R, C.nv, nv, cnc, drows, 0, &raw, err))) return rc;
-    if ((rc = dev_window_cols(&T, raw, P.o0, P.o1, &tR, err))) return rc;
-    if ((rc = finalize_bsr(h, &T, tR, &D.R, 0, false, err))) return rc;
-  }
-  return MAMG_OK;
-}
-
-int upload_dcsr(DistHandle* h, const Csr& M, DCsr* D, int lanes, std::string* err) {
-  D->n = M.n;
-  D->m = M.m;
-  D->nnz = M.nnz();
-  D->lanes = lanes > 0 ? lanes : pick_lanes(M.n, D->nnz);
-  int rc;
-  if ((rc = ddalloc(h, &D->ptr, M.n + 1, err))) return rc;
-  if ((rc = ddalloc(h, &D->col, std::max<int64_t>(D->nnz, 1), err))) return rc;
-  if ((rc = ddalloc(h, &D->val, std::max<int64_t>(D->nnz, 1), err))) return rc;
-  if (M.ptr.size() == (size_t)M.n + 1)
-    HIPCHK(hipMemcpy(D->ptr, M.ptr.data(), (M.n + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-  if (D->nnz) {
-    HIPCHK(hipMemcpy(D->col, M.col.data(), D->nnz * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(D->val, M.val.data(), D->nnz * sizeof(double), hipMemcpyHostToDevice));
-  }
-  return MAMG_OK;
-}
-
-// one level of a scalar (CSR) plan: A_loc / P_loc / Rp_loc, the WB rows or
-// the winv slice, POLY's step smoothers (values only, as poly_scaled), the
-// dense inverse in natural order, and the level-0 interior row run
-int upload_scalar_level(DistHandle* h, const HostLevel& hl, const DistLevel& P, int l, int pm, const double* pw,
-                        std::string* err) {
-  DDLevel& D = h->L[l];
-  int rc;
-  if ((rc = upload_dcsr(h, P.cA, &D.cA, l == 0 ? h->p.spmv_lanes : 0, err))) return rc;
-  if (D.coarsest) {
-    const int64_t n = hl.n;
-    if ((rc = ddalloc(h, &D.Ainv, n * n, err))) return rc;
-    HIPCHK(hipMemcpy(D.Ainv, hl.Ainv.data(), n * n * sizeof(double), hipMemcpyHostToDevice));
-    return MAMG_OK;
-  }
-  if ((rc = upload_dcsr(h, P.cP, &D.cP, 0, err))) return rc;
-  if ((rc = upload_dcsr(h, P.cRp, &D.cR, 0, err))) return rc;
-  const bool blk = P.cWB.n > 0;
-  if (blk) {
-    if ((rc = upload_dcsr(h, P.cWB, &D.cWB, 0, err))) return rc;
-  } else {
-    if ((int64_t)P.W.size() != D.nloc) { *err = "scalar plan: winv slice does not cover the owned rows"; return MAMG_ERR_ARG; }
-    if ((rc = ddalloc(h, &D.winv, D.nloc, err))) return rc;
-    if (D.nloc) HIPCHK(hipMemcpy(D.winv, P.W.data(), D.nloc * sizeof(double), hipMemcpyHostToDevice));
-  }
-  if (h->p.smoother == MAMG_SMOOTHER_POLY) {
-    const int64_t n = blk ? D.cWB.nnz : D.nloc;
-    const double* src = blk ? D.cWB.val : D.winv;
-    for (int k = 0; k < pm; ++k) {
-      double* q = nullptr;
-      if ((rc = ddalloc(h, &q, std::max<int64_t>(n, 1), err))) return rc;
-      if (n) wscale_kernel<<<nblocks(n), 256>>>(n, pw[k], src, q);
-      HIPCHK(hipGetLastError());
-      if (blk) {
-        DCsr c = D.cWB;
-        c.val = q;
-        D.cWBk.push_back(c);
-      } else {
-        D.winvk.push_back(q);
-      }
-    }
-  }
-  if (l == 0 && !P.replicated) {   // longest run of A_loc rows without ghost columns
-    int64_t best0 = 0, best1 = 0, run0 = 0;
-    for (int64_t i = 0; i <= P.cA.n; ++i) {
-      // rows are sorted by local column: the last entry tells
-      const bool ghost = i == P.cA.n || (P.cA.ptr[i + 1] > P.cA.ptr[i] && P.cA.col[P.cA.ptr[i + 1] - 1] >= P.nloc);
-      if (ghost) {
-        if (i - run0 > best1 - best0) { best0 = run0; best1 = i; }
-        run0 = i + 1;
-      }
-    }
-    D.ib0 = best0;
-    D.ib1 = best1;
-  }
-  return MAMG_OK;
-}
-
-}  // namespace
-
-int dist_check(const mamg_params& p, std::string* err) {
-  if (p.maxit != 1) {
-    *err = "multi-GPU apply supports maxit 1 (one cycle per application, src/amg_parameters.py:71)";
-    return MAMG_ERR_UNSUPPORTED;
-  }
-  if (int rc = dist_layout_check(p, err)) return rc;   // scalar (CSR) or nodal (BSR2) hierarchies (dist.cpp)
-  return MAMG_OK;
-}
-
-int dist_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, const Switches& sw, int rank,
-                int nranks, const void* comm_id, int64_t rep_nodes, DistHandle** out, std::string* err,
-                const GhostLists* ghosts, const GHier* G, const DevMat* A0d) {
-  if (int rc = dist_check(p, err)) return rc;
-  const bool gs = gs_smoother(p);
-  const bool patches = patch_schwarz(p);
-  const bool rings = rings_schwarz(p);
-  if ((patches || rings) && !(G && A0d && ghosts)) {
-    *err = std::string("multi-GPU ") + (patches ? "node patches need the rank operators and the 3-hop" :
-           "seed rings need the rank operators and the (2 Schwarz_maxlvl + 1)-hop") +
-           " ghost lists built from the GPU hierarchy (mamg_setup_dist with a GPU-setup profile)";
-    return MAMG_ERR_UNSUPPORTED;
-  }
-  if (gs && !G) {
-    *err = "multi-GPU multicolour GS needs the rank operators built from the GPU hierarchy (mamg_setup_dist "
-           "with a GPU-setup profile)";
-    return MAMG_ERR_UNSUPPORTED;
-  }
-  double pw[MAMG_POLY_MAX];
-  const int pm = poly_weights(p, pw);
-  DistPlan plan;
-  const auto tp0 = std::chrono::steady_clock::now();
-  const double kw = p.smoother == MAMG_SMOOTHER_POLY ? pw[pm - 1] : 1.0;
-  bool fuse = p.post_fusion != 0 && !gs && !patches && !rings;   // GS / patches / rings post-smooth after x += P e (as on one GPU)
-  if (G)                   // operators from the GPU hierarchy: fusion needs its A P on every level
-    for (size_t l = 0; l + 1 < G->levels.size() && fuse; ++l)
-      if (!G->levels[l].coarsest && G->levels[l].AP.n != G->levels[l].n) fuse = false;
-  int rc = build_dist_plan(H, A0, rank, nranks, rep_nodes, fuse, &plan, err, sw.post_k != 0, kw, ghosts,
-                           G != nullptr);
-  if (rc) return rc;
-  if (p.print_level >= 2)
-    std::fprintf(stderr, "[mamg] rank %d/%d setup:   of which host plan    %.3f s\n", rank, nranks,
-                 std::chrono::duration<double>(std::chrono::steady_clock::now() - tp0).count());
-  std::unique_ptr<DistHandle> h(new DistHandle(sw));
-  h->p = p;
-  h->rank = rank;
-  h->nranks = nranks;
-  h->w = plan.dofs;
-  h->device = p.device;
-  adopt_prereserve(h.get(), h->device);
-  HIPCHK(hipSetDevice(p.device));
-  if (comm_id) {                         // RCCL communicator; NULL = virtual (tests)
-    ncclUniqueId uid;
-    std::memcpy(&uid, comm_id, sizeof(uid));
-    NCCLCHK(ncclCommInitRank(&h->comm, nranks, uid, rank));
-  }
-  h->dry = !comm_id && sw.dist_test == "dry";
-  HIPCHK(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-  HIPCHK(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming));
-  const int nl = (int)plan.levels.size();
-  h->L.resize(nl);
-  for (int l = 0; l < nl; ++l) {
-    DistLevel& P = plan.levels[l];
-    DDLevel& D = h->L[l];
-    D.nv = P.nv;
-    D.nloc = P.nloc;
-    D.ng = (int64_t)P.ghosts.size();
-    D.replicated = P.replicated;
-    D.coarsest = P.coarsest;
-    D.send_off = P.send_off;
-    D.ghost_off = P.ghost_off;
-    if (h->w == 1) {   // scalar level: the plan's CSR operators as they are
-      if ((rc = upload_scalar_level(h.get(), H.levels[l], P, l, pm, pw, err))) return rc;
-    } else if (D.coarsest) {
-      const HostLevel& hl = H.levels[l];
-      const int64_t n = hl.n, nv = n / 2;
-      std::vector<double> Ap(n * n);
-      auto pos = [nv](int64_t i) { return 2 * (i % nv) + i / nv; };
-      for (int64_t i = 0; i < n; ++i)
-        for (int64_t j = 0; j < n; ++j) Ap[pos(i) * n + pos(j)] = hl.Ainv[i * n + j];
-      if ((rc = ddalloc(h.get(), &D.Ainv, n * n, err))) return rc;
-      HIPCHK(hipMemcpy(D.Ainv, Ap.data(), n * n * sizeof(double), hipMemcpyHostToDevice));
-    } else if (G) {
-      // multicolour GS: the level's global colouring (every rank computes the
-      // same one, as the single-GPU build_gs), then each colour's halo lists
-      TmpPool TC(h->sw);
-      int8_t* gcol = nullptr;
-      int ncol = 0;
-      const bool rl0 = l == 0 && rings && !G->seeds.empty();   // level-0 seed rings + the rest's GS
-      if ((gs || rl0) && !(l == 0 && patches)) {
-        TBsr B;
-        if ((rc = dev_csr_to_bsr(&TC, l == 0 ? *A0d : G->levels[l].A, D.nv, D.nv, &B, err))) return rc;
-        if ((rc = gs_colour(&TC, B, l, &gcol, &ncol, err))) return rc;
-        TC.release(B.ptr); TC.release(B.col); TC.release(B.val);
-        if (rl0) {
-          if ((rc = dist_rings(h.get(), *A0d, P, G->seeds, gcol, ncol, &D, &D.rcov, err))) return rc;
-        } else if (!D.replicated && (rc = colour_halo_lists(h.get(), P, gcol, ncol, &D, err))) {
-          return rc;
-        }
-      }
-      if ((rc = dev_rank_ops(h.get(), *G, *A0d, plan, l, kw, gcol, ncol, err))) return rc;
-      if (l == 0 && patches && !D.coarsest && (rc = dist_patches(h.get(), *A0d, P, &D, err))) return rc;
-    } else {
-      // longest run of rows without ghost columns (columns < nown): the
-      // overlap windows, as ghost_free_run on the device path
-      auto run_of = [](const HBsr& M, int64_t nown, int64_t* r0, int64_t* r1) {
-        int64_t best0 = 0, best1 = 0, run0 = 0;
-        for (int64_t I = 0; I <= M.nr; ++I) {
-          bool ghost = I == M.nr;
-          for (int64_t k = I < M.nr ? M.ptr[I] : 0; !ghost && k < M.ptr[I + 1]; ++k)
-            ghost = M.col[k] >= nown;
-          if (ghost) {
-            if (I - run0 > best1 - best0) { best0 = run0; best1 = I; }
-            run0 = I + 1;
-          }
-        }
-        *r0 = best0;
-        *r1 = best1;
-      };
-      if (!P.replicated) run_of(P.A, P.A.nr, &D.ib0, &D.ib1);
-      if (l == 0 && !P.replicated && !plan.levels[1].replicated && P.K.nr > 0) {
-        int64_t k0 = 0, k1 = 0;
-        run_of(P.K, plan.levels[1].nloc, &k0, &k1);
-        k0 = (k0 + K_ROWS_ALIGN - 1) / K_ROWS_ALIGN * K_ROWS_ALIGN;
-        k1 = k1 == P.K.nr ? P.K.nr : k1 / K_ROWS_ALIGN * K_ROWS_ALIGN;
-        if (k1 > k0) { D.kb0 = k0; D.kb1 = k1; }
-      }
-      if (l == 0) {
-        if ((rc = upload_half_or_bsr(h.get(), P.A, &D.A, err))) return rc;
-        if ((rc = build_band_sched_range(h.get(), &D.A, D.ib0, D.ib1, err))) return rc;
-      } else if ((rc = upload_bsr(h.get(), P.A, &D.A, 0, err, true))) {
-        return rc;
-      }
-      if (P.K.nr > 0) {
-        if ((rc = upload_bsr(h.get(), P.K, &D.K, 0, err))) return rc;
-        D.K.kvar = h->sw.k_variant;
-      } else if (P.PA.nr > 0) {
-        if ((rc = upload_bsr(h.get(), P.PA, &D.PA, 0, err))) return rc;
-      } else {
-        if ((rc = upload_bsr(h.get(), P.P, &D.P, 0, err))) return rc;
-      }
-      if ((rc = upload_bsr(h.get(), P.Rp, &D.R, 0, err))) return rc;
-      if ((rc = ddalloc(h.get(), &D.W, D.nloc, err))) return rc;
-      HIPCHK(hipMemcpy(D.W, P.W.data(), 4 * D.nloc * sizeof(double), hipMemcpyHostToDevice));
-    }
-    if (!D.coarsest && h->w == 2) {
-      if (p.smoother == MAMG_SMOOTHER_POLY) {   // w_k W as on one GPU (poly_scaled)
-        for (int k = 0; k < pm; ++k) {
-          dv4* q = nullptr;
-          if ((rc = ddalloc(h.get(), &q, D.nloc, err))) return rc;
-          if (D.nloc)
-            wscale_kernel<<<nblocks(4 * D.nloc), 256>>>(4 * D.nloc, pw[k], reinterpret_cast<const double*>(D.W),
-                                                         reinterpret_cast<double*>(q));
-          HIPCHK(hipGetLastError());
-          D.Wk.push_back(q);
-        }
-      }
-    }
-    const int64_t full = D.nloc + D.ng;
-    const int w = h->w;
-    if ((rc = ddalloc(h.get(), &D.b, w * full, err))) return rc;
-    if ((rc = ddalloc(h.get(), &D.x, w * full, err))) return rc;
-    if ((rc = ddalloc(h.get(), &D.t, w * full, err))) return rc;
-    if ((rc = ddalloc(h.get(), &D.t2, w * full, err))) return rc;
-    if ((rc = ddalloc(h.get(), &D.r, w * full, err))) return rc;
-    if (l == 0 && !D.coarsest && (rc = ddalloc(h.get(), &D.spx, w * full, err))) return rc;
-    if ((D.patches || D.rings) && (rc = ddalloc(h.get(), &D.pb, w * full, err))) return rc;
-    if (D.cWB.n > 0 && (rc = ddalloc(h.get(), &D.gb, full, err))) return rc;
-    if (l > 0 && p.cycle_type == MAMG_W_CYCLE) {
-      if ((rc = ddalloc(h.get(), &D.c, w * full, err))) return rc;
-      if ((rc = ddalloc(h.get(), &D.e, w * full, err))) return rc;
-    }
-    if (l > 0 && p.coarse_scaling) {
-      if ((rc = ddalloc(h.get(), &D.q, w * full, err))) return rc;
-      if ((rc = ddalloc(h.get(), &D.part2, 2 * SCALE_BLOCKS, err))) return rc;
-    }
-    const int64_t ns = P.send_idx.size();
-    // colour halos: a node in the lists of every colour that writes it (node
-    // patches), so their totals may exceed the plain lists
-    const int64_t tcs = D.cs_off.empty() ? 0 : D.cs_off.back(), tcg = D.cg_off.empty() ? 0 : D.cg_off.back();
-    if (ns) {
-      if ((rc = ddalloc(h.get(), &D.send_idx, ns, err))) return rc;
-      HIPCHK(hipMemcpy(D.send_idx, P.send_idx.data(), ns * sizeof(int64_t), hipMemcpyHostToDevice));
-    }
-    if (std::max(ns, tcs) > 0 && (rc = ddalloc(h.get(), &D.sendbuf, w * std::max(ns, tcs), err))) return rc;
-    const int64_t nrcv = std::max(std::max(ns, D.ng), tcg);
-    if (nrcv > 0 && (rc = ddalloc(h.get(), &D.recvbuf, w * nrcv, err))) return rc;
-  }
-  h->nv0 = plan.levels[0].nv;
-  h->o0 = plan.levels[0].o0;
-  h->o1 = plan.levels[0].o1;
-  // the rank-local operators are not re-homed: they are plain allocations
-  // made after the setup already, and a second copy measured 204-208 vs
-  // 209-214 applies/s (2 ranks, one GPU, profiles/r02_bench_2rank_rehome_ab.txt)
-  std::vector<DOp> ops;
-  dapply_ops(h.get(), nullptr, nullptr, &ops);
-  for (const DOp& d : ops) h->apply_bytes += d.bytes;
-  HIPCHK(null_sync());
-  *out = h.release();
-  return MAMG_OK;
-}
-
-void dist_destroy(DistHandle* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  if (h->last) (void)hipEventSynchronize(h->last);   // the last apply / spmv / timing on any stream
-  if (h->side) (void)hipStreamSynchronize(h->side);
-  delete h;
-}
-
-int dist_dofs(const DistHandle* h) { return h->w; }
-const Switches& dist_switches(const DistHandle* h) { return h->sw; }
-
-void dist_range(const DistHandle* h, int64_t* o0, int64_t* o1, int64_t* nv) {
-  *o0 = h->o0; *o1 = h->o1; *nv = h->nv0;
-}
-
-double dist_apply_bytes(const DistHandle* h) { return h->apply_bytes; }
-
-int dist_num_levels(const DistHandle* h) { return (int)h->L.size(); }
-
-// mamg_level_format's bits for the rank-local operators of a nodal level (0
-// on a scalar handle: its levels are plain CSR)
-int dist_level_format(const DistHandle* h, int level) {
-  const DDLevel& D = h->L[level];
-  if (h->w != 2) return 0;
-  return (D.A.sell ? MAMG_FMT_SELL : 0) | (D.A.sym ? MAMG_FMT_SYM : 0) | (D.A.half ? MAMG_FMT_HALF : 0) |
-         (D.PA.nr > 0 || D.K.nr > 0 ? MAMG_FMT_POST_FUSED : 0) | (D.K.nr > 0 ? MAMG_FMT_POST_K : 0) |
-         (D.K.sell ? MAMG_FMT_POST_SELL : 0) | (D.A.nsched > 0 || D.A.nsched_r > 0 ? MAMG_FMT_BANDS : 0) |
-         (D.patches ? MAMG_FMT_PATCHES : 0) | (D.gcs.size() > 1 ? MAMG_FMT_GS : 0) |
-         (D.rings ? MAMG_FMT_RINGS : 0) | (D.R.nrsched > 0 ? MAMG_FMT_R_BANDS : 0) |
-         (D.K.col16 ? MAMG_FMT_K_COL16 : 0);
-}
-
-// ---------------------------------------------------------------------------
-// fp32 storage of the operators a rank's cycle streams
-// (mamg_dist_set_cycle_storage): dev_set_cycle_storage
-// on the rank-local operators.  A_loc (level 0: both value arrays of the
-// half-symmetric form, owned part and ghost part), K_loc or plain P_loc and
-// the partial restriction of every level above the coarsest become fp32
-// copies in the same layout; W / Wk, the coarsest inverse, the merged
-// [P_loc | AP_loc], every vector and every exchange buffer stay fp64, and so
-// does level 0's A_loc itself (dspmv_ops: the Krylov operator), whose index
-// arrays the fp32 copy Ac shares.  No communication: every rank calls it.
-// ---------------------------------------------------------------------------
-int dist_level_storage(const DistHandle* h, int level) { return h->L[level].storage; }
-
-int dist_cycle_storage(const DistHandle* h) {
-  for (const DDLevel& D : h->L)
-    if (D.storage != 0) return MAMG_STORE_F32;
-  return MAMG_STORE_F64;
-}
-
-int dist_set_cycle_storage(DistHandle* h, int storage, std::string* err) {
-  std::lock_guard<std::recursive_mutex> lock(capture_mutex());
-  const bool narrowed = dist_cycle_storage(h) == MAMG_STORE_F32;
-  if (storage == MAMG_STORE_F64) {
-    if (!narrowed) return MAMG_OK;
-    *err = "cycle storage: the fp64 originals of a narrowed handle are gone (fp32 storage is one way)";
-    return MAMG_ERR_UNSUPPORTED;
-  }
-  if (narrowed) return MAMG_OK;
-  if (h->w != 2) {
-    *err = "cycle storage: fp32 needs the BSR2 layout (this rank handle holds a scalar hierarchy in the CSR layout)";
-    return MAMG_ERR_UNSUPPORTED;
-  }
-  for (const DDLevel& D : h->L) {
-    if (D.patches) { *err = "cycle storage: fp32 is not available with SCHWARZ_PATCHES"; return MAMG_ERR_UNSUPPORTED; }
-    if (D.rings) { *err = "cycle storage: fp32 is not available with SCHWARZ_RINGS"; return MAMG_ERR_UNSUPPORTED; }
-    if (D.gcs.size() > 1) { *err = "cycle storage: fp32 is not available with the GS / SGS smoothers"; return MAMG_ERR_UNSUPPORTED; }
-  }
-  if (gs_smoother(h->p) || patch_schwarz(h->p) || rings_schwarz(h->p)) {
-    *err = "cycle storage: fp32 is not available with the GS / SGS smoothers or the Schwarz smoothers";
-    return MAMG_ERR_UNSUPPORTED;
-  }
-  HIPCHK(hipSetDevice(h->device));
-  std::vector<NarrowJob> jobs;
-  auto add = [&](DBsr* src, DBsr* dst) {
-    if (value_count(*src) > 0) jobs.push_back({src, dst, false});
-    if (ghost_value_count(*src) > 0) jobs.push_back({src, dst, true});
-  };
-  std::vector<int> bits(h->L.size(), 0);
-  for (size_t l = 0; l < h->L.size(); ++l) {
-    DDLevel& D = h->L[l];
-    if (D.coarsest) break;
-    add(&D.A, l == 0 ? &D.Ac : &D.A);
-    add(&D.K, &D.K);
-    add(&D.P, &D.P);
-    add(&D.R, &D.R);
-    // a merged [P_loc | AP_loc] (PA, MAMG_POST_K=0) stays fp64: bsr2_post_kernel has no fp32 side
-    bits[l] = 1 | (D.PA.nr > 0 ? 0 : 2) | 4;
-  }
-  // wait for the rank's last work; the kernels below run on the null stream
-  if (h->last) HIPCHK(hipEventSynchronize(h->last));
-  if (h->side) HIPCHK(hipStreamSynchronize(h->side));
-  if (h->cap) HIPCHK(hipStreamSynchronize(h->cap));
-  // the cached graphs and PCG plans hold the fp64 op list: dropped, the next use captures anew
-  auto drop_cached = [&]() {
-    h->drop_graphs();
-    for (auto& q : h->pcgs) q.release();
-    h->pcgs.clear();
-  };
-  // the fp64 originals go back except level 0's A_loc (the Krylov operator)
-  auto release = [&](void* old) {
-    auto it = std::find(h->allocs.begin(), h->allocs.end(), old);
-    if (!old || it == h->allocs.end()) return;
-    (void)raw_free(old);
-    h->allocs.erase(it);
-  };
-  int rc = narrow_values(jobs, &h->allocs, drop_cached, release, err);
-  if (rc) return rc;
-  for (size_t l = 0; l < h->L.size(); ++l) h->L[l].storage = bits[l];
-  std::vector<DOp> ops;
-  dapply_ops(h, nullptr, nullptr, &ops);
-  h->apply_bytes = 0.0;
-  for (const DOp& d : ops) h->apply_bytes += d.bytes;
-  return MAMG_OK;
-}
-
-int dist_mark(DistHandle* h, hipStream_t s, std::string* err) {
-  if (!h->last) HIPCHK(hipEventCreateWithFlags(&h->last, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(h->last, s));
-  return MAMG_OK;
-}
-
-// What one distributed apply issues on a rank with P > 1 peers over RCCL
-// (the same walk as run_dop, nothing launched): c[0] kernels, c[1] RCCL
-// send / receive groups, c[2] point-to-point messages, c[3] all-reduces,
-// c[4] stream forks (interior rows on the side stream).  With P == 1 only
-// the kernels remain.
-static void count_launches(const DistHandle* h, const std::vector<DOp>& ops, int64_t c[5]) {
-  for (int k = 0; k < 5; ++k) c[k] = 0;
-  const int P = h->nranks;
-  for (const DOp& d : ops) {
-    if (d.dk == D_OP || (P == 1 && d.dk == D_OVERLAP)) { ++c[0]; continue; }
-    if (P == 1) continue;
-    if (d.dk == D_ALLREDUCE) { ++c[3]; continue; }
-    const DDLevel& D = h->L[d.level];
-    const int64_t ns = D.send_off.back();
-    if (d.dk == D_OVERLAP) { ++c[0]; ++c[4]; }
-    if (d.dk == D_OVERLAP || d.dk == D_HALO) {
-      if (ns) ++c[0];
-      ++c[1];
-      for (int q = 0; q < P; ++q) {
-        if (q == h->rank) continue;
-        c[2] += (D.send_off[q + 1] > D.send_off[q]) + (D.ghost_off[q + 1] > D.ghost_off[q]);
-      }
-    } else if (d.dk == D_CHALO) {
-      const size_t b0 = (size_t)d.colour * (P + 1);
-      c[0] += (D.cs_off[b0 + P] > D.cs_off[b0]) + (D.cg_off[b0 + P] > D.cg_off[b0]);
-      ++c[1];
-      for (int q = 0; q < P; ++q) {
-        if (q == h->rank) continue;
-        c[2] += (D.cs_off[b0 + q + 1] > D.cs_off[b0 + q]) + (D.cg_off[b0 + q + 1] > D.cg_off[b0 + q]);
-      }
-    } else {   // D_REVERSE
-      ++c[1];
-      for (int q = 0; q < P; ++q) {
-        if (q == h->rank) continue;
-        const bool sc = D.send_off[q + 1] > D.send_off[q], gc = D.ghost_off[q + 1] > D.ghost_off[q];
-        c[2] += sc + gc;
-        c[0] += sc;
-      }
-    }
-  }
-}
-
-void dist_apply_launches(const DistHandle* h, int64_t c[5]) {
-  std::vector<DOp> ops;
-  dapply_ops(h, nullptr, nullptr, &ops);
-  count_launches(h, ops, c);
-}
-
-int dist_apply(DistHandle* h, const double* d_r, double* d_z, void* stream, std::string* err) {
-  HIPCHK(hipSetDevice(h->device));
-  std::vector<DOp> ops;
-  dapply_ops(h, d_r, d_z, &ops);
-  for (const DOp& d : ops) {
-    int rc = run_dop(h, d, (hipStream_t)stream, err);
-    if (rc) return rc;
-  }
-  HIPCHK(hipGetLastError());
-  return dist_mark(h, (hipStream_t)stream, err);
-}
-
-int dist_spmv(DistHandle* h, const double* d_x, double* d_y, void* stream, std::string* err) {
-  HIPCHK(hipSetDevice(h->device));
-  if (h->L.empty() || h->L[0].coarsest) { *err = "single-level hierarchy: no distributed operator"; return MAMG_ERR_ARG; }
-  std::vector<DOp> ops;
-  dspmv_ops(h, d_x, d_y, &ops);
-  for (const DOp& d : ops) {
-    int rc = run_dop(h, d, (hipStream_t)stream, err);
-    if (rc) return rc;
-  }
-  HIPCHK(hipGetLastError());
-  return dist_mark(h, (hipStream_t)stream, err);
-}
-
-// The op list of one apply captured into a hipGraph on the handle's capture
-// stream: kernels, the side-stream fork of the interior rows (events), and
-// the RCCL send / receive groups and all-reduces inside the capture.  A
-// failed capture leaves nothing behind and is reported (the caller stays
-// eager).
-int dist_capture(DistHandle* h, const std::vector<DOp>& ops, hipGraph_t* gr, hipGraphExec_t* ex, std::string* err) {
-  *gr = nullptr;
-  *ex = nullptr;
-  std::lock_guard<std::recursive_mutex> capture_lock(capture_mutex());
-  if (!h->cap) HIPCHK(hipStreamCreateWithFlags(&h->cap, hipStreamNonBlocking));
-  HIPCHK(hipStreamBeginCapture(h->cap, hipStreamCaptureModeThreadLocal));
-  int rc = MAMG_OK;
-  for (const DOp& d : ops)
-    if ((rc = run_dop(h, d, h->cap, err))) break;
-  hipGraph_t g = nullptr;
-  const hipError_t e = hipStreamEndCapture(h->cap, &g);
-  if (rc || e != hipSuccess) {
-    if (g) (void)hipGraphDestroy(g);
-    (void)hipGetLastError();
-    if (!rc) *err = std::string("stream capture of the distributed apply: ") + hipGetErrorString(e);
-    return rc ? rc : MAMG_ERR_HIP;
-  }
-  const hipError_t ei = graph_instantiate(ex, g);
-  if (ei != hipSuccess) {
-    (void)hipGraphDestroy(g);
-    (void)hipGetLastError();
-    *err = std::string("hipGraphInstantiate of the distributed apply: ") + hipGetErrorString(ei);
-    return MAMG_ERR_HIP;
-  }
-  *gr = g;
-  return MAMG_OK;
-}
-
-int dist_graph_exec(DistHandle* h, const double* d_r, double* d_z, hipGraphExec_t* ex, std::string* err) {
-  if (!h->comm && h->nranks > 1 && !h->dry) {
-    *err = "graph replay needs an RCCL communicator (or one rank): host-staged and virtual exchanges run eagerly";
-    return MAMG_ERR_UNSUPPORTED;
-  }
-  if (!h->graph_err.empty()) { *err = "graph capture failed on this handle: " + h->graph_err; return MAMG_ERR_UNSUPPORTED; }
-  for (auto& g : h->graphs)
-    if (g.r == d_r && g.z == d_z) { *ex = g.e; return MAMG_OK; }
-  if (h->graphs.size() >= 16) {   // evict the oldest once every launch on the handle finished
-    if (h->last) HIPCHK(hipEventSynchronize(h->last));
-    (void)hipGraphExecDestroy(h->graphs.front().e);
-    (void)hipGraphDestroy(h->graphs.front().g);
-    h->graphs.erase(h->graphs.begin());
-  }
-  std::vector<DOp> ops;
-  dapply_ops(h, d_r, d_z, &ops);
-  DistHandle::Graph g{d_r, d_z, nullptr, nullptr};
-  const int rc = dist_capture(h, ops, &g.g, &g.e, err);
-  if (rc) {
-    h->graph_err = *err;
-    return rc;
-  }
-  h->graphs.push_back(g);
-  *ex = g.e;
-  return MAMG_OK;
-}
-
-int dist_graph_prepare(DistHandle* h, const double* d_r, double* d_z, std::string* err) {
-  HIPCHK(hipSetDevice(h->device));
-  hipGraphExec_t ex = nullptr;
-  return dist_graph_exec(h, d_r, d_z, &ex, err);
-}
-
-int dist_apply_graph(DistHandle* h, const double* d_r, double* d_z, void* stream, std::string* err) {
-  HIPCHK(hipSetDevice(h->device));
-  hipGraphExec_t ex = nullptr;
-  const int rc = dist_graph_exec(h, d_r, d_z, &ex, err);
-  if (rc) return rc;
-  HIPCHK(hipGraphLaunch(ex, (hipStream_t)stream));
-  return dist_mark(h, (hipStream_t)stream, err);
-}
-
-int dist_time_apply(DistHandle* h, const double* d_r, double* d_z, int reps, int mode, double* ms,
-                    double* kernel_ms, double* class_bytes, void* stream, std::string* err) {
-  HIPCHK(hipSetDevice(h->device));
-  hipStream_t s = (hipStream_t)stream;
-  std::vector<DOp> ops;
-  dapply_ops(h, d_r, d_z, &ops);
-  if (class_bytes) {
-    for (int c = 0; c < 16; ++c) class_bytes[c] = 0.0;
-    for (const DOp& d : ops) class_bytes[d.cls] += d.bytes;
-  }
-  if (reps <= 0) { *ms = 0.0; return MAMG_OK; }
-  if (mode == 2) {   // graph replays, events around the whole run only
-    hipGraphExec_t ex = nullptr;
-    int rc = dist_graph_exec(h, d_r, d_z, &ex, err);
-    if (rc) return rc;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, s));
-    for (int rp = 0; rp < reps; ++rp) HIPCHK(hipGraphLaunch(ex, s));
-    HIPCHK(hipEventRecord(e1, s));
-    HIPCHK(hipEventSynchronize(e1));
-    float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, e0, e1));
-    *ms = t / reps;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (kernel_ms)
-      for (int c = 0; c < 16; ++c) kernel_ms[c] = 0.0;
-    return dist_mark(h, s, err);
-  }
-  std::vector<int> inst;
-  for (size_t k = 0; k < ops.size(); ++k)
-    if (mode == 1 || ops[k].cls == C_L0_RESID || ops[k].cls == C_L0_SMOOTH) inst.push_back((int)k);
-  std::vector<hipEvent_t> ev(2 * inst.size() * (size_t)reps + 2);
-  for (auto& e : ev) HIPCHK(hipEventCreate(&e));
-  HIPCHK(hipEventRecord(ev[0], s));
-  size_t q = 2;
-  int rc;
-  for (int rp = 0; rp < reps; ++rp) {
-    size_t ii = 0;
-    for (size_t k = 0; k < ops.size(); ++k) {
-      const bool timed = ii < inst.size() && inst[ii] == (int)k;
-      if (timed) HIPCHK(hipEventRecord(ev[q], s));
-      if ((rc = run_dop(h, ops[k], s, err))) return rc;
-      if (timed) { HIPCHK(hipEventRecord(ev[q + 1], s)); q += 2; ++ii; }
-    }
-  }
-  HIPCHK(hipEventRecord(ev[1], s));
-  HIPCHK(hipEventSynchronize(ev[1]));
-  HIPCHK(hipGetLastError());
-  float tot = 0.f;
-  HIPCHK(hipEventElapsedTime(&tot, ev[0], ev[1]));
-  *ms = tot / reps;
-  if (kernel_ms) {
-    for (int c = 0; c < 16; ++c) kernel_ms[c] = 0.0;
-    q = 2;
-    for (int rp = 0; rp < reps; ++rp)
-      for (size_t ii = 0; ii < inst.size(); ++ii) {
-        float t = 0.f;
-        HIPCHK(hipEventElapsedTime(&t, ev[q], ev[q + 1]));
-        kernel_ms[ops[inst[ii]].cls] += t / reps;
-        q += 2;
-      }
-  }
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  return MAMG_OK;
-}
-
-}  // namespace mamg
-
-// ---------------------------------------------------------------------------
-// Virtual communicator (tests on a single GPU): P rank handles on one device,
-// executed in lockstep on one stream; exchanges are device copies between the
-// ranks' buffers with exactly the counts/offsets the RCCL path uses.
-// ---------------------------------------------------------------------------
-namespace mamg {
 
 __global__ __launch_bounds__(256) void vsum_kernel(int64_t n, const double* __restrict__ a,
                                                    double* acc) {
@@ -10017,538 +7236,8 @@ __global__ __launch_bounds__(256) void vsum_kernel(int64_t n, const double* __re
   if (i < n) acc[i] = acc[i] + a[i];
 }
 
-// P ranks' op lists in lockstep on one stream
-int virtual_run(const std::vector<DistHandle*>& hs, const std::vector<std::vector<DOp>>& ops, hipStream_t s,
-                std::string* err, bool mark = true) {
-  const int P = (int)hs.size(), w = hs[0]->w;
-  for (int p = 1; p < P; ++p)
-    if (hs[p]->w != w) { *err = "rank handles of different layouts"; return MAMG_ERR_ARG; }
-  for (int p = 1; p < P; ++p)
-    if (ops[p].size() != ops[0].size()) { *err = "rank schedules differ"; return MAMG_ERR_SETUP; }
-  for (size_t k = 0; k < ops[0].size(); ++k) {
-    const int dk = ops[0][k].dk;
-    if (dk == D_OP) {
-      for (int p = 0; p < P; ++p) launch(ops[p][k].op, s);
-    } else if (dk == D_HALO || dk == D_OVERLAP) {
-      if (dk == D_OVERLAP)
-        for (int p = 0; p < P; ++p) launch(ops[p][k].op, s);
-      for (int p = 0; p < P; ++p) {
-        const DDLevel& D = hs[p]->L[ops[p][k].level];
-        const int64_t ns = D.send_off.back();
-        if (ns) pack_w(w, ns, D.send_idx, ops[p][k].buf, D.sendbuf, s);
-      }
-      for (int p = 0; p < P; ++p) {          // p receives from q
-        const DDLevel& D = hs[p]->L[ops[p][k].level];
-        for (int q = 0; q < P; ++q) {
-          if (q == p) continue;
-          const int64_t gc = D.ghost_off[q + 1] - D.ghost_off[q];
-          if (!gc) continue;
-          const DDLevel& Q = hs[q]->L[ops[q][k].level];
-          const int64_t sc = Q.send_off[p + 1] - Q.send_off[p];
-          if (sc != gc) { *err = "halo count mismatch"; return MAMG_ERR_SETUP; }
-          HIPCHK(dev_copy(ops[p][k].buf + w * (D.nloc + D.ghost_off[q]), Q.sendbuf + w * Q.send_off[p], w * gc * sizeof(double), s));
-        }
-      }
-    } else if (dk == D_CHALO) {
-      const int c = ops[0][k].colour;
-      const size_t b0 = (size_t)c * (P + 1);
-      for (int p = 0; p < P; ++p) {
-        const DDLevel& D = hs[p]->L[ops[p][k].level];
-        const int64_t s0 = D.cs_off[b0], s1 = D.cs_off[b0 + P];
-        if (s1 > s0)
-          pack_w(w, s1 - s0, D.csend_idx + s0, ops[p][k].buf, D.sendbuf + w * s0, s);
-      }
-      for (int p = 0; p < P; ++p) {          // p receives colour c's ghosts from q
-        const DDLevel& D = hs[p]->L[ops[p][k].level];
-        for (int q = 0; q < P; ++q) {
-          if (q == p) continue;
-          const int64_t gc = D.cg_off[b0 + q + 1] - D.cg_off[b0 + q];
-          const DDLevel& Q = hs[q]->L[ops[q][k].level];
-          const int64_t sc = Q.cs_off[b0 + p + 1] - Q.cs_off[b0 + p];
-          if (sc != gc) { *err = "colour halo count mismatch"; return MAMG_ERR_SETUP; }
-          if (!gc) continue;
-          HIPCHK(dev_copy(D.recvbuf + w * D.cg_off[b0 + q], Q.sendbuf + w * Q.cs_off[b0 + p], w * gc * sizeof(double), s));
-        }
-      }
-      for (int p = 0; p < P; ++p) {
-        const DDLevel& D = hs[p]->L[ops[p][k].level];
-        const int64_t g0 = D.cg_off[b0], g1 = D.cg_off[b0 + P];
-        if (g1 > g0)
-          unpack_w(w, g1 - g0, D.cghost_idx + g0, D.nloc, D.recvbuf + w * g0, ops[p][k].buf, s);
-      }
-    } else if (dk == D_REVERSE) {
-      for (int q = 0; q < P; ++q) {          // owner q receives partials from p
-        const DDLevel& Q = hs[q]->L[ops[q][k].level];
-        for (int p = 0; p < P; ++p) {
-          if (p == q) continue;
-          const int64_t sc = Q.send_off[p + 1] - Q.send_off[p];
-          if (!sc) continue;
-          const DDLevel& D = hs[p]->L[ops[p][k].level];
-          const int64_t gc = D.ghost_off[q + 1] - D.ghost_off[q];
-          if (sc != gc) { *err = "reverse count mismatch"; return MAMG_ERR_SETUP; }
-          HIPCHK(dev_copy(Q.recvbuf + w * Q.send_off[p], ops[p][k].buf + w * (D.nloc + D.ghost_off[q]), w * sc * sizeof(double), s));
-        }
-      }
-      for (int q = 0; q < P; ++q) {
-        const DDLevel& Q = hs[q]->L[ops[q][k].level];
-        for (int p = 0; p < P; ++p) {
-          const int64_t sc = Q.send_off[p + 1] - Q.send_off[p];
-          if (p == q || !sc) continue;
-          addidx_w(w, sc, Q.send_idx + Q.send_off[p], Q.recvbuf + w * Q.send_off[p], ops[q][k].buf, s);
-        }
-      }
-    } else {                                 // D_ALLREDUCE: sum in rank order
-      const int64_t n = ops[0][k].count;
-      for (int p = 1; p < P; ++p)
-        vsum_kernel<<<nblocks(n), 256, 0, s>>>(n, ops[p][k].buf, ops[0][k].buf);
-      for (int p = 1; p < P; ++p)
-        HIPCHK(dev_copy(ops[p][k].buf, ops[0][k].buf, n * sizeof(double), s));
-    }
-  }
-  HIPCHK(hipGetLastError());
-  if (mark)
-    for (DistHandle* h : hs) {
-      const int rc = dist_mark(h, s, err);
-      if (rc) return rc;
-    }
-  return MAMG_OK;
-}
-
-int dist_set_exchange(DistHandle* h, const mamg_exchange& ex, std::string* err) {
-  if (h->comm) { *err = "handle has an RCCL communicator; the host exchange is for comm_id == NULL"; return MAMG_ERR_ARG; }
-  HIPCHK(hipSetDevice(h->device));
-  auto pin = [&](double** p, int64_t n) -> int {
-    *p = nullptr;
-    if (n <= 0) return MAMG_OK;
-    void* q = nullptr;
-    HIPCHK(hipHostMalloc(&q, n * sizeof(double), hipHostMallocDefault));
-    h->pinned.push_back(q);
-    *p = (double*)q;
-    return MAMG_OK;
-  };
-  if (!h->host_ex) {
-    int64_t red = 0;
-    const int w = h->w;
-    const int nl = (int)h->L.size();
-    h->hsend.assign(nl, nullptr);
-    h->hghost.assign(nl, nullptr);
-    h->hrecv.assign(nl, nullptr);
-    for (int l = 0; l < nl; ++l) {
-      const DDLevel& D = h->L[l];
-      const int64_t ns = D.send_off.empty() ? 0 : D.send_off.back();
-      const int64_t tcs = D.cs_off.empty() ? 0 : D.cs_off.back(), tcg = D.cg_off.empty() ? 0 : D.cg_off.back();
-      int rc;
-      if ((rc = pin(&h->hsend[l], w * std::max(ns, tcs))) || (rc = pin(&h->hghost[l], w * std::max(D.ng, tcg))) ||
-          (rc = pin(&h->hrecv[l], w * ns)))
-        return rc;
-      red = std::max(red, w * D.nv);
-    }
-    red = std::max<int64_t>(red, 2 * SCALE_BLOCKS);   // coarse scaling partials
-    red = std::max<int64_t>(red, 3 * (int64_t)h->nranks);   // the PCG dots' P-vectors (dist_pcg)
-    int rc = pin(&h->hred, red);
-    if (rc) return rc;
-  }
-  h->ex = ex;
-  h->host_ex = true;
-  return MAMG_OK;
-}
-
-int dist_virtual_apply(const std::vector<DistHandle*>& hs, const std::vector<const double*>& r,
-                       const std::vector<double*>& z, void* stream, std::string* err) {
-  const int P = (int)hs.size();
-  HIPCHK(hipSetDevice(hs[0]->device));
-  std::vector<std::vector<DOp>> ops(P);
-  for (int p = 0; p < P; ++p) dapply_ops(hs[p], r[p], z[p], &ops[p]);
-  return virtual_run(hs, ops, (hipStream_t)stream, err);
-}
-
-// the virtual ranks' lockstep apply captured into one hipGraph (rank 0's
-// capture stream), launched once and destroyed: the graph path's kernels,
-// forks and exchange order, checked bitwise against the eager lockstep run
-int dist_virtual_apply_graph(const std::vector<DistHandle*>& hs, const std::vector<const double*>& r,
-                             const std::vector<double*>& z, void* stream, std::string* err) {
-  const int P = (int)hs.size();
-  HIPCHK(hipSetDevice(hs[0]->device));
-  std::vector<std::vector<DOp>> ops(P);
-  for (int p = 0; p < P; ++p) dapply_ops(hs[p], r[p], z[p], &ops[p]);
-  DistHandle* h0 = hs[0];
-  std::lock_guard<std::recursive_mutex> capture_lock(capture_mutex());
-  if (!h0->cap) HIPCHK(hipStreamCreateWithFlags(&h0->cap, hipStreamNonBlocking));
-  HIPCHK(hipStreamBeginCapture(h0->cap, hipStreamCaptureModeThreadLocal));
-  int rc = virtual_run(hs, ops, h0->cap, err, false);
-  hipGraph_t g = nullptr;
-  const hipError_t e = hipStreamEndCapture(h0->cap, &g);
-  if (rc || e != hipSuccess) {
-    if (g) (void)hipGraphDestroy(g);
-    (void)hipGetLastError();
-    if (!rc) *err = std::string("stream capture of the virtual apply: ") + hipGetErrorString(e);
-    return rc ? rc : MAMG_ERR_HIP;
-  }
-  hipGraphExec_t ex = nullptr;
-  const hipError_t ei = graph_instantiate(&ex, g);
-  if (ei != hipSuccess) {
-    (void)hipGraphDestroy(g);
-    *err = std::string("hipGraphInstantiate of the virtual apply: ") + hipGetErrorString(ei);
-    return MAMG_ERR_HIP;
-  }
-  const hipError_t el = hipGraphLaunch(ex, (hipStream_t)stream);
-  const hipError_t es = hipStreamSynchronize((hipStream_t)stream);
-  (void)hipGraphExecDestroy(ex);
-  (void)hipGraphDestroy(g);
-  if (el != hipSuccess || es != hipSuccess) {
-    *err = std::string("virtual apply graph launch: ") + hipGetErrorString(el != hipSuccess ? el : es);
-    return MAMG_ERR_HIP;
-  }
-  for (DistHandle* h : hs)
-    if ((rc = dist_mark(h, (hipStream_t)stream, err))) return rc;
-  return MAMG_OK;
-}
-
-int dist_virtual_spmv(const std::vector<DistHandle*>& hs, const std::vector<const double*>& x,
-                      const std::vector<double*>& y, void* stream, std::string* err) {
-  const int P = (int)hs.size();
-  HIPCHK(hipSetDevice(hs[0]->device));
-  std::vector<std::vector<DOp>> ops(P);
-  for (int p = 0; p < P; ++p) {
-    if (hs[p]->L.empty() || hs[p]->L[0].coarsest) { *err = "single-level hierarchy"; return MAMG_ERR_ARG; }
-    dspmv_ops(hs[p], x[p], y[p], &ops[p]);
-  }
-  return virtual_run(hs, ops, (hipStream_t)stream, err);
-}
-
-// ---------------------------------------------------------------------------
-// Device-resident PCG on row-partitioned ranks: dev_pcg's loop
-// with the operator, the preconditioner and the dots as one DOp list per
-// iteration, so the RCCL, captured-graph, host-staged and virtual backends
-// all execute the same schedule.
-// ---------------------------------------------------------------------------
-namespace {
-
-void append(std::vector<DOp>* ops, const std::vector<DOp>& more) { ops->insert(ops->end(), more.begin(), more.end()); }
-
-DOp pcg_op(int kind, const DPcgCtx* c, double bytes, int64_t n = 0) {
-  Op o;
-  o.kind = kind; o.cls = C_MISC; o.pcg = c; o.n = n; o.bytes = bytes;
-  return wrap(o);
-}
-
-// the rank's partials of <a, b> (dot 0), its slot in each of the nd
-// P-vectors (dots 1, 2: partials already written by the pass before), and
-// the all-reduce of the nd P-vectors
-void dpcg_dot_ops(const DPcgCtx* c, const double* a, const double* b, int nd, std::vector<DOp>* ops) {
-  DOp d = pcg_op(OP_PDOT, c, 16.0 * c->n);
-  d.op.x = a; d.op.y = b;
-  ops->push_back(d);
-  ops->push_back(pcg_op(OP_PSLOT, c, 8.0 * nd * DOT_BLOCKS, nd));
-  DOp r;
-  r.dk = D_ALLREDUCE; r.cls = C_COMM; r.buf = c->pv; r.count = (int64_t)nd * c->P; r.bytes = 16.0 * r.count;
-  ops->push_back(r);
-}
-
-// one iteration: q = A d, <d,q>, alpha, x / r update (+ ||r||^2 partials),
-// z = B r, <r,z> (and ||r||^2), beta + histories + stop test, d update.  An
-// inactive iteration issues every op and every exchange; the state's flags
-// mask the x, r and d updates only.
-void dpcg_iter_ops(const DistHandle* h, const DPcgCtx* c, std::vector<DOp>* ops) {
-  ops->clear();
-  std::vector<DOp> part;
-  dspmv_ops(h, c->d, c->q, &part);
-  append(ops, part);
-  dpcg_dot_ops(c, c->d, c->q, 1, ops);
-  ops->push_back(pcg_op(OP_PALPHA, c, 0.0));
-  ops->push_back(pcg_op(OP_PXR, c, 48.0 * c->n));
-  dapply_ops(h, c->r, c->z, &part);
-  append(ops, part);
-  dpcg_dot_ops(c, c->r, c->z, c->stop ? 2 : 1, ops);
-  ops->push_back(pcg_op(OP_PBETA, c, 0.0));
-  ops->push_back(pcg_op(OP_PD, c, 24.0 * c->n));
-}
-
-// start-up: r = b - A x0, z = B r, d = z, <r,z> (and ||r||^2, ||b||^2), first state
-void dpcg_start_ops(const DistHandle* h, const DPcgCtx* c, std::vector<DOp>* ops) {
-  ops->clear();
-  std::vector<DOp> part;
-  dspmv_ops(h, c->x, c->q, &part);
-  append(ops, part);
-  ops->push_back(pcg_op(OP_PR0, c, 24.0 * c->n));
-  dapply_ops(h, c->r, c->z, &part);
-  append(ops, part);
-  Op cp;
-  cp.kind = OP_COPY; cp.cls = C_MISC; cp.n = c->n; cp.x = c->z; cp.out = c->d; cp.bytes = 16.0 * c->n;
-  ops->push_back(wrap(cp));
-  dpcg_dot_ops(c, c->r, c->z, c->stop ? 3 : 1, ops);
-  ops->push_back(pcg_op(OP_PINIT, c, 0.0));
-}
-
-int dpcg_check(const DistHandle* h, int maxiter, int stop, const double* rnorms, std::string* err) {
-  if (stop != 0 && stop != 1) { *err = "stop_type must be 0 (cbc.block) or 1 (||r|| <= tol ||b||)"; return MAMG_ERR_ARG; }
-  if (maxiter < 0) { *err = "maxiter must be >= 0"; return MAMG_ERR_ARG; }
-  if (stop == 1 && !rnorms) { *err = "stop_type 1 needs the rnorms history"; return MAMG_ERR_ARG; }
-  if (h->L.empty() || h->L[0].coarsest) { *err = "single-level hierarchy: no distributed operator"; return MAMG_ERR_ARG; }
-  return MAMG_OK;
-}
-
-// the handle's plan for (x, maxiter, stop): work buffers on first use,
-// histories and the ops' context per plan (at most 4, the oldest evicted
-// once the handle's work is done); slots: host mirrors of the state wanted
-int dpcg_plan(DistHandle* h, double* x, int maxiter, int stop, int slots, DistHandle::PcgPlan** out,
-              std::string* err) {
-  int rc;
-  const int64_t n = (int64_t)h->w * h->L[0].nloc;
-  if (!h->pst) {
-    double** v[] = {&h->cr, &h->cz, &h->cd, &h->cq};
-    for (double** q : v)
-      if ((rc = ddalloc(h, q, std::max<int64_t>(n, 1), err))) return rc;
-    if ((rc = ddalloc(h, &h->ppart, 3 * DOT_BLOCKS, err))) return rc;
-    if ((rc = ddalloc(h, &h->pv, 3 * (int64_t)h->nranks, err))) return rc;
-    if ((rc = ddalloc(h, &h->pst, 1, err))) return rc;
-  }
-  if (h->hst_ranks < slots) {
-    if (h->last) HIPCHK(hipEventSynchronize(h->last));
-    if (h->hst) HIPCHK(hipHostFree(h->hst));
-    h->hst = nullptr;
-    h->hst_ranks = 0;
-    HIPCHK(hipHostMalloc((void**)&h->hst, 2 * (size_t)slots * sizeof(DPcgState), hipHostMallocDefault));
-    h->hst_ranks = slots;
-  }
-  for (auto& q : h->pcgs)
-    if (q.c->x == x && q.c->maxiter == maxiter && q.c->stop == stop) { *out = &q; return MAMG_OK; }
-  if (h->pcgs.size() >= 4) {
-    if (h->last) HIPCHK(hipEventSynchronize(h->last));
-    h->pcgs.front().release();
-    h->pcgs.erase(h->pcgs.begin());
-  }
-  DistHandle::PcgPlan q;
-  if (raw_malloc((void**)&q.hist, (4 * (size_t)maxiter + 2) * sizeof(double), "long") != hipSuccess) {
-    (void)hipGetLastError();
-    *err = "PCG history allocation failed";
-    return MAMG_ERR_HIP;
-  }
-  hipError_t e = hipSuccess;
-  for (hipEvent_t& v : q.ev)
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&v, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    q.release();
-    *err = std::string("PCG events: ") + hipGetErrorString(e);
-    return MAMG_ERR_HIP;
-  }
-  q.c.reset(new DPcgCtx());
-  DPcgCtx& c = *q.c;
-  c.st = h->pst; c.n = n; c.P = h->nranks; c.rank = h->rank; c.stop = stop; c.maxiter = maxiter;
-  c.x = x; c.r = h->cr; c.z = h->cz; c.d = h->cd; c.q = h->cq; c.part = h->ppart; c.pv = h->pv;
-  c.res = q.hist; c.rn = c.res + maxiter + 1; c.al = c.rn + maxiter + 1; c.be = c.al + maxiter;
-  h->pcgs.push_back(std::move(q));
-  *out = &h->pcgs.back();
-  return MAMG_OK;
-}
-
-// histories and the return code from the final state (dev_pcg's messages)
-int dpcg_finish(const DPcgCtx& c, const DPcgState& fin, double* residuals, double* rnorms, double* alphas,
-                double* betas, int* niters, std::string* err) {
-  const int it = fin.it;
-  HIPCHK(hipMemcpy(residuals, c.res, (it + 1) * sizeof(double), hipMemcpyDeviceToHost));
-  if (c.stop && rnorms) HIPCHK(hipMemcpy(rnorms, c.rn, (it + 1) * sizeof(double), hipMemcpyDeviceToHost));
-  if (it > 0) {
-    HIPCHK(hipMemcpy(alphas, c.al, it * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(betas, c.be, it * sizeof(double), hipMemcpyDeviceToHost));
-  }
-  *niters = it;
-  if (fin.status == PCG_DQ_ZERO) { *err = "ConjGrad stopped: <d,Ad> = 0"; return MAMG_ERR_BREAKDOWN; }
-  if (fin.status == PCG_RZ_NEG) { *err = "ConjGrad breakdown (<r,Br> < 0)"; return MAMG_ERR_BREAKDOWN; }
-  return MAMG_OK;
-}
-
-}  // namespace
-
-void dist_pcg_launches(const DistHandle* h, int stop, int64_t c[5]) {
-  DPcgCtx ctx;
-  ctx.P = h->nranks; ctx.rank = h->rank; ctx.stop = stop; ctx.n = (int64_t)h->w * h->L[0].nloc;
-  std::vector<DOp> ops;
-  dpcg_iter_ops(h, &ctx, &ops);
-  count_launches(h, ops, c);
-}
-
-int dist_pcg(DistHandle* h, const double* d_b, double* d_x, double tol, int maxiter, int relativeconv,
-             int stop, double* residuals, double* rnorms, double* alphas, double* betas, int* niters,
-             void* stream, std::string* err) {
-  int rc;
-  if ((rc = dpcg_check(h, maxiter, stop, rnorms, err))) return rc;
-  if (!h->comm && h->nranks > 1 && !h->host_ex && !h->dry) {
-    *err = "virtual rank handle (no communicator): use mamg_dist_virtual_pcg";
-    return MAMG_ERR_ARG;
-  }
-  HIPCHK(hipSetDevice(h->device));
-  hipStream_t s = (hipStream_t)stream;
-  DistHandle::PcgPlan* pl = nullptr;
-  if ((rc = dpcg_plan(h, d_x, maxiter, stop, 1, &pl, err))) return rc;
-  DPcgCtx& c = *pl->c;
-  c.b = d_b; c.tol = tol; c.relconv = relativeconv;
-  DPcgState* st = h->pst;
-  DPcgState* hst = h->hst;
-  std::vector<DOp> ops;
-  dpcg_iter_ops(h, &c, &ops);
-  // one iteration as one hipGraph (RCCL calls inside) on an RCCL or
-  // single-rank handle; a failed capture is recorded and the same op list
-  // runs eagerly -- the RCCL sequence of a rank is the same either way
-  const bool graphable = (h->comm || h->nranks == 1) && h->graph_err.empty() && h->pcg_graph_err.empty();
-  if (graphable && !pl->e) {
-    std::string cerr;
-    if (dist_capture(h, ops, &pl->g, &pl->e, &cerr)) {
-      h->pcg_graph_err = cerr;
-      pl->g = nullptr;
-      pl->e = nullptr;
-    }
-  }
-  if (h->last) HIPCHK(hipStreamWaitEvent(s, h->last, 0));   // the work buffers are the handle's
-  std::vector<DOp> start;
-  dpcg_start_ops(h, &c, &start);
-  for (const DOp& d : start)
-    if ((rc = run_dop(h, d, s, err))) return rc;
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(&hst[0], st, sizeof(DPcgState), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (hst[0].status == PCG_NOT_POS) {
-    *niters = 0;
-    residuals[0] = 0.0;
-    (void)dist_mark(h, s, err);
-    *err = "Matrix is not positive";
-    return MAMG_ERR_BREAKDOWN;
-  }
-  if (hst[0].active) {
-    // iteration k's state lands in hst[k & 1].  The host-staged exchange
-    // synchronises at every exchange, so its state is read after each
-    // iteration; otherwise iteration k + 1 is queued before the host waits
-    // for iteration k.  Either way the number of iterations a rank issues
-    // depends on all-reduced state only: the same on every rank.
-    const bool ahead = !(h->host_ex && !h->comm);
-    for (int k = 0; k < maxiter; ++k) {
-      if (pl->e) {
-        HIPCHK(hipGraphLaunch(pl->e, s));
-      } else {
-        for (const DOp& d : ops)
-          if ((rc = run_dop(h, d, s, err))) return rc;
-      }
-      HIPCHK(hipMemcpyAsync(&hst[k & 1], st, sizeof(DPcgState), hipMemcpyDeviceToHost, s));
-      HIPCHK(hipEventRecord(pl->ev[k & 1], s));
-      if (ahead && k == 0) continue;
-      const int w = ahead ? (k - 1) & 1 : k & 1;
-      HIPCHK(hipEventSynchronize(pl->ev[w]));
-      if (!hst[w].active) break;
-    }
-  }
-  HIPCHK(hipMemcpyAsync(&hst[0], st, sizeof(DPcgState), hipMemcpyDeviceToHost, s));
-  if ((rc = dist_mark(h, s, err))) return rc;
-  HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipGetLastError());
-  return dpcg_finish(c, hst[0], residuals, rnorms, alphas, betas, niters, err);
-}
-
-// test mode: the ranks' op lists in lockstep (virtual_run), eager or as one
-// captured lockstep iteration replayed; every rank's state is compared with
-// rank 0's, byte for byte, whenever it is read back
-int dist_virtual_pcg(const std::vector<DistHandle*>& hs, const std::vector<const double*>& b,
-                     const std::vector<double*>& x, double tol, int maxiter, int relativeconv, int stop,
-                     int graph, double* residuals, double* rnorms, double* alphas, double* betas, int* niters,
-                     void* stream, std::string* err) {
-  const int P = (int)hs.size();
-  int rc;
-  for (int p = 0; p < P; ++p) {
-    if ((rc = dpcg_check(hs[p], maxiter, stop, rnorms, err))) return rc;
-    if (hs[p]->nranks != P || hs[p]->rank != p) { *err = "rank handles do not form ranks 0..n-1 of n"; return MAMG_ERR_ARG; }
-  }
-  DistHandle* h0 = hs[0];
-  HIPCHK(hipSetDevice(h0->device));
-  hipStream_t s = (hipStream_t)stream;
-  std::vector<DistHandle::PcgPlan*> pl(P, nullptr);
-  std::vector<std::vector<DOp>> start(P), ops(P);
-  for (int p = 0; p < P; ++p) {
-    if ((rc = dpcg_plan(hs[p], x[p], maxiter, stop, p == 0 ? P : 1, &pl[p], err))) return rc;
-    DPcgCtx& c = *pl[p]->c;
-    c.b = b[p]; c.tol = tol; c.relconv = relativeconv;
-    dpcg_start_ops(hs[p], &c, &start[p]);
-    dpcg_iter_ops(hs[p], &c, &ops[p]);
-    if (hs[p]->last) HIPCHK(hipStreamWaitEvent(s, hs[p]->last, 0));
-  }
-  DPcgState* hst = h0->hst;                    // [2][P]
-  auto read_states = [&](int slot) -> int {
-    for (int p = 0; p < P; ++p)
-      HIPCHK(hipMemcpyAsync(&hst[(size_t)slot * P + p], hs[p]->pst, sizeof(DPcgState), hipMemcpyDeviceToHost, s));
-    return MAMG_OK;
-  };
-  auto same_states = [&](int slot, int k) -> int {
-    for (int p = 1; p < P; ++p)
-      if (std::memcmp(&hst[(size_t)slot * P + p], &hst[(size_t)slot * P], sizeof(DPcgState))) {
-        *err = "virtual PCG: rank " + std::to_string(p) + "'s state differs from rank 0's after iteration " +
-               std::to_string(k);
-        return MAMG_ERR_SETUP;
-      }
-    return MAMG_OK;
-  };
-  hipGraph_t g = nullptr;
-  hipGraphExec_t ex = nullptr;
-  auto drop = [&]() {
-    if (ex) (void)hipGraphExecDestroy(ex);
-    if (g) (void)hipGraphDestroy(g);
-    ex = nullptr; g = nullptr;
-  };
-  if (graph && maxiter > 0) {
-    std::lock_guard<std::recursive_mutex> capture_lock(capture_mutex());
-    if (!h0->cap) HIPCHK(hipStreamCreateWithFlags(&h0->cap, hipStreamNonBlocking));
-    HIPCHK(hipStreamBeginCapture(h0->cap, hipStreamCaptureModeThreadLocal));
-    rc = virtual_run(hs, ops, h0->cap, err, false);
-    const hipError_t e = hipStreamEndCapture(h0->cap, &g);
-    if (rc || e != hipSuccess) {
-      drop();
-      (void)hipGetLastError();
-      if (!rc) *err = std::string("stream capture of the virtual PCG iteration: ") + hipGetErrorString(e);
-      return rc ? rc : MAMG_ERR_HIP;
-    }
-    const hipError_t ei = graph_instantiate(&ex, g);
-    if (ei != hipSuccess) {
-      drop();
-      *err = std::string("hipGraphInstantiate of the virtual PCG iteration: ") + hipGetErrorString(ei);
-      return MAMG_ERR_HIP;
-    }
-  }
-  // from here on every exit drains the stream and drops the graph
-  auto body = [&]() -> int {
-    int r;
-    if ((r = virtual_run(hs, start, s, err, false))) return r;
-    if ((r = read_states(0))) return r;
-    HIPCHK(hipStreamSynchronize(s));
-    if ((r = same_states(0, 0))) return r;
-    if (hst[0].status == PCG_NOT_POS || !hst[0].active) return MAMG_OK;
-    for (int k = 0; k < maxiter; ++k) {
-      if (ex) HIPCHK(hipGraphLaunch(ex, s));
-      else if ((r = virtual_run(hs, ops, s, err, false))) return r;
-      if ((r = read_states(k & 1))) return r;
-      HIPCHK(hipEventRecord(pl[0]->ev[k & 1], s));
-      if (k == 0) continue;
-      const int w = (k - 1) & 1;
-      HIPCHK(hipEventSynchronize(pl[0]->ev[w]));
-      if ((r = same_states(w, k))) return r;
-      if (!hst[(size_t)w * P].active) break;
-    }
-    if ((r = read_states(0))) return r;
-    HIPCHK(hipStreamSynchronize(s));
-    return same_states(0, hst[0].it);
-  };
-  rc = body();
-  for (DistHandle* h : hs) {
-    std::string merr;
-    (void)dist_mark(h, s, &merr);
-  }
-  (void)hipStreamSynchronize(s);
-  drop();
-  if (rc) return rc;
-  HIPCHK(hipGetLastError());
-  if (hst[0].status == PCG_NOT_POS) {
-    *niters = 0;
-    residuals[0] = 0.0;
-    *err = "Matrix is not positive";
-    return MAMG_ERR_BREAKDOWN;
-  }
-  return dpcg_finish(*pl[0]->c, hst[0], residuals, rnorms, alphas, betas, niters, err);
+void vsum(int64_t n, const double* a, double* acc, hipStream_t s) {
+  vsum_kernel<<<nblocks(n), 256, 0, s>>>(n, a, acc);
 }
 
 }  // namespace mamg

@@ -48,7 +48,7 @@ void dist_ranges(const std::vector<int64_t>& nv, const std::vector<char>& coarse
                  int64_t rep_nodes, std::vector<std::vector<int64_t>>* own, std::vector<char>* rep);
 
 // which hierarchies the row partition takes (dist.cpp; also part of
-// device.hip dist_check): scalar ones (num_functions 1, CSR layout) with the
+// dist_layout.hip dist_check): scalar ones (num_functions 1, CSR layout) with the
 // Jacobi-family / POLY smoothers and the additive seed blocks, and nodal ones
 // (num_functions 2, node-block smoothers, BSR2 layout); the message names the
 // alternative
@@ -63,7 +63,7 @@ int dist_layout_check(const mamg_params& p, std::string* err);
 // the rows this rank reads, and node-major smoother slices in HostLevel::Wn);
 // nullptr = computed here from the full hierarchy.
 // meta_only: ranges, ghosts and send lists only (the operators are built on
-// the device from the GPU hierarchy, device.hip dev_rank_ops); H then needs
+// the device from the GPU hierarchy, dist_layout.hip dev_rank_ops); H then needs
 // only each level's n / coarsest (and the coarsest Ainv), `pre` is required.
 int build_dist_plan(const Hierarchy& H, const CsrView& A0, int rank, int nranks, int64_t rep_nodes,
                     bool fuse, DistPlan* plan, std::string* err, bool kpost = true, double kw = 1.0,

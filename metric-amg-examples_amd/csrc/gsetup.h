@@ -106,7 +106,8 @@ int dscan_incl_i64(const int64_t* in, int64_t* out, int64_t n, void* stream, std
 // one tiny scan on `stream` (its own buffers, kept): loads dprims' code
 // object, which the runtime defers to the first launch (gsetup.hip warm_modules)
 void dprims_warm(void* stream);
-// one empty kernel of device.hip on `stream` (the same, for its code object)
+// one empty kernel of device.hip and one of dist_layout.hip on `stream` (the same, for
+// their code objects)
 void device_warm(void* stream);
 int dsort_pairs_i32_i64(const int32_t* kin, int32_t* kout, const int64_t* vin, int64_t* vout,
                         int64_t n, int key_bits, void* stream, std::string* err);

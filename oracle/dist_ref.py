@@ -268,8 +268,8 @@ def local_slice(v, nv, o0, o1):
 
 
 # --------------------------------------------------------------------------
-# Node-patch Schwarz on P ranks (device.hip dist_patches
-# / dcycle_patch): rank p owns the nodes [own[p], own[p+1]) (contiguous, as
+# Node-patch Schwarz on P ranks (dist_layout.hip dist_patches
+# / dist_apply.hip dcycle_patch): rank p owns the nodes [own[p], own[p+1]) (contiguous, as
 # the level-0 z-slabs); its local copy of x covers the owned nodes and every
 # node within 3 hops; it computes the patches centred within 1 hop of its
 # nodes (each patch that writes an owned node) from its local x, writes the
@@ -357,8 +357,8 @@ class PartitionedPatchSweep:
 
 
 # --------------------------------------------------------------------------
-# Seed-ring Schwarz on P ranks (device.hip dist_rings /
-# dcycle_rings): rank p owns the nodes [own[p], own[p+1]); its local copy of x
+# Seed-ring Schwarz on P ranks (dist_layout.hip dist_rings /
+# dist_apply.hip dcycle_rings): rank p owns the nodes [own[p], own[p+1]); its local copy of x
 # covers the owned nodes and every node within 2 maxlvl + 1 hops; it computes
 # every block with a member node it owns (all members lie within 2 maxlvl
 # hops of that node, their rows read within 2 maxlvl + 1) from its local x,

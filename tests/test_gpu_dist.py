@@ -164,7 +164,7 @@ def test_virtual_ranks_multicolour_gs(lib_built, kw, P, rep):
                                          ('merged', 2, 100)])
 def test_rank_slice_download_bitwise(lib_built, monkeypatch, case, P, rep):
     """The rank-local operators built in HBM from the GPU hierarchy (default;
-    ghost lists marked on the device, device.hip dev_rank_ops), from the
+    ghost lists marked on the device, dist_layout.hip dev_rank_ops), from the
     rank's downloaded rows planned on the host, and from the whole
     downloaded hierarchy planned on the host: bitwise equal applies and byte
     counts, also with every level above the coarsest distributed (rep_nodes
