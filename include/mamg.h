@@ -362,6 +362,9 @@ int mamg_dist_apply_bytes(const mamg_dhandle* h, double* bytes);
  * list, nothing launched): counts[0] kernels, [1] RCCL send / receive groups,
  * [2] point-to-point messages, [3] all-reduces, [4] side-stream forks */
 int mamg_dist_apply_launches(const mamg_dhandle* h, int64_t counts[5]);
+/* z_local = (B r)_local, enqueued on `stream`.  Streams and ordering: see
+ * "Streams and ordering" above mamg_apply -- a rank handle orders its calls
+ * across streams exactly as a single-GPU handle does. */
 int mamg_dist_apply_device(mamg_dhandle* h, const double* d_r_local, double* d_z_local,
                            void* stream);
 /* The same apply replayed from a hipGraph: captured on the first call per
@@ -613,8 +616,34 @@ int mamg_dist_level_storage(const mamg_dhandle* h, int level);
 int mamg_dist_num_levels(const mamg_dhandle* h);
 int mamg_dist_level_format(const mamg_dhandle* h, int level);
 
+/* Streams and ordering, for both handle types (mamg_handle, mamg_dhandle).
+ * Every call that takes a `stream` enqueues all of its device work -- kernels,
+ * copies, memsets, graph launches, RCCL calls -- on that stream (hipStream_t,
+ * NULL = the legacy default stream), behind whatever the caller queued there
+ * before; the handle's own streams (graph capture, the side stream of the
+ * interior rows) are forked from and joined back into it by events, so the
+ * caller's stream order covers them.  The inputs are read and the outputs
+ * written in stream order: a buffer filled by work queued on `stream` before
+ * the call is a valid input, no host synchronisation needed.
+ * A handle's work vectors (level vectors, ghost, send and receive buffers,
+ * the PCG vectors) are shared by all of its calls, so the handle orders them:
+ * each call first makes `stream` wait for the handle's previous call, on
+ * whatever stream that ran (an event, no host wait), and records its own end.
+ * Calls on one handle from different streams therefore run one after the
+ * other, in the order the host issued them; calls on different handles are
+ * independent.  mamg_dist_virtual_* order against every handle of the list.
+ * The ordering is between device work only: the host must not issue calls on
+ * one handle from two threads at once (one handle per host thread).
+ * mamg_apply_device, mamg_spmv_device, mamg_dist_apply_device,
+ * mamg_dist_apply_graph, mamg_dist_spmv_device, mamg_dist_virtual_apply and
+ * mamg_dist_virtual_spmv return with the work queued (a host-staged exchange
+ * waits for `stream` at every exchange); the PCG calls, the timing hooks,
+ * mamg_dist_virtual_apply_graph and the host-pointer mamg_apply wait for
+ * their own work before they return. */
+
 /* z = B r : one preconditioner application (`maxit` cycles from x0 = 0).
- * Host pointers (copies in/out, synchronous). */
+ * Host pointers (copies in/out, synchronous; ordered behind the handle's
+ * queued device-pointer calls). */
 int mamg_apply(mamg_handle* h, const double* r, double* z);
 /* Device pointers, enqueued on `stream` (hipStream_t, NULL = default).
  * r is not modified; r and z must not alias. */

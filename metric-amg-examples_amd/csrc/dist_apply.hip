@@ -870,6 +870,15 @@ int dist_set_cycle_storage(DistHandle* h, int storage, std::string* err) {
   return MAMG_OK;
 }
 
+// handle ordering (DistHandle::last), as order_begin / order_end of a
+// DeviceHandle: every call that touches the rank's ghost, send, receive and
+// level work buffers first makes its stream wait for the handle's last mark,
+// whatever stream that was recorded on, and leaves its own mark behind
+int dist_wait(DistHandle* h, hipStream_t s, std::string* err) {
+  if (h->last) HIPCHK(hipStreamWaitEvent(s, h->last, 0));
+  return MAMG_OK;
+}
+
 int dist_mark(DistHandle* h, hipStream_t s, std::string* err) {
   if (!h->last) HIPCHK(hipEventCreateWithFlags(&h->last, hipEventDisableTiming));
   HIPCHK(hipEventRecord(h->last, s));
@@ -928,9 +937,10 @@ int dist_apply(DistHandle* h, const double* d_r, double* d_z, void* stream, std:
   HIPCHK(hipSetDevice(h->device));
   std::vector<DOp> ops;
   dapply_ops(h, d_r, d_z, &ops);
+  int rc = dist_wait(h, (hipStream_t)stream, err);
+  if (rc) return rc;
   for (const DOp& d : ops) {
-    int rc = run_dop(h, d, (hipStream_t)stream, err);
-    if (rc) return rc;
+    if ((rc = run_dop(h, d, (hipStream_t)stream, err))) return rc;
   }
   HIPCHK(hipGetLastError());
   return dist_mark(h, (hipStream_t)stream, err);
@@ -941,9 +951,10 @@ int dist_spmv(DistHandle* h, const double* d_x, double* d_y, void* stream, std::
   if (h->L.empty() || h->L[0].coarsest) { *err = "single-level hierarchy: no distributed operator"; return MAMG_ERR_ARG; }
   std::vector<DOp> ops;
   dspmv_ops(h, d_x, d_y, &ops);
+  int rc = dist_wait(h, (hipStream_t)stream, err);
+  if (rc) return rc;
   for (const DOp& d : ops) {
-    int rc = run_dop(h, d, (hipStream_t)stream, err);
-    if (rc) return rc;
+    if ((rc = run_dop(h, d, (hipStream_t)stream, err))) return rc;
   }
   HIPCHK(hipGetLastError());
   return dist_mark(h, (hipStream_t)stream, err);
@@ -1018,8 +1029,9 @@ int dist_graph_prepare(DistHandle* h, const double* d_r, double* d_z, std::strin
 int dist_apply_graph(DistHandle* h, const double* d_r, double* d_z, void* stream, std::string* err) {
   HIPCHK(hipSetDevice(h->device));
   hipGraphExec_t ex = nullptr;
-  const int rc = dist_graph_exec(h, d_r, d_z, &ex, err);
+  int rc = dist_graph_exec(h, d_r, d_z, &ex, err);
   if (rc) return rc;
+  if ((rc = dist_wait(h, (hipStream_t)stream, err))) return rc;
   HIPCHK(hipGraphLaunch(ex, (hipStream_t)stream));
   return dist_mark(h, (hipStream_t)stream, err);
 }
@@ -1039,6 +1051,7 @@ int dist_time_apply(DistHandle* h, const double* d_r, double* d_z, int reps, int
     hipGraphExec_t ex = nullptr;
     int rc = dist_graph_exec(h, d_r, d_z, &ex, err);
     if (rc) return rc;
+    if ((rc = dist_wait(h, s, err))) return rc;
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0));
     HIPCHK(hipEventCreate(&e1));
@@ -1060,9 +1073,10 @@ int dist_time_apply(DistHandle* h, const double* d_r, double* d_z, int reps, int
     if (mode == 1 || ops[k].cls == C_L0_RESID || ops[k].cls == C_L0_SMOOTH) inst.push_back((int)k);
   std::vector<hipEvent_t> ev(2 * inst.size() * (size_t)reps + 2);
   for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+  int rc;
+  if ((rc = dist_wait(h, s, err))) return rc;
   HIPCHK(hipEventRecord(ev[0], s));
   size_t q = 2;
-  int rc;
   for (int rp = 0; rp < reps; ++rp) {
     size_t ii = 0;
     for (size_t k = 0; k < ops.size(); ++k) {
@@ -1241,6 +1255,9 @@ int dist_virtual_apply(const std::vector<DistHandle*>& hs, const std::vector<con
   HIPCHK(hipSetDevice(hs[0]->device));
   std::vector<std::vector<DOp>> ops(P);
   for (int p = 0; p < P; ++p) dapply_ops(hs[p], r[p], z[p], &ops[p]);
+  int rc;
+  for (DistHandle* h : hs)
+    if ((rc = dist_wait(h, (hipStream_t)stream, err))) return rc;
   return virtual_run(hs, ops, (hipStream_t)stream, err);
 }
 
@@ -1273,6 +1290,8 @@ int dist_virtual_apply_graph(const std::vector<DistHandle*>& hs, const std::vect
     *err = std::string("hipGraphInstantiate of the virtual apply: ") + hipGetErrorString(ei);
     return MAMG_ERR_HIP;
   }
+  for (DistHandle* h : hs)
+    if (h->last) (void)hipStreamWaitEvent((hipStream_t)stream, h->last, 0);
   const hipError_t el = hipGraphLaunch(ex, (hipStream_t)stream);
   const hipError_t es = hipStreamSynchronize((hipStream_t)stream);
   (void)hipGraphExecDestroy(ex);
@@ -1295,6 +1314,9 @@ int dist_virtual_spmv(const std::vector<DistHandle*>& hs, const std::vector<cons
     if (hs[p]->L.empty() || hs[p]->L[0].coarsest) { *err = "single-level hierarchy"; return MAMG_ERR_ARG; }
     dspmv_ops(hs[p], x[p], y[p], &ops[p]);
   }
+  int rc;
+  for (DistHandle* h : hs)
+    if ((rc = dist_wait(h, (hipStream_t)stream, err))) return rc;
   return virtual_run(hs, ops, (hipStream_t)stream, err);
 }
 
