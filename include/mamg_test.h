@@ -70,6 +70,25 @@ int mamg_sharded_galerkin_check(const mamg_csr* A, const mamg_csr* P, const mamg
  *  17.. per dense solve: n, 1 if its matrix is in the LDS region (else global) */
 int mamg_tail_info(const mamg_handle* h, int index, int64_t* info, int cap);
 
+/* Thresholds of the row-pattern dictionary of a level-0 A (DESIGN.md section
+ * 3), for the process: the node rows from which it is tried, the cap on row
+ * types, and the bits kept of a row's hash (a few bits force collisions; the
+ * layout must then be refused or exact).  A negative value restores that
+ * default.  Read by every setup at its entry, with the switches. */
+int mamg_test_set_rowdict(int64_t min_rows, int max_types, int hash_bits);
+
+/* What the dictionary's builder decided for the handle's level-0 A.  Writes
+ * up to cap values, returns how many there are (5), MAMG_ERR_ARG for a bad
+ * argument.  info[]:
+ *   0 taken (1 / 0)
+ *   1 refusal reason: 0 none, 1 more row types than the cap, 2 a row longer
+ *     than 32 blocks, 3 the verification pass found a difference, 4 fewer
+ *     rows than the threshold, 5 not square, 6 the table exceeds 64 KB,
+ *     7 not tried (the handle holds the CSR layout)
+ *   2 row types found (past the cap: as many as were counted before the stop)
+ *   3 longest row in blocks      4 bytes of the type table */
+int mamg_rowdict_info(const mamg_handle* h, int64_t* info, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,8 @@ SIGNATURES = {
     'mamg_dist_num_levels': (C.c_int, [VP]),
     'mamg_dist_level_format': (C.c_int, [VP, C.c_int]),
     'mamg_tail_info': (C.c_int, [VP, C.c_int, P_I64, C.c_int]),
+    'mamg_test_set_rowdict': (C.c_int, [C.c_int64, C.c_int, C.c_int]),
+    'mamg_rowdict_info': (C.c_int, [VP, P_I64, C.c_int]),
     'mamg_apply': (C.c_int, [VP, P_F64, P_F64]),
     'mamg_apply_device': (C.c_int, [VP, VP, VP, VP]),
     'mamg_spmv_device': (C.c_int, [VP, VP, VP, VP]),
@@ -197,6 +199,12 @@ def set_option(name, value):
     one of the library's internal layout switches for the process."""
     v = None if value is None else str(value).encode()
     check(lib().mamg_set_option(name.encode(), v))
+
+
+def set_rowdict(min_rows=-1, max_types=-1, hash_bits=-1):
+    """mamg_test_set_rowdict (include/mamg_test.h): thresholds of the
+    row-pattern dictionary for the setups that follow (negative: default)."""
+    check(lib().mamg_test_set_rowdict(int(min_rows), int(max_types), int(hash_bits)))
 
 
 def option_names():

@@ -270,7 +270,8 @@ class MetricAMG:
         return {'sell': bool(f & 1), 'sym': bool(f & 2), 'post_fused': bool(f & 4),
                 'post_k': bool(f & 8), 'post_sell': bool(f & 16), 'half': bool(f & 32),
                 'bands': bool(f & 64), 'patches': bool(f & 128), 'gs': bool(f & 256),
-                'rings': bool(f & 512), 'r_bands': bool(f & 1024), 'k_col16': bool(f & 2048)}
+                'rings': bool(f & 512), 'r_bands': bool(f & 1024), 'k_col16': bool(f & 2048),
+                'rowdict': bool(f & 4096)}
 
     def set_cycle_storage(self, storage):
         """'f32': narrow the operators the cycle streams to fp32 storage
@@ -286,6 +287,17 @@ class MetricAMG:
         f = self._L.mamg_level_storage(self._h, int(level))
         _lib.check(min(f, 0))
         return {'A': bool(f & 1), 'KP': bool(f & 2), 'R': bool(f & 4)}
+
+    def rowdict_info(self) -> dict:
+        """What the row-pattern dictionary's builder decided for level 0's A
+        (mamg_rowdict_info, a test hook): ``taken``, the refusal ``reason``
+        (None when taken), ``types`` found, the longest row ``maxlen`` and
+        the ``table_bytes``."""
+        v = (C.c_int64 * 8)()
+        _lib.check(min(self._L.mamg_rowdict_info(self._h, v, 8), 0))
+        reasons = (None, 'types', 'length', 'verification', 'threshold', 'not square', 'table', 'not tried')
+        return {'taken': bool(v[0]), 'reason': reasons[int(v[1])], 'types': int(v[2]), 'maxlen': int(v[3]),
+                'table_bytes': int(v[4])}
 
     def tail_info(self) -> dict:
         """Which plan the coarse tail took (mamg_tail_info, a test hook):
@@ -757,7 +769,8 @@ class DistMetricAMG:
         return {'sell': bool(f & 1), 'sym': bool(f & 2), 'post_fused': bool(f & 4),
                 'post_k': bool(f & 8), 'post_sell': bool(f & 16), 'half': bool(f & 32),
                 'bands': bool(f & 64), 'patches': bool(f & 128), 'gs': bool(f & 256),
-                'rings': bool(f & 512), 'r_bands': bool(f & 1024), 'k_col16': bool(f & 2048)}
+                'rings': bool(f & 512), 'r_bands': bool(f & 1024), 'k_col16': bool(f & 2048),
+                'rowdict': bool(f & 4096)}
 
     def set_cycle_storage(self, storage):
         """'f32': narrow the rank-local operators the cycle streams to fp32

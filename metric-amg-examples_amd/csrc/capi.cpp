@@ -1066,6 +1066,23 @@ int mamg_tail_info(const mamg_handle* h, int index, int64_t* info, int cap) {
   GUARD_END
 }
 
+int mamg_test_set_rowdict(int64_t min_rows, int max_types, int hash_bits) {
+  GUARD_BEGIN
+  mamg::set_rowdict_hook(min_rows, max_types, hash_bits);
+  return MAMG_OK;
+  GUARD_END
+}
+
+int mamg_rowdict_info(const mamg_handle* h, int64_t* info, int cap) {
+  GUARD_BEGIN
+  if (!h || cap < 0 || (cap > 0 && !info)) {
+    set_error("mamg_rowdict_info: bad handle or buffer");
+    return MAMG_ERR_ARG;
+  }
+  return mamg::dev_rowdict_info(h->d, info, cap);
+  GUARD_END
+}
+
 int mamg_handle_options(const mamg_handle* h, char* buf, int64_t cap) {
   GUARD_BEGIN
   return write_options(h ? mamg::dev_switches(h->d) : mamg::read_switches(), buf, cap);

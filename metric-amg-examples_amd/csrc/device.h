@@ -45,6 +45,8 @@ int dev_set_cycle_storage(DeviceHandle* h, int storage, std::string* err);
 int dev_level_storage(const DeviceHandle* h, int level);
 // the coarse tail's plan (mamg_test.h mamg_tail_info)
 int dev_tail_info(const DeviceHandle* h, int index, int64_t* info, int cap);
+// the row-pattern dictionary's decision for level 0's A (mamg_test.h mamg_rowdict_info)
+int dev_rowdict_info(const DeviceHandle* h, int64_t* info, int cap);
 mamg_params dev_params(const DeviceHandle* h);
 // the switches the handle was built with (dev_upload's sw, dev_from_ghier's G->sw)
 const Switches& dev_switches(const DeviceHandle* h);

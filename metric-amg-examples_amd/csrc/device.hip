@@ -777,6 +777,117 @@ __global__ __launch_bounds__(256) void hsell2_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Row-pattern dictionary for an A0 whose node rows repeat (a constant-
+// coefficient stencil: 28 distinct rows in 3-D, 10 in 2-D, whatever the mesh
+// size).  The matrix is one 16-bit row-type code per node row plus a table
+// of a few KB: type t has rlen[t] entries (column - row, block) in the row's
+// stored column order at slots t rw + j.  No matrix stream is left: the
+// kernel reads 2 B of code per row, gathers x and streams b / out.
+// A wavefront whose 64 rows share one type (97 % of them at n = 256) takes
+// the type through readfirstlane, so the table reads are scalar loads and
+// x[node + delta] is 64 consecutive nodes, one coalesced 1 KB load; other
+// wavefronts read the table per lane (it stays in L1 / L2).
+// Each row is summed in its stored column order with hsell2_kernel's
+// expression, so the result is bitwise that of the half and SELL layouts.
+// ---------------------------------------------------------------------------
+template <bool XFM, bool SYM, int U, class VT>
+__device__ __forceinline__ void rowdict_row(int t, int64_t node, const int32_t* __restrict__ rlen,
+                                            const int32_t* __restrict__ rdelta, const VT* __restrict__ rval,
+                                            const VT* __restrict__ offd, int rw, const double* __restrict__ x,
+                                            int64_t xs, double& s0, double& s1) {
+  const int len = rlen[t];
+  const int k0 = t * rw;
+  for (int j = 0; j < len; j += U) {
+    int32_t c[U];
+    dv4 v[U];
+    double2 a[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int kk = k0 + (j + u < len ? j + u : len - 1);
+      c[u] = (int32_t)(node + rdelta[kk]);
+      v[u] = blk<SYM, false, VT>(rval, offd, kk);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) a[u] = xget<XFM>(x, xs, c[u]);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      // hsell2_kernel's and sell2_kernel's v.x * a.x + v.y * a.y as the
+      // compiler contracts it there, spelled out: left to itself it turned
+      // the products round for some entries of this kernel's fp32 side
+      const bool ok = j + u < len;
+      s0 += ok ? __builtin_fma(v[u].x, a[u].x, v[u].y * a[u].y) : 0.0;
+      s1 += ok ? __builtin_fma(v[u].z, a[u].x, v[u].w * a[u].y) : 0.0;
+    }
+  }
+}
+
+// U: entries in flight per lane on the wave-uniform path (mixed waves take 4)
+#ifndef MAMG_ROWDICT_LDS
+#define MAMG_ROWDICT_LDS 0   // 1: mixed waves read the table from LDS (A/B: slower)
+#endif
+template <int EPI, bool XFM, bool SYM, int U, int TAG, class VT = double>
+__global__ __launch_bounds__(256) void rowdict2_kernel(
+    int64_t row0, int64_t nr, const uint16_t* __restrict__ rcode, const int32_t* __restrict__ rlen,
+    const int32_t* __restrict__ rdelta, const VT* __restrict__ rval, int64_t nbs, int rw,
+    const double* __restrict__ x, int64_t xs, const double* y, const double* __restrict__ b, int64_t bs,
+    const dv4* __restrict__ W, double* out, int64_t os, int remap, const int32_t* __restrict__ sched) {
+  const int64_t blk0 = sched ? (int64_t)sched[blockIdx.x] : row_block(remap);
+  const int64_t node = row0 + blk0 * 256 + threadIdx.x;   // rows [row0, nr)
+  if (node >= nr) return;
+  const VT* offd = SYM ? rval + 2 * nbs : nullptr;
+  const int code = (int)ld_once(rcode + node);
+  const int first = __builtin_amdgcn_readfirstlane(code);
+  double s0 = 0.0, s1 = 0.0;
+  const bool mixed = __ballot(code != first) != 0;
+#if MAMG_ROWDICT_LDS
+  // A/B only: a workgroup with a mixed wave stages the
+  // table in LDS and its mixed waves read it from there
+  extern __shared__ double rowdict_lds[];
+  if (__syncthreads_or(mixed)) {   // every thread of the workgroup is live here (full blocks) or none votes
+    constexpr int PER = SYM ? 3 : 4;
+    VT* lval = reinterpret_cast<VT*>(rowdict_lds);
+    int32_t* ldel = reinterpret_cast<int32_t*>(lval + PER * nbs);
+    for (int i = threadIdx.x; i < PER * (int)nbs; i += 256) lval[i] = rval[i];
+    for (int i = threadIdx.x; i < (int)nbs; i += 256) ldel[i] = rdelta[i];
+    __syncthreads();
+    if (mixed) rowdict_row<XFM, SYM, 4, VT>(code, node, rlen, ldel, lval, SYM ? lval + 2 * nbs : nullptr, rw, x, xs, s0, s1);
+  } else if (mixed) {
+    rowdict_row<XFM, SYM, 4, VT>(code, node, rlen, rdelta, rval, offd, rw, x, xs, s0, s1);
+  }
+  if (!mixed) rowdict_row<XFM, SYM, U, VT>(first, node, rlen, rdelta, rval, offd, rw, x, xs, s0, s1);
+#else
+  if (!mixed) rowdict_row<XFM, SYM, U, VT>(first, node, rlen, rdelta, rval, offd, rw, x, xs, s0, s1);
+  else rowdict_row<XFM, SYM, 4, VT>(code, node, rlen, rdelta, rval, offd, rw, x, xs, s0, s1);
+#endif
+  double2 bb = {0.0, 0.0}, yy = {0.0, 0.0};
+  dv4 w = {0.0, 0.0, 0.0, 0.0};
+  if (EPI == EPI_RESID || EPI == EPI_BJAC)
+    bb = MAMG_HSELL_NT >= 2 ? double2{ld_once(b + (bs ? node : 2 * node)), ld_once(b + (bs ? bs + node : 2 * node + 1))}
+                            : double2{vget(b, bs, node, 0), vget(b, bs, node, 1)};
+  if (EPI == EPI_YADD || EPI == EPI_BJAC) yy = reinterpret_cast<const double2*>(y)[node];
+  if (EPI == EPI_BJAC) w = W[node];
+  double o0, o1;
+  if (EPI == EPI_Y) {
+    o0 = s0; o1 = s1;
+  } else if (EPI == EPI_YADD) {
+    o0 = yy.x + s0; o1 = yy.y + s1;
+  } else if (EPI == EPI_RESID) {
+    o0 = bb.x - s0; o1 = bb.y - s1;
+  } else {  // EPI_BJAC
+    const double r0 = bb.x - s0, r1 = bb.y - s1;
+    o0 = yy.x + (w.x * r0 + w.y * r1);
+    o1 = yy.y + (w.z * r0 + w.w * r1);
+  }
+  if constexpr (MAMG_HSELL_NT >= 2) {
+    __builtin_nontemporal_store(o0, out + (os ? node : 2 * node));
+    __builtin_nontemporal_store(o1, out + (os ? os + node : 2 * node + 1));
+  } else {
+    vset(out, os, node, 0, o0);
+    vset(out, os, node, 1, o1);
+  }
+}
+
 // fused prolongation + first post sweep on a SELL-64 [P | AP] (see
 // bsr2_post_kernel).  Rows are sorted by length inside windows of
 // SELL_SIGMA rows (slot i holds row perm[i]) so a wavefront's lanes have
@@ -3652,6 +3763,241 @@ int build_rest_sched(HandleMem* h, TmpPool* T, DBsr* D, int64_t Sf, std::string*
   return MAMG_OK;
 }
 
+// ---- row-pattern dictionary (DBsr::rowdict, rowdict2_kernel) ----------------
+constexpr int RD_SLOTS = 4096;   // hash table slots (>= 2 x the cap on types)
+
+__device__ __forceinline__ unsigned long long rd_mix(unsigned long long h, unsigned long long w) {
+  h = (h ^ w) * 0x9E3779B97F4A7C15ull;
+  return h ^ (h >> 29);
+}
+__device__ __forceinline__ int rd_slot0(unsigned long long key) {
+  return (int)((key * 0xD6E8FEB86659FD93ull) >> 52);   // RD_SLOTS = 2^12
+}
+
+// Key of every node row: the hash of (length, column - row and value bits of
+// each block) masked to `bits` bits, plus 1 (0 marks an empty slot).  The key
+// goes into a small open-addressed table with the smallest row that holds it.
+// flags: [0] distinct keys, [1] abort (too many keys), [2] a row longer than
+// maxlen, [3] longest row.  Nearly every row meets its key already in the
+// table with a smaller row: those issue no atomic.
+__global__ __launch_bounds__(256) void rowdict_hash_kernel(int64_t nr, const int64_t* __restrict__ ptr,
+                                                           const int32_t* __restrict__ col,
+                                                           const dv4* __restrict__ val, int bits, int max_types,
+                                                           int maxlen, unsigned long long* keys,
+                                                           unsigned long long* minrow, int* flags,
+                                                           unsigned long long* __restrict__ rowkey) {
+  const int64_t I = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (I >= nr) return;
+  // every row's length is looked at (the refusal reason does not depend on
+  // timing); the hashing stops once the attempt is lost
+  const int64_t p0 = ptr[I], p1 = ptr[I + 1];
+  const int64_t len = p1 - p0;
+  if (len > __hip_atomic_load(flags + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+    atomicMax(flags + 3, (int)(len < 0x7fffffff ? len : 0x7fffffff));
+  if (len > maxlen) { atomicOr(flags + 2, 1); return; }
+  if (__hip_atomic_load(flags + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) |
+      __hip_atomic_load(flags + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+    return;
+  unsigned long long h = rd_mix(0x243F6A8885A308D3ull, (unsigned long long)len);
+  for (int64_t k = p0; k < p1; ++k) {
+    const dv4 v = val[k];
+    h = rd_mix(h, (unsigned long long)(int64_t)(col[k] - I));
+    h = rd_mix(h, (unsigned long long)__double_as_longlong(v.x));
+    h = rd_mix(h, (unsigned long long)__double_as_longlong(v.y));
+    h = rd_mix(h, (unsigned long long)__double_as_longlong(v.z));
+    h = rd_mix(h, (unsigned long long)__double_as_longlong(v.w));
+  }
+  const unsigned long long key = (h & ((1ull << bits) - 1ull)) + 1ull;
+  rowkey[I] = key;
+  int s = rd_slot0(key);
+  for (int probe = 0; probe < RD_SLOTS; ++probe, s = (s + 1) & (RD_SLOTS - 1)) {
+    unsigned long long cur = __hip_atomic_load(keys + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == 0ull) {
+      cur = atomicCAS(keys + s, 0ull, key);
+      if (cur == 0ull) {
+        if (atomicAdd(flags, 1) + 1 > max_types) atomicOr(flags + 1, 1);
+        cur = key;
+      }
+    }
+    if (cur == key) {
+      if (__hip_atomic_load(minrow + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (unsigned long long)I)
+        atomicMin(minrow + s, (unsigned long long)I);
+      return;
+    }
+  }
+  atomicOr(flags + 1, 1);   // table full
+}
+
+// the table: entry j of type t from the type's first row reps[t]
+__global__ __launch_bounds__(256) void rowdict_table_kernel(int nt, int rw, const int64_t* __restrict__ reps,
+                                                            const int64_t* __restrict__ ptr,
+                                                            const int32_t* __restrict__ col,
+                                                            const dv4* __restrict__ val, int sym,
+                                                            int32_t* __restrict__ rlen, int32_t* __restrict__ rdelta,
+                                                            double* __restrict__ rval) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nt * rw) return;
+  const int t = i / rw, j = i % rw;
+  const int64_t I = reps[t], p0 = ptr[I];
+  const int len = (int)(ptr[I + 1] - p0);
+  if (j == 0) rlen[t] = len;
+  dv4 a = {0.0, 0.0, 0.0, 0.0};
+  int32_t d = 0;
+  if (j < len) {
+    a = val[p0 + j];
+    d = (int32_t)(col[p0 + j] - I);
+  }
+  rdelta[i] = d;
+  if (sym) {
+    const int64_t nbs = (int64_t)nt * rw;
+    rval[2 * i] = a.x;
+    rval[2 * i + 1] = a.w;
+    rval[2 * nbs + i] = a.y;
+  } else {
+    reinterpret_cast<dv4*>(rval)[i] = a;
+  }
+}
+
+// Every row against its type's table, entry by entry and bitwise (length,
+// column - row, all four value words) and 0 <= row + delta < nc; the row's
+// code is written.  Any difference (a hash collision included) sets *bad.
+__global__ __launch_bounds__(256) void rowdict_verify_kernel(int64_t nr, int64_t nc, const int64_t* __restrict__ ptr,
+                                                             const int32_t* __restrict__ col,
+                                                             const dv4* __restrict__ val,
+                                                             const unsigned long long* __restrict__ rowkey,
+                                                             const unsigned long long* __restrict__ keys,
+                                                             const int32_t* __restrict__ slot_type, int rw,
+                                                             const int64_t* __restrict__ reps,
+                                                             const int32_t* __restrict__ rlen,
+                                                             const int32_t* __restrict__ rdelta,
+                                                             uint16_t* __restrict__ rcode, int* bad) {
+  const int64_t I = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (I >= nr) return;
+  const unsigned long long key = rowkey[I];
+  int s = rd_slot0(key), t = -1;
+  for (int probe = 0; probe < RD_SLOTS; ++probe, s = (s + 1) & (RD_SLOTS - 1)) {
+    const unsigned long long cur = keys[s];
+    if (cur == key) { t = slot_type[s]; break; }
+    if (cur == 0ull) break;
+  }
+  if (t < 0) { atomicOr(bad, 1); rcode[I] = 0; return; }
+  rcode[I] = (uint16_t)t;
+  const int64_t p0 = ptr[I], q0 = ptr[reps[t]];
+  const int len = rlen[t];
+  bool ok = ptr[I + 1] - p0 == (int64_t)len;
+  if (ok)
+    for (int j = 0; j < len; ++j) {
+      const int64_t d = (int64_t)col[p0 + j] - I, c = I + d;
+      const dv4 a = val[p0 + j], r = val[q0 + j];
+      ok = ok && d == (int64_t)rdelta[t * rw + j] && c >= 0 && c < nc &&
+           __double_as_longlong(a.x) == __double_as_longlong(r.x) &&
+           __double_as_longlong(a.y) == __double_as_longlong(r.y) &&
+           __double_as_longlong(a.z) == __double_as_longlong(r.z) &&
+           __double_as_longlong(a.w) == __double_as_longlong(r.w);
+    }
+  if (!ok) atomicOr(bad, 1);
+}
+
+// Row-pattern dictionary for the one-GPU level-0 A (nr == nc).  Returns
+// MAMG_OK with D->rowdict set, or MAMG_OK with it false and the reason in
+// D->rdinfo[RD_REASON] (the caller then builds the half / SELL layout exactly
+// as without the attempt; the temporaries of a refused attempt go back to the
+// pool).  The types are numbered by the smallest row that holds each, which
+// does not depend on the order the atomics ran in.
+int try_rowdict(HandleMem* h, TmpPool* T, const TBsr& B, DBsr* D, bool sym, std::string* err) {
+  int rc;
+  const int64_t nr = B.nr;
+  int64_t* info = D->rdinfo;
+  info[RD_TAKEN] = 0;
+  auto refuse = [&](int why) { info[RD_REASON] = why; return MAMG_OK; };
+  if (nr != B.nc) return refuse(RDR_NOT_SQUARE);
+  if (nr < h->sw.rowdict_min_rows || nr < 1 || B.nb < 1) return refuse(RDR_THRESHOLD);
+  const int max_types = h->sw.rowdict_max_types;
+  unsigned long long *keys = nullptr, *minrow = nullptr, *rowkey = nullptr;
+  int* flags = nullptr;   // + [4]: the verification's mismatch flag
+  if ((rc = T->alloc(&keys, RD_SLOTS, err))) return rc;
+  if ((rc = T->alloc(&minrow, RD_SLOTS, err))) return rc;
+  if ((rc = T->alloc(&flags, 8, err))) return rc;
+  if ((rc = T->alloc(&rowkey, nr, err))) return rc;
+  auto drop = [&](int why) {
+    T->release(keys); T->release(minrow); T->release(flags); T->release(rowkey);
+    return refuse(why);
+  };
+  HIPCHK(dev_memset(keys, 0, RD_SLOTS * sizeof(unsigned long long)));
+  HIPCHK(dev_memset(minrow, 0xff, RD_SLOTS * sizeof(unsigned long long)));
+  HIPCHK(dev_memset(flags, 0, 8 * sizeof(int)));
+  rowdict_hash_kernel<<<nblocks(nr), 256>>>(nr, B.ptr, B.col, B.val, h->sw.rowdict_hash_bits, max_types,
+                                            ROWDICT_MAX_LEN, keys, minrow, flags, rowkey);
+  HIPCHK(hipGetLastError());
+  int hf[4] = {0, 0, 0, 0};
+  HIPCHK(hipMemcpy(hf, flags, sizeof hf, hipMemcpyDeviceToHost));
+  info[RD_TYPES] = hf[0];
+  info[RD_MAXLEN] = hf[3];
+  if (hf[2]) return drop(RDR_LENGTH);
+  if (hf[1] || hf[0] > max_types) return drop(RDR_TYPES);
+  std::vector<unsigned long long> hk(RD_SLOTS), hm(RD_SLOTS);
+  HIPCHK(hipMemcpy(hk.data(), keys, RD_SLOTS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(hm.data(), minrow, RD_SLOTS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  std::vector<std::pair<int64_t, int>> occ;   // (first row, slot)
+  for (int s = 0; s < RD_SLOTS; ++s)
+    if (hk[s]) occ.push_back({(int64_t)hm[s], s});
+  std::sort(occ.begin(), occ.end());
+  const int nt = (int)occ.size(), rw = hf[3];
+  if (nt < 1 || rw < 1) return drop(RDR_THRESHOLD);
+  const int per = sym ? 3 : 4;
+  const int64_t nbs = (int64_t)nt * rw;
+  const int64_t table = 4 * (int64_t)nt + nbs * (4 + 8 * per);
+  info[RD_TABLE_BYTES] = table;
+  if (table > ROWDICT_MAX_TABLE) return drop(RDR_TABLE);
+  std::vector<int32_t> st(RD_SLOTS, -1);
+  std::vector<int64_t> reps(nt);
+  for (int t = 0; t < nt; ++t) {
+    st[occ[t].second] = t;
+    reps[t] = occ[t].first;
+  }
+  int32_t *slot_type = nullptr, *rlen = nullptr, *rdelta = nullptr;
+  int64_t* dreps = nullptr;
+  double* rval = nullptr;
+  uint16_t* rcode = nullptr;
+  if ((rc = T->alloc(&slot_type, RD_SLOTS, err))) return rc;
+  if ((rc = T->alloc(&dreps, nt, err))) return rc;
+  if ((rc = T->alloc(&rlen, nt, err))) return rc;
+  if ((rc = T->alloc(&rdelta, nbs, err))) return rc;
+  if ((rc = T->alloc(&rval, per * nbs, err))) return rc;
+  if ((rc = T->alloc(&rcode, nr, err))) return rc;
+  auto drop2 = [&](int why) {
+    T->release(slot_type); T->release(dreps); T->release(rlen); T->release(rdelta); T->release(rval);
+    T->release(rcode);
+    return drop(why);
+  };
+  HIPCHK(hipMemcpy(slot_type, st.data(), RD_SLOTS * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dreps, reps.data(), nt * sizeof(int64_t), hipMemcpyHostToDevice));
+  rowdict_table_kernel<<<nblocks(nbs), 256>>>(nt, rw, dreps, B.ptr, B.col, B.val, sym ? 1 : 0, rlen, rdelta, rval);
+  HIPCHK(hipGetLastError());
+  rowdict_verify_kernel<<<nblocks(nr), 256>>>(nr, B.nc, B.ptr, B.col, B.val, rowkey, keys, slot_type, rw, dreps, rlen,
+                                              rdelta, rcode, flags + 4);
+  HIPCHK(hipGetLastError());
+  int bad = 1;
+  HIPCHK(hipMemcpy(&bad, flags + 4, sizeof(int), hipMemcpyDeviceToHost));
+  if (bad) return drop2(RDR_VERIFY);
+  if ((rc = dalloc(h, &D->rcode, nr, err))) return rc;
+  if ((rc = dalloc(h, &D->rlen, nt, err))) return rc;
+  if ((rc = dalloc(h, &D->rdelta, nbs, err))) return rc;
+  if ((rc = dalloc(h, &D->val, per * nbs, err))) return rc;
+  HIPCHK(dev_copy(D->rcode, rcode, nr * sizeof(uint16_t)));
+  HIPCHK(dev_copy(D->rlen, rlen, nt * sizeof(int32_t)));
+  HIPCHK(dev_copy(D->rdelta, rdelta, nbs * sizeof(int32_t)));
+  HIPCHK(dev_copy(D->val, rval, per * nbs * sizeof(double)));
+  drop2(RDR_NONE);
+  D->rowdict = true;
+  D->rw = rw;
+  D->rtypes = nt;
+  D->nbs = nbs;
+  info[RD_TAKEN] = 1;
+  info[RD_TYPES] = nt;
+  return build_band_sched(h, B, D, err);
+}
+
 }  // namespace
 
 // half-symmetric ELL-64 for a symmetric-block A whose owned part (columns
@@ -3783,7 +4129,12 @@ int finalize_bsr(HandleMem* h, TmpPool* T, TBsr& B, DBsr* D, int lanes, bool sym
     const double mean = nr ? (double)D->nb / (double)nr : 0.0;
     D->lpr = mean <= 10.0 ? 2 : mean <= 20.0 ? 4 : mean <= 40.0 ? 8 : 16;
   }
+  if (allow_half) D->rdinfo[RD_REASON] = RDR_THRESHOLD;   // the one-GPU level-0 A: below the SELL threshold
   if (allow_sell && ((nr >= h->sw.sell_min_rows && D->nb <= sell_max_len * nr) || msell) && !B.merged) {
+    if (allow_half) {   // rows that repeat: the row-pattern dictionary, no matrix stream at all
+      if ((rc = try_rowdict(h, T, B, D, sym, err))) return rc;
+      if (D->rowdict) return MAMG_OK;
+    }
     if (allow_half && h->sw.half && sym && nr == B.nc) {
       if ((rc = try_half(h, T, B, D, err))) return rc;
       if (D->half) return MAMG_OK;
@@ -4643,6 +4994,15 @@ double bsr_bytes(const DBsr& M, int epi) {
   // with its column is 16 B (SYM / half), 18 B (16-bit column) or 20 B
   const double vb = M.f32 ? 4.0 : 8.0;
   const double sym_b = 3.0 * vb + 4.0, c16_b = 4.0 * vb + 2.0, gen_b = 4.0 * vb + 4.0;
+  // row-pattern dictionary: one 16-bit code per row and the type table
+  // (lengths, column offsets, blocks), x and out; no matrix stream
+  if (M.rowdict) {
+    double b = 2.0 * M.nr + 4.0 * M.rtypes + (4.0 + (M.sym ? 3.0 : 4.0) * vb) * M.nbs + 16.0 * M.nc + 16.0 * M.nr;
+    if (epi == EPI_YADD) b += 16.0 * M.nr;
+    if (epi == EPI_RESID) b += 16.0 * M.nr;
+    if (epi == EPI_BJAC || epi == EPI_KPOST) b += 16.0 * M.nr + 16.0 * M.nr + 32.0 * M.nr;   // y, b, W
+    return b;
+  }
   double b = M.half ? sym_b * (M.nb - M.nlo) + 4.0 * M.nlo + 4.0 * M.nr + (M.ngs ? 8.0 * (M.nr / SELL_C + 2) : 0.0) +
                           16.0 * M.nc + 16.0 * M.nr
                     : (M.sym ? sym_b : M.col16 ? c16_b : gen_b) * M.nb + index_bytes(M, M.nr + 1) +
@@ -4981,7 +5341,7 @@ bool to_tail(const Op& o, int vl_cap, TOp* t) {
     case OP_BSR:
     case OP_GS: {
       const DBsr& M = *o.Mb;
-      if (M.sell || M.half || M.split || o.xs || o.bs || o.os || o.xfm || M.lanes < 1 || M.lanes > 64) return false;
+      if (M.sell || M.half || M.rowdict || M.split || o.xs || o.bs || o.os || o.xfm || M.lanes < 1 || M.lanes > 64) return false;
       t->kind = o.kind == OP_GS ? T_GS : T_BSR;
       t->epi = o.epi; t->vl = std::min(M.lanes, vl_cap); t->sym = M.sym ? 1 : 0; t->n = M.nr; t->nb = M.nb;
       t->ptr = M.ptr; t->col = M.col; t->val = M.val;
@@ -5780,8 +6140,46 @@ void launch_half(const Op& o, hipStream_t s) {
   }
 }
 
+// row-pattern dictionary (rowdict2_kernel); the band schedule as for the half
+// layout.  Entries in flight per lane on the wave-uniform path: build switch
+// for A/Bs
+#ifndef MAMG_ROWDICT_U
+#define MAMG_ROWDICT_U 8
+#endif
+constexpr int ROWDICT_U = MAMG_ROWDICT_U;
+
+template <bool XFM, bool SYM, int TAG, class VT = double>
+void launch_rowdict_x(const Op& o, hipStream_t s) {
+  const DBsr& M = *o.Mb;
+  const int64_t r0 = o.r1 < 0 ? 0 : o.r0, r1 = o.r1 < 0 ? M.nr : o.r1;
+  const unsigned g = nblocks(r1 - r0);
+  if (r1 <= r0) return;
+  const size_t lds = MAMG_ROWDICT_LDS ? (size_t)M.nbs * (4 + (SYM ? 3 : 4) * sizeof(VT)) : 0;
+#define RD_ARGS r0, r1, M.rcode, M.rlen, M.rdelta, reinterpret_cast<const VT*>(M.val), M.nbs, M.rw, \
+    o.x, o.xs, o.y, o.b, o.bs, o.W, o.out, o.os, 1, \
+    (r0 == 0 && r1 == M.nr && (int64_t)g == M.nsched) ? M.sched : nullptr
+  switch (o.epi) {
+    case EPI_Y: rowdict2_kernel<EPI_Y, XFM, SYM, ROWDICT_U, TAG, VT><<<g, 256, lds, s>>>(RD_ARGS); break;
+    case EPI_YADD: rowdict2_kernel<EPI_YADD, XFM, SYM, ROWDICT_U, TAG, VT><<<g, 256, lds, s>>>(RD_ARGS); break;
+    case EPI_RESID: rowdict2_kernel<EPI_RESID, XFM, SYM, ROWDICT_U, TAG, VT><<<g, 256, lds, s>>>(RD_ARGS); break;
+    case EPI_KPOST: break;   // A is never the K operator
+    default: rowdict2_kernel<EPI_BJAC, XFM, SYM, ROWDICT_U, TAG, VT><<<g, 256, lds, s>>>(RD_ARGS); break;
+  }
+#undef RD_ARGS
+}
+
+template <int TAG, class VT = double>
+void launch_rowdict(const Op& o, hipStream_t s) {
+  if (o.Mb->sym) {
+    if (o.xfm) launch_rowdict_x<true, true, TAG, VT>(o, s); else launch_rowdict_x<false, true, TAG, VT>(o, s);
+  } else {
+    if (o.xfm) launch_rowdict_x<true, false, TAG, VT>(o, s); else launch_rowdict_x<false, false, TAG, VT>(o, s);
+  }
+}
+
 template <int TAG, class VT = double>
 void launch_bsr_st(const Op& o, hipStream_t s) {
+  if (o.Mb->rowdict) { launch_rowdict<TAG, VT>(o, s); return; }
   if (o.Mb->half) { launch_half<TAG, VT>(o, s); return; }
   if (o.Mb->sell) { launch_sell<TAG, VT>(o, s); return; }
   switch (o.Mb->lanes) {
@@ -6052,6 +6450,7 @@ void rehome_array(DeviceHandle* h, void** ptr, size_t b) {
 // values and columns of one operator (half-symmetric: the upper part)
 void rehome_bsr(DeviceHandle* h, DBsr& M) {
   if (M.nr == 0) return;
+  if (M.rowdict) return;   // a few KB of table: nothing to place
   const int64_t slots = (M.sell || M.half) ? M.nbs : M.nb;
   rehome_array(h, (void**)&M.val, (size_t)slots * ((M.sym || M.half) ? 3 : 4) * sizeof(double));
   rehome_array(h, (void**)&M.col, (size_t)slots * sizeof(int32_t));
@@ -6271,9 +6670,10 @@ void debug_sums(DeviceHandle* h, const char* stage, bool konly) {
       const DBsr& M = *m.second;
       if (!M.nr) continue;
       const int per = (M.sym || M.half) ? 3 : 4;
-      const int64_t slots = (M.sell || M.half) ? M.nbs : M.nb;
+      const int64_t slots = (M.sell || M.half || M.rowdict) ? M.nbs : M.nb;
       std::snprintf(buf, sizeof buf, " L%zu.%s val %016llx col %016llx", l, m.first,
-                    hash(M.val, (size_t)slots * per * (M.f32 ? 4 : 8)), hash(M.col, (size_t)slots * 4));
+                    hash(M.val, (size_t)slots * per * (M.f32 ? 4 : 8)),
+                    M.rowdict ? hash(M.rdelta, (size_t)slots * 4) : hash(M.col, (size_t)slots * 4));
       line += buf;
     }
     if (L.Wd) {
@@ -6638,6 +7038,7 @@ int dev_layout(const DeviceHandle* h) { return h->bsr ? 1 : 0; }
 int dev_level_format(const DeviceHandle* h, int level) {
   const DLevel& L = h->L[level];
   return (L.Ab.sell ? MAMG_FMT_SELL : 0) | (L.Ab.sym ? MAMG_FMT_SYM : 0) | (L.Ab.half ? MAMG_FMT_HALF : 0) |
+         (L.Ab.rowdict ? MAMG_FMT_ROWDICT : 0) |
          (L.PAb.nr > 0 || L.KPb.nr > 0 ? MAMG_FMT_POST_FUSED : 0) | (L.KPb.nr > 0 ? MAMG_FMT_POST_K : 0) |
          (L.KPb.sell ? MAMG_FMT_POST_SELL : 0) | (L.Ab.nsched > 0 || L.Ab.nsched_r > 0 ? MAMG_FMT_BANDS : 0) |
          (L.pcs.size() > 1 ? MAMG_FMT_PATCHES : 0) | (L.gcs.size() > 1 ? MAMG_FMT_GS : 0) |
@@ -6745,6 +7146,15 @@ void release_owned(DeviceHandle* h, void* old) {
 }  // namespace
 
 int dev_level_storage(const DeviceHandle* h, int level) { return h->L[level].storage; }
+
+int dev_rowdict_info(const DeviceHandle* h, int64_t* info, int cap) {
+  const DBsr& A = h->L[0].Ab;
+  int64_t v[RD_INFO_N];
+  for (int i = 0; i < RD_INFO_N; ++i) v[i] = A.rdinfo[i];
+  if (!h->bsr) v[RD_REASON] = RDR_NOT_TRIED;
+  for (int i = 0; i < cap && i < RD_INFO_N; ++i) info[i] = v[i];
+  return RD_INFO_N;
+}
 
 int dev_tail_info(const DeviceHandle* h, int index, int64_t* info, int cap) {
   std::lock_guard<std::recursive_mutex> lock(capture_mutex());

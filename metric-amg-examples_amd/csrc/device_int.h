@@ -196,7 +196,25 @@ struct DBsr {              // 2x2 blocks, node-major
   // values stored fp32 (dev_set_cycle_storage): val then points to a float
   // array of the same element layout, read by the kernels' float side
   bool f32 = false;
+  // row-pattern dictionary (rowdict == true, a level-0 A whose node rows
+  // repeat; rowdict2_kernel): rcode holds one row-type code per node row;
+  // type t has rlen[t] entries, entry j at slot t rw + j of rdelta (column -
+  // row, in the row's stored column order) and of val (nbs = types x rw
+  // slots of the SYM or general block layout; padding slots are zero).  ptr,
+  // col, meta are unused; sched / band_stride as for the half layout.
+  bool rowdict = false;
+  uint16_t* rcode = nullptr;
+  int32_t* rlen = nullptr;
+  int32_t* rdelta = nullptr;
+  int rw = 0, rtypes = 0;
+  // what the builder decided (mamg_test.h mamg_rowdict_info, RD_*)
+  int64_t rdinfo[5] = {0, 0, 0, 0, 0};
 };
+
+// mamg_rowdict_info's values and refusal reasons (include/mamg_test.h)
+enum RowdictInfo { RD_TAKEN = 0, RD_REASON, RD_TYPES, RD_MAXLEN, RD_TABLE_BYTES, RD_INFO_N };
+enum RowdictReason { RDR_NONE = 0, RDR_TYPES = 1, RDR_LENGTH = 2, RDR_VERIFY = 3, RDR_THRESHOLD = 4, RDR_NOT_SQUARE = 5,
+                     RDR_TABLE = 6, RDR_NOT_TRIED = 7 };
 
 struct DLevel {
   int64_t n = 0;           // dofs
@@ -538,7 +556,7 @@ enum TailInfo { TI_PROGS = 0, TI_LEVEL, TI_OPS, TI_LDS, TI_XL, TI_RES, TI_PROG_L
 // stored values of an operator's main array (rehome_bsr's count)
 inline int64_t value_count(const DBsr& M) {
   if (M.nr == 0 || !M.val) return 0;
-  const int64_t slots = (M.sell || M.half) ? M.nbs : M.nb;
+  const int64_t slots = (M.sell || M.half || M.rowdict) ? M.nbs : M.nb;
   return slots * ((M.sym || M.half) ? 3 : 4);
 }
 // stored values of a half-symmetric operator's ghost part (gval: the diagonal

@@ -27,6 +27,8 @@ struct Table {
   std::map<std::string, size_t> set;   // name -> index into vals
   std::deque<std::string> vals;        // never shrinks: returned pointers stay valid
   std::string names;
+  int64_t rd_min_rows = -1;            // set_rowdict_hook (negative: default)
+  int rd_max_types = -1, rd_hash_bits = -1;
 };
 Table& table() {
   static Table t;
@@ -108,6 +110,9 @@ Switches read_switches() {
     if (const char* e = find(t, #name)) parse(e, &s.field);
     MAMG_SWITCHES(X)
 #undef X
+    if (t.rd_min_rows >= 0) s.rowdict_min_rows = t.rd_min_rows;
+    if (t.rd_max_types >= 0) s.rowdict_max_types = std::max(1, std::min(2048, t.rd_max_types));
+    if (t.rd_hash_bits >= 0) s.rowdict_hash_bits = std::max(1, std::min(62, t.rd_hash_bits));
   }
   s.tail_vl = std::max(1, std::min(64, s.tail_vl));
   s.upload_threads = std::max(1, std::min(16, s.upload_threads));
@@ -116,6 +121,14 @@ Switches read_switches() {
   if (const char* e = std::getenv("MAMG_K_VARIANT")) s.k_variant = std::atoi(e);
 #endif
   return s;
+}
+
+void set_rowdict_hook(int64_t min_rows, int max_types, int hash_bits) {
+  Table& t = table();
+  std::lock_guard<std::mutex> g(t.m);
+  t.rd_min_rows = min_rows;
+  t.rd_max_types = max_types;
+  t.rd_hash_bits = hash_bits;
 }
 
 std::string format_switches(const Switches& s) {

@@ -56,6 +56,16 @@ struct AutoCount {
   X(MAMG_UPLOAD_THREADS, upload_threads, int, 2) /* host threads copying A0, clamped to [1, 16] */ \
   X(MAMG_PATCH_INV, patch_inv, int, 3) /* node-patch inverses: 1 one patch per wave, 2 two per wave, else 3 matrix cores */
 
+// Row-pattern dictionary of a level-0 A: tried from
+// ROWDICT_MIN_ROWS node rows.  The bound stays above 3-D n=128 (2,146,689
+// rows), where one plane band of the half layout's upper values still fits an
+// XCD's L2 and the mirrors cost no HBM traffic.
+constexpr int64_t ROWDICT_MIN_ROWS = (int64_t)1 << 22;
+constexpr int ROWDICT_MAX_TYPES = 256;    // row types at most (64 KB of table / ~9 blocks of 28 B per type)
+constexpr int ROWDICT_MAX_LEN = 32;       // blocks in a row at most
+constexpr int ROWDICT_HASH_BITS = 62;     // bits kept of a row's hash
+constexpr int64_t ROWDICT_MAX_TABLE = 64 << 10;   // bytes of the type table at most
+
 struct Switches {
 #define X(name, field, type, def) type field = def;
   MAMG_SWITCHES(X)
@@ -63,7 +73,17 @@ struct Switches {
   // diagnosis build only (the environment's MAMG_K_VARIANT; always 0 in the
   // product): the level-0 K kernel, see launch_kvariant
   int k_variant = 0;
+  // the row-pattern dictionary's thresholds (mamg_test.h mamg_test_set_rowdict;
+  // not switches: a test hook, defaults in the product): node rows from which
+  // a level-0 A is tried, the cap on row types, the bits kept of a row's hash
+  int64_t rowdict_min_rows = ROWDICT_MIN_ROWS;
+  int rowdict_max_types = ROWDICT_MAX_TYPES;
+  int rowdict_hash_bits = ROWDICT_HASH_BITS;
 };
+
+// process-wide thresholds of the row-pattern dictionary, read by the next
+// read_switches() (a negative value: the default)
+void set_rowdict_hook(int64_t min_rows, int max_types, int hash_bits);
 
 // the switch's value (nullptr: unset, the built-in default applies)
 const char* opt(const char* name);

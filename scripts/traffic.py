@@ -11,7 +11,7 @@ streaming kernel reads (4..32-byte lanes alike), WRITE_SIZE * 1024 = 1.0 x
 the bytes written (full and half 128-byte lines alike).  So
     bytes = 2 * 1024 * FETCH_SIZE + 1024 * WRITE_SIZE.
 Kernel -> class (per launch, medians over the launches of the largest grid):
-  L0_resid        sell2 / hsell2 / bsr2 with EPI_RESID = 2, TAG 0
+  L0_resid        rowdict2 / sell2 / hsell2 / bsr2 with EPI_RESID = 2, TAG 0
   L0_smooth_spmv  the fused post kernel: msell <.., KPOST, .., TAG 0> / bsr2_post TAG 0
   L0_restrict     bsr2 with EPI_Y = 0, TAG 0 (R_0 r_1)
   L0_smoother     bd2_kernel at level 0's grid (the first pre-smoothing W r)
@@ -31,7 +31,7 @@ FETCH_SCALE = 2 * 1024
 WRITE_SCALE = 1024
 
 
-FAMILY = r'(hsell2_kernel|msell_kernel|sell2_kernel|bsr2_kernel|bsr2_post_kernel|gs2_kernel)<([^>]*)>'
+FAMILY = r'(rowdict2_kernel|hsell2_kernel|msell_kernel|sell2_kernel|bsr2_kernel|bsr2_post_kernel|gs2_kernel)<([^>]*)>'
 
 
 def classify(name):
@@ -53,7 +53,9 @@ def classify(name):
         return None
     if kind == 'bsr2_post_kernel':
         return 'L0_smooth_spmv' if targs[-1] == '0' else 'coarse'
-    if kind in ('sell2_kernel', 'hsell2_kernel'):
+    if kind == 'rowdict2_kernel':       # <EPI, XFM, SYM, U, TAG, VT>
+        epi, xfm, tag = targs[0], targs[1], targs[4]
+    elif kind in ('sell2_kernel', 'hsell2_kernel'):
         epi, xfm, tag = targs[0], targs[1], targs[-1]
     else:                               # bsr2_kernel <VL, EPI, XFM, SYM, TAG, NT>
         epi, xfm, tag = targs[1], targs[2], targs[4]
@@ -111,7 +113,7 @@ def main():
     ap.add_argument('--layout', default='bsr2')
     ap.add_argument('--post', default='k', choices=('k', 'merged'),
                     help='post-smoothing operator the profiled run used (MAMG_POST_K)')
-    ap.add_argument('--a0', default='half', choices=('half', 'sell'),
+    ap.add_argument('--a0', default='half', choices=('half', 'sell', 'rowdict'),
                     help='level-0 operator storage of the profiled run')
     ap.add_argument('--out', default='profiles/traffic.json')
     ap.add_argument('--bench-json', default=None,
