@@ -55,7 +55,7 @@ std::recursive_mutex& capture_mutex() {
   static std::recursive_mutex m;
   return m;
 }
-hipError_t graph_instantiate(hipGraphExec_t* ex, hipGraph_t g) {
+static hipError_t graph_instantiate(hipGraphExec_t* ex, hipGraph_t g) {
   size_t nodes = 0;
   hipError_t e = hipGraphGetNodes(g, nullptr, &nodes);
   if (e != hipSuccess) return e;
@@ -83,6 +83,35 @@ hipError_t graph_instantiate(hipGraphExec_t* ex, hipGraph_t g) {
   if (rc != 0) return hipErrorOutOfMemory;
   pthread_join(t, nullptr);
   return job.e;
+}
+
+int capture_graph(hipStream_t* cap, const std::function<int()>& body, const char* what, CapturedGraph* out,
+                  std::string* err) {
+  *out = CapturedGraph();
+  std::lock_guard<std::recursive_mutex> capture_lock(capture_mutex());
+  hipGraph_t g = nullptr;
+  hipGraphExec_t ex = nullptr;
+  int rc = MAMG_OK;
+  hipError_t e = *cap ? hipSuccess : hipStreamCreateWithFlags(cap, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipStreamBeginCapture(*cap, hipStreamCaptureModeThreadLocal);
+  if (e == hipSuccess) {
+    rc = body();
+    e = hipStreamEndCapture(*cap, &g);   // also after a failed body: the stream must leave capture mode
+  }
+  const char* stage = "stream capture of the ";
+  if (!rc && e == hipSuccess) {
+    e = graph_instantiate(&ex, g);
+    stage = "hipGraphInstantiate of the ";
+  }
+  if (rc || e != hipSuccess) {
+    if (g) (void)hipGraphDestroy(g);
+    (void)hipGetLastError();
+    if (!rc) *err = std::string(stage) + what + ": " + hipGetErrorString(e);
+    return rc ? rc : MAMG_ERR_HIP;
+  }
+  out->graph = g;
+  out->exec = ex;
+  return MAMG_OK;
 }
 
 namespace {
@@ -5888,65 +5917,58 @@ Op a0_op(const DeviceHandle* h, int epi, const double* x, const double* b, doubl
   return csr_op(L0.A, epi, C_MISC, 1, x, nullptr, b, nullptr, out);
 }
 
-template <int VL, int TAG>
-void launch_csr_vl(const Op& o, hipStream_t s) {
-  const DCsr& M = *o.M;
-  const int64_t r0 = o.r1 >= 0 ? o.r0 : 0, r1 = o.r1 >= 0 ? o.r1 : M.n;   // row range (multi-GPU), else all rows
-  if (r1 <= r0) return;
-  const unsigned g = nblocks((r1 - r0) * (int64_t)VL);
-  switch (o.epi) {
-    case EPI_Y:
-      csr_kernel<VL, EPI_Y, TAG><<<g, 256, 0, s>>>(r0, r1, M.ptr, M.col, M.val, o.x, o.y, o.b, o.w, o.out);
-      break;
-    case EPI_YADD:
-      csr_kernel<VL, EPI_YADD, TAG><<<g, 256, 0, s>>>(r0, r1, M.ptr, M.col, M.val, o.x, o.y, o.b, o.w, o.out);
-      break;
-    case EPI_RESID:
-      csr_kernel<VL, EPI_RESID, TAG><<<g, 256, 0, s>>>(r0, r1, M.ptr, M.col, M.val, o.x, o.y, o.b, o.w, o.out);
-      break;
-    default:
-      csr_kernel<VL, EPI_JACOBI, TAG><<<g, 256, 0, s>>>(r0, r1, M.ptr, M.col, M.val, o.x, o.y, o.b, o.w, o.out);
-      break;
-  }
-}
+// ---- the launch ladder: an op's run-time fields become template arguments
+// through the with_* helpers (device_int.h), so each kernel family's launch
+// statement is written once.  The `if constexpr` guards keep the set of
+// instantiated kernels to the combinations the planner builds.
 
 template <int TAG>
 void launch_csr_tag(const Op& o, hipStream_t s) {
-  switch (o.M->lanes) {
-    case 2: launch_csr_vl<2, TAG>(o, s); break;
-    case 4: launch_csr_vl<4, TAG>(o, s); break;
-    case 8: launch_csr_vl<8, TAG>(o, s); break;
-    case 16: launch_csr_vl<16, TAG>(o, s); break;
-    case 32: launch_csr_vl<32, TAG>(o, s); break;
-    default: launch_csr_vl<64, TAG>(o, s); break;
-  }
+  const DCsr& M = *o.M;
+  const int64_t r0 = o.r1 >= 0 ? o.r0 : 0, r1 = o.r1 >= 0 ? o.r1 : M.n;   // row range (multi-GPU), else all rows
+  if (r1 <= r0) return;
+  with_lanes(M.lanes, [&](auto vl) {
+    constexpr int VL = decltype(vl)::value;
+    with_epi<EPI_JACOBI, EPI_Y, EPI_YADD, EPI_RESID>(o.epi, [&](auto epi) {
+      csr_kernel<VL, decltype(epi)::value, TAG><<<nblocks((r1 - r0) * (int64_t)VL), 256, 0, s>>>(
+          r0, r1, M.ptr, M.col, M.val, o.x, o.y, o.b, o.w, o.out);
+    });
+  });
 }
+
+// the block families' epilogues: anything else is the fused block Jacobi
+// sweep.  EPI_KPOST exists for !XFM && !SYM only (K is never symmetric and e
+// is node-major), and so does the lane-group kernel's EPI_YBD (restrictions
+// only: node-interleaved, never symmetric); elsewhere such an op launches
+// nothing.  The half and row-dictionary layouts hold A, never the K operator.
+template <class F>
+void with_block_epi(int epi, F&& f) { with_epi<EPI_BJAC, EPI_Y, EPI_YADD, EPI_RESID, EPI_KPOST>(epi, f); }
+constexpr bool plain_only(int epi) { return epi == EPI_YBD || epi == EPI_KPOST; }
 
 // rows [o.r0, o.r1) when o.r1 >= 0 (the distributed K's overlap split: r0 a
 // multiple of 256, r1 too or = nr, so each workgroup's rows lie in the range)
-template <int VL, bool XFM, bool SYM, int TAG, class VT = double>
-void launch_bsr_x(const Op& o, hipStream_t s) {
+template <int TAG, class VT>
+void launch_bsr_vl(const Op& o, hipStream_t s) {
   const DBsr& M = *o.Mb;
   const bool rng = o.r1 >= 0;
   const int64_t r0 = rng ? o.r0 : 0, r1 = rng ? o.r1 : M.nr;
   if (r1 <= r0) return;
-  const int64_t b0 = r0 * VL / 256;
-  const unsigned g = (unsigned)(nblocks(r1 * (int64_t)VL) - b0);
-#define BSR_ARGS r1, M.ptr, M.col, reinterpret_cast<const VT*>(M.val), o.x, o.xs, o.y, o.b, o.bs, o.W, o.out, o.os, remap_of(o), \
-    (!rng && M.rsched && M.rsched_vl == VL && (int64_t)g == M.nrsched) ? M.rsched : nullptr, b0
-  switch (o.epi) {
-    case EPI_Y: bsr2_kernel<VL, EPI_Y, XFM, SYM, TAG, false, VT><<<g, 256, 0, s>>>(BSR_ARGS); break;
-    case EPI_YBD:   // restrictions only: node-interleaved, never symmetric
-      if constexpr (!XFM && !SYM) bsr2_kernel<VL, EPI_YBD, false, false, TAG, false, VT><<<g, 256, 0, s>>>(BSR_ARGS);
-      break;
-    case EPI_YADD: bsr2_kernel<VL, EPI_YADD, XFM, SYM, TAG, false, VT><<<g, 256, 0, s>>>(BSR_ARGS); break;
-    case EPI_RESID: bsr2_kernel<VL, EPI_RESID, XFM, SYM, TAG, false, VT><<<g, 256, 0, s>>>(BSR_ARGS); break;
-    case EPI_KPOST:   // K is never symmetric and e is node-major
-      if constexpr (!XFM && !SYM) bsr2_kernel<VL, EPI_KPOST, false, false, TAG, false, VT><<<g, 256, 0, s>>>(BSR_ARGS);
-      break;
-    default: bsr2_kernel<VL, EPI_BJAC, XFM, SYM, TAG, false, VT><<<g, 256, 0, s>>>(BSR_ARGS); break;
-  }
-#undef BSR_ARGS
+  with_lanes(M.lanes, [&](auto vl) {
+    constexpr int VL = decltype(vl)::value;
+    const int64_t b0 = r0 * VL / 256;
+    const unsigned g = (unsigned)(nblocks(r1 * (int64_t)VL) - b0);
+    with_bools([&](auto xfm, auto sym) {
+      constexpr bool XFM = decltype(xfm)::value, SYM = decltype(sym)::value;
+      with_epi<EPI_BJAC, EPI_Y, EPI_YBD, EPI_YADD, EPI_RESID, EPI_KPOST>(o.epi, [&](auto epi) {
+        constexpr int E = decltype(epi)::value;
+        if constexpr (!plain_only(E) || (!XFM && !SYM))
+          bsr2_kernel<VL, E, XFM, SYM, TAG, false, VT><<<g, 256, 0, s>>>(
+              r1, M.ptr, M.col, reinterpret_cast<const VT*>(M.val), o.x, o.xs, o.y, o.b, o.bs, o.W, o.out, o.os,
+              remap_of(o), (!rng && M.rsched && M.rsched_vl == VL && (int64_t)g == M.nrsched) ? M.rsched : nullptr,
+              b0);
+      });
+    }, o.xfm, M.sym);
+  });
 }
 
 template <bool XFM, bool SYM, int U, bool NT, int TAG, class VT = double>
@@ -5954,19 +5976,13 @@ void launch_sell_u(const Op& o, hipStream_t s) {
   const DBsr& M = *o.Mb;
   const unsigned g = nblocks(M.nr);
   if (g == 0) return;
-#define SELL_ARGS M.nr, M.soff, M.meta, M.col, reinterpret_cast<const VT*>(M.val), M.nbs, o.x, o.xs, o.y, o.b, o.bs, o.W, o.out, o.os, \
-    0, \
-    ((int64_t)g == M.nsched ? M.sched : nullptr), M.lsort ? 1 : 0
-  switch (o.epi) {
-    case EPI_Y: sell2_kernel<EPI_Y, XFM, SYM, U, NT, TAG, VT><<<g, 256, 0, s>>>(SELL_ARGS); break;
-    case EPI_YADD: sell2_kernel<EPI_YADD, XFM, SYM, U, NT, TAG, VT><<<g, 256, 0, s>>>(SELL_ARGS); break;
-    case EPI_RESID: sell2_kernel<EPI_RESID, XFM, SYM, U, NT, TAG, VT><<<g, 256, 0, s>>>(SELL_ARGS); break;
-    case EPI_KPOST:
-      if constexpr (!XFM && !SYM) sell2_kernel<EPI_KPOST, false, false, U, NT, TAG, VT><<<g, 256, 0, s>>>(SELL_ARGS);
-      break;
-    default: sell2_kernel<EPI_BJAC, XFM, SYM, U, NT, TAG, VT><<<g, 256, 0, s>>>(SELL_ARGS); break;
-  }
-#undef SELL_ARGS
+  with_block_epi(o.epi, [&](auto epi) {
+    constexpr int E = decltype(epi)::value;
+    if constexpr (!plain_only(E) || (!XFM && !SYM))
+      sell2_kernel<E, XFM, SYM, U, NT, TAG, VT><<<g, 256, 0, s>>>(
+          M.nr, M.soff, M.meta, M.col, reinterpret_cast<const VT*>(M.val), M.nbs, o.x, o.xs, o.y, o.b, o.bs, o.W,
+          o.out, o.os, 0, ((int64_t)g == M.nsched ? M.sched : nullptr), M.lsort ? 1 : 0);
+  });
 }
 
 // rows [o.r0, o.r1) when o.r1 >= 0: the bounds are multiples of 256 (or
@@ -5980,23 +5996,18 @@ void launch_msell(const Op& o, hipStream_t s) {
   if (r1 <= r0) return;
   const int64_t b0 = r0 / rows;
   const unsigned g = (unsigned)((r1 + rows - 1) / rows - b0);
-#define MSELL_ARGS r1, M.soff, M.meta, M.col, reinterpret_cast<const VT*>(M.val), M.nbs, o.x, o.xs, o.y, o.b, o.bs, o.W, o.out, o.os, \
-    (TAG == 0 && M.kvar == 3) ? 1 : 0, M.lsort ? 1 : 0, b0, M.col16, M.cbase
-  switch (o.epi) {
-    case EPI_Y: msell_kernel<LPR, U, EPI_Y, XFM, SYM, SPL, TAG, PROBE, false, VT><<<g, 256, 0, s>>>(MSELL_ARGS); break;
-    case EPI_YADD: msell_kernel<LPR, U, EPI_YADD, XFM, SYM, SPL, TAG, PROBE, false, VT><<<g, 256, 0, s>>>(MSELL_ARGS); break;
-    case EPI_RESID: msell_kernel<LPR, U, EPI_RESID, XFM, SYM, SPL, TAG, PROBE, false, VT><<<g, 256, 0, s>>>(MSELL_ARGS); break;
-    case EPI_KPOST:
-      if constexpr (!XFM && !SYM) {
-        if (TAG == 0 && PROBE == 0 && M.col16)   // level-0 K with 16-bit columns (compress_sell_cols)
-          msell_kernel<LPR, U, EPI_KPOST, false, false, SPL, TAG, 0, true, VT><<<g, 256, 0, s>>>(MSELL_ARGS);
-        else
-          msell_kernel<LPR, U, EPI_KPOST, false, false, SPL, TAG, PROBE, false, VT><<<g, 256, 0, s>>>(MSELL_ARGS);
-      }
-      break;
-    default: msell_kernel<LPR, U, EPI_BJAC, XFM, SYM, SPL, TAG, PROBE, false, VT><<<g, 256, 0, s>>>(MSELL_ARGS); break;
-  }
-#undef MSELL_ARGS
+  with_block_epi(o.epi, [&](auto epi) {
+    constexpr int E = decltype(epi)::value;
+    auto go = [&](auto col16) {
+      constexpr bool C16 = decltype(col16)::value;
+      msell_kernel<LPR, U, E, XFM, SYM, SPL, TAG, C16 ? 0 : PROBE, C16, VT><<<g, 256, 0, s>>>(
+          r1, M.soff, M.meta, M.col, reinterpret_cast<const VT*>(M.val), M.nbs, o.x, o.xs, o.y, o.b, o.bs, o.W,
+          o.out, o.os, (TAG == 0 && M.kvar == 3) ? 1 : 0, M.lsort ? 1 : 0, b0, M.col16, M.cbase);
+    };
+    if constexpr (E != EPI_KPOST) go(std::false_type{});
+    // level-0 K with 16-bit columns (compress_sell_cols)
+    else if constexpr (!XFM && !SYM) with_bools(go, TAG == 0 && PROBE == 0 && M.col16 != nullptr);
+  });
 }
 
 // the level-0 K kernel (DBsr::kvar, the diagnosis build's MAMG_K_VARIANT for
@@ -6044,36 +6055,15 @@ void launch_sell_x(const Op& o, hipStream_t s) {
   }
   if constexpr (!XFM) {
     if (o.Mb->lpr > 1 && !o.Mb->split) {
-      switch (o.Mb->lpr) {
-        case 2: launch_msell<2, 5, false, SYM, false, TAG, 0, VT>(o, s); return;
-        case 4: launch_msell<4, 5, false, SYM, false, TAG, 0, VT>(o, s); return;
-        case 8: launch_msell<8, 5, false, SYM, false, TAG, 0, VT>(o, s); return;
-        default: launch_msell<16, 5, false, SYM, false, TAG, 0, VT>(o, s); return;
-      }
+      with_lpr(o.Mb->lpr, [&](auto lpr) { launch_msell<decltype(lpr)::value, 5, false, SYM, false, TAG, 0, VT>(o, s); });
+      return;
     }
   }
-  if (o.Mb->split && TAG == 0) launch_sell_u<XFM, SYM, post_u, true, TAG, VT>(o, s);
-  else if (o.Mb->split) launch_sell_u<XFM, SYM, sell_u, true, TAG, VT>(o, s);
-  else if (TAG == 0 && o.epi == EPI_KPOST) launch_sell_u<XFM, SYM, post_u, false, TAG, VT>(o, s);
-  else launch_sell_u<XFM, SYM, sell_u, false, TAG, VT>(o, s);
-}
-
-template <int TAG, class VT = double>
-void launch_sell(const Op& o, hipStream_t s) {
-  if (o.Mb->sym) {
-    if (o.xfm) launch_sell_x<true, true, TAG, VT>(o, s); else launch_sell_x<false, true, TAG, VT>(o, s);
-  } else {
-    if (o.xfm) launch_sell_x<true, false, TAG, VT>(o, s); else launch_sell_x<false, false, TAG, VT>(o, s);
-  }
-}
-
-template <int VL, int TAG, class VT = double>
-void launch_bsr_vl(const Op& o, hipStream_t s) {
-  if (o.Mb->sym) {
-    if (o.xfm) launch_bsr_x<VL, true, true, TAG, VT>(o, s); else launch_bsr_x<VL, false, true, TAG, VT>(o, s);
-  } else {
-    if (o.xfm) launch_bsr_x<VL, true, false, TAG, VT>(o, s); else launch_bsr_x<VL, false, false, TAG, VT>(o, s);
-  }
+  // a split operator streams non-temporally; chunks of post_u for the tagged-0 K side
+  const bool nt = o.Mb->split != 0;
+  with_bools([&](auto post, auto ntl) {
+    launch_sell_u<XFM, SYM, decltype(post)::value ? post_u : sell_u, decltype(ntl)::value, TAG, VT>(o, s);
+  }, TAG == 0 && (nt || o.epi == EPI_KPOST), nt);
 }
 
 template <int VL, int TAG>
@@ -6094,50 +6084,29 @@ void launch_post_tag(const Op& o, hipStream_t s) {
                                                            o.x, o.y, o.b, o.W, o.out, o.os);
     return;
   }
-  switch (o.Mb->lanes) {
-    case 2: launch_post_vl<2, TAG>(o, s); break;
-    case 4: launch_post_vl<4, TAG>(o, s); break;
-    case 8: launch_post_vl<8, TAG>(o, s); break;
-    case 16: launch_post_vl<16, TAG>(o, s); break;
-    case 32: launch_post_vl<32, TAG>(o, s); break;
-    default: launch_post_vl<64, TAG>(o, s); break;
-  }
+  with_lanes(o.Mb->lanes, [&](auto vl) { launch_post_vl<decltype(vl)::value, TAG>(o, s); });
 }
 
-template <bool XFM, int U, bool GH, int TAG, class VT = double>
-void launch_half_u(const Op& o, hipStream_t s) {
+// half-symmetric A, four entries in flight per lane
+template <int TAG, class VT = double>
+void launch_half(const Op& o, hipStream_t s) {
   const DBsr& M = *o.Mb;
   const int64_t r0 = o.r1 < 0 ? 0 : o.r0, r1 = o.r1 < 0 ? M.nr : o.r1;
   const unsigned g = nblocks(r1 - r0);
   if (r1 <= r0) return;
-#define HALF_ARGS r0, r1, M.meta, M.col, reinterpret_cast<const VT*>(M.val), M.nbs, M.hwu, M.lptr, M.hwl, M.gsoff, M.gcol, \
-    reinterpret_cast<const VT*>(M.gval), M.ngs, \
-    o.x, o.xs, o.y, o.b, o.bs, o.W, o.out, o.os, 1, \
-    (r0 == 0 && r1 == M.nr && (int64_t)g == M.nsched) ? M.sched \
-    : (r0 == M.sr0 && r1 == M.sr1 && (int64_t)g == M.nsched_r) ? M.sched_r : nullptr
-  switch (o.epi) {
-    case EPI_Y: hsell2_kernel<EPI_Y, XFM, U, GH, TAG, VT><<<g, 256, 0, s>>>(HALF_ARGS); break;
-    case EPI_YADD: hsell2_kernel<EPI_YADD, XFM, U, GH, TAG, VT><<<g, 256, 0, s>>>(HALF_ARGS); break;
-    case EPI_RESID: hsell2_kernel<EPI_RESID, XFM, U, GH, TAG, VT><<<g, 256, 0, s>>>(HALF_ARGS); break;
-    case EPI_KPOST: break;   // A is never the K operator
-    default: hsell2_kernel<EPI_BJAC, XFM, U, GH, TAG, VT><<<g, 256, 0, s>>>(HALF_ARGS); break;
-  }
-#undef HALF_ARGS
-}
-
-template <bool XFM, bool GH, int TAG, class VT = double>
-void launch_half_x(const Op& o, hipStream_t s) {
-  launch_half_u<XFM, 4, GH, TAG, VT>(o, s);
-}
-
-template <int TAG, class VT = double>
-void launch_half(const Op& o, hipStream_t s) {
-  const bool gh = o.Mb->ngs > 0;   // a rank-local A's ghost part (fp32 storage: gval narrowed with val)
-  if (o.xfm) {
-    if (gh) launch_half_x<true, true, TAG, VT>(o, s); else launch_half_x<true, false, TAG, VT>(o, s);
-  } else {
-    if (gh) launch_half_x<false, true, TAG, VT>(o, s); else launch_half_x<false, false, TAG, VT>(o, s);
-  }
+  // gh: a rank-local A's ghost part (fp32 storage: gval narrowed with val)
+  with_bools([&](auto xfm, auto gh) {
+    with_block_epi(o.epi, [&](auto epi) {
+      constexpr int E = decltype(epi)::value;
+      if constexpr (E != EPI_KPOST)
+        hsell2_kernel<E, decltype(xfm)::value, 4, decltype(gh)::value, TAG, VT><<<g, 256, 0, s>>>(
+            r0, r1, M.meta, M.col, reinterpret_cast<const VT*>(M.val), M.nbs, M.hwu, M.lptr, M.hwl, M.gsoff, M.gcol,
+            reinterpret_cast<const VT*>(M.gval), M.ngs, o.x, o.xs, o.y, o.b, o.bs, o.W, o.out, o.os, 1,
+            (r0 == 0 && r1 == M.nr && (int64_t)g == M.nsched)            ? M.sched
+            : (r0 == M.sr0 && r1 == M.sr1 && (int64_t)g == M.nsched_r) ? M.sched_r
+                                                                       : nullptr);
+    });
+  }, o.xfm, M.ngs > 0);
 }
 
 // row-pattern dictionary (rowdict2_kernel); the band schedule as for the half
@@ -6148,102 +6117,65 @@ void launch_half(const Op& o, hipStream_t s) {
 #endif
 constexpr int ROWDICT_U = MAMG_ROWDICT_U;
 
-template <bool XFM, bool SYM, int TAG, class VT = double>
-void launch_rowdict_x(const Op& o, hipStream_t s) {
+template <int TAG, class VT = double>
+void launch_rowdict(const Op& o, hipStream_t s) {
   const DBsr& M = *o.Mb;
   const int64_t r0 = o.r1 < 0 ? 0 : o.r0, r1 = o.r1 < 0 ? M.nr : o.r1;
   const unsigned g = nblocks(r1 - r0);
   if (r1 <= r0) return;
-  const size_t lds = MAMG_ROWDICT_LDS ? (size_t)M.nbs * (4 + (SYM ? 3 : 4) * sizeof(VT)) : 0;
-#define RD_ARGS r0, r1, M.rcode, M.rlen, M.rdelta, reinterpret_cast<const VT*>(M.val), M.nbs, M.rw, \
-    o.x, o.xs, o.y, o.b, o.bs, o.W, o.out, o.os, 1, \
-    (r0 == 0 && r1 == M.nr && (int64_t)g == M.nsched) ? M.sched : nullptr
-  switch (o.epi) {
-    case EPI_Y: rowdict2_kernel<EPI_Y, XFM, SYM, ROWDICT_U, TAG, VT><<<g, 256, lds, s>>>(RD_ARGS); break;
-    case EPI_YADD: rowdict2_kernel<EPI_YADD, XFM, SYM, ROWDICT_U, TAG, VT><<<g, 256, lds, s>>>(RD_ARGS); break;
-    case EPI_RESID: rowdict2_kernel<EPI_RESID, XFM, SYM, ROWDICT_U, TAG, VT><<<g, 256, lds, s>>>(RD_ARGS); break;
-    case EPI_KPOST: break;   // A is never the K operator
-    default: rowdict2_kernel<EPI_BJAC, XFM, SYM, ROWDICT_U, TAG, VT><<<g, 256, lds, s>>>(RD_ARGS); break;
-  }
-#undef RD_ARGS
-}
-
-template <int TAG, class VT = double>
-void launch_rowdict(const Op& o, hipStream_t s) {
-  if (o.Mb->sym) {
-    if (o.xfm) launch_rowdict_x<true, true, TAG, VT>(o, s); else launch_rowdict_x<false, true, TAG, VT>(o, s);
-  } else {
-    if (o.xfm) launch_rowdict_x<true, false, TAG, VT>(o, s); else launch_rowdict_x<false, false, TAG, VT>(o, s);
-  }
-}
-
-template <int TAG, class VT = double>
-void launch_bsr_st(const Op& o, hipStream_t s) {
-  if (o.Mb->rowdict) { launch_rowdict<TAG, VT>(o, s); return; }
-  if (o.Mb->half) { launch_half<TAG, VT>(o, s); return; }
-  if (o.Mb->sell) { launch_sell<TAG, VT>(o, s); return; }
-  switch (o.Mb->lanes) {
-    case 2: launch_bsr_vl<2, TAG, VT>(o, s); break;
-    case 4: launch_bsr_vl<4, TAG, VT>(o, s); break;
-    case 8: launch_bsr_vl<8, TAG, VT>(o, s); break;
-    case 16: launch_bsr_vl<16, TAG, VT>(o, s); break;
-    case 32: launch_bsr_vl<32, TAG, VT>(o, s); break;
-    default: launch_bsr_vl<64, TAG, VT>(o, s); break;
-  }
+  with_bools([&](auto xfm, auto sym) {
+    constexpr bool SYM = decltype(sym)::value;
+    const size_t lds = MAMG_ROWDICT_LDS ? (size_t)M.nbs * (4 + (SYM ? 3 : 4) * sizeof(VT)) : 0;
+    with_block_epi(o.epi, [&](auto epi) {
+      constexpr int E = decltype(epi)::value;
+      if constexpr (E != EPI_KPOST)
+        rowdict2_kernel<E, decltype(xfm)::value, SYM, ROWDICT_U, TAG, VT><<<g, 256, lds, s>>>(
+            r0, r1, M.rcode, M.rlen, M.rdelta, reinterpret_cast<const VT*>(M.val), M.nbs, M.rw, o.x, o.xs, o.y, o.b,
+            o.bs, o.W, o.out, o.os, 1, (r0 == 0 && r1 == M.nr && (int64_t)g == M.nsched) ? M.sched : nullptr);
+    });
+  }, o.xfm, M.sym);
 }
 
 // DBsr::f32: the operator's values are stored fp32 (dev_set_cycle_storage)
 template <int TAG>
 void launch_bsr_tag(const Op& o, hipStream_t s) {
-  if (o.Mb->f32) launch_bsr_st<TAG, float>(o, s);
-  else launch_bsr_st<TAG, double>(o, s);
-}
-
-template <int VL>
-void launch_gs_vl(const Op& o, hipStream_t s) {
-  const DBsr& M = *o.Mb;
-  const unsigned g = nblocks(o.n * (int64_t)VL);
-  if (M.sym)
-    gs2_kernel<VL, true><<<g, 256, 0, s>>>(o.r0, o.r1, o.perm, M.ptr, M.col, M.val, M.nb, o.W, o.out, o.b, o.bs);
-  else
-    gs2_kernel<VL, false><<<g, 256, 0, s>>>(o.r0, o.r1, o.perm, M.ptr, M.col, M.val, M.nb, o.W, o.out, o.b, o.bs);
+  with_value_type(o.Mb->f32, [&](auto vt) {
+    using VT = typename decltype(vt)::type;
+    if (o.Mb->rowdict) launch_rowdict<TAG, VT>(o, s);
+    else if (o.Mb->half) launch_half<TAG, VT>(o, s);
+    else if (o.Mb->sell)
+      with_bools([&](auto xfm, auto sym) { launch_sell_x<decltype(xfm)::value, decltype(sym)::value, TAG, VT>(o, s); },
+                 o.xfm, o.Mb->sym);
+    else launch_bsr_vl<TAG, VT>(o, s);
+  });
 }
 
 void launch_gs(const Op& o, hipStream_t s) {
-  switch (o.Mb->lanes) {
-    case 2: launch_gs_vl<2>(o, s); break;
-    case 4: launch_gs_vl<4>(o, s); break;
-    case 8: launch_gs_vl<8>(o, s); break;
-    case 16: launch_gs_vl<16>(o, s); break;
-    case 32: launch_gs_vl<32>(o, s); break;
-    default: launch_gs_vl<64>(o, s); break;
-  }
-}
-
-template <int VL>
-void launch_cgs_vl(const Op& o, hipStream_t s) {
-  const DCsr& M = *o.M;
-  if (o.kind == OP_CGS) {
-    csr_gs_kernel<VL><<<nblocks(o.n * (int64_t)VL), 256, 0, s>>>(o.r0, o.r1, o.perm, M.ptr, M.col, M.val, o.w, o.out,
-                                                                o.b);
-    return;
-  }
-  const DLevel& L = *o.lev;
-  auto dir = [](int v) { return v == 1 ? 1 : v == 2 ? -1 : 0; };
-  csr_gs_small_kernel<VL><<<1, CSR_GS_SMALL_THREADS, (size_t)M.n * sizeof(double), s>>>(
-      M.n, (int)L.gcs.size() - 1, L.gcs_d, o.perm, M.ptr, M.col, M.val, o.w, o.out, o.b, o.epi & 1, (int)o.n,
-      dir((o.epi >> 1) & 3), dir((o.epi >> 3) & 3));
+  const DBsr& M = *o.Mb;
+  with_lanes(M.lanes, [&](auto vl) {
+    constexpr int VL = decltype(vl)::value;
+    with_bools([&](auto sym) {
+      gs2_kernel<VL, decltype(sym)::value><<<nblocks(o.n * (int64_t)VL), 256, 0, s>>>(
+          o.r0, o.r1, o.perm, M.ptr, M.col, M.val, M.nb, o.W, o.out, o.b, o.bs);
+    }, M.sym);
+  });
 }
 
 void launch_cgs(const Op& o, hipStream_t s) {
-  switch (o.M->lanes) {
-    case 2: launch_cgs_vl<2>(o, s); break;
-    case 4: launch_cgs_vl<4>(o, s); break;
-    case 8: launch_cgs_vl<8>(o, s); break;
-    case 16: launch_cgs_vl<16>(o, s); break;
-    case 32: launch_cgs_vl<32>(o, s); break;
-    default: launch_cgs_vl<64>(o, s); break;
-  }
+  const DCsr& M = *o.M;
+  with_lanes(M.lanes, [&](auto vl) {
+    constexpr int VL = decltype(vl)::value;
+    if (o.kind == OP_CGS) {
+      csr_gs_kernel<VL><<<nblocks(o.n * (int64_t)VL), 256, 0, s>>>(o.r0, o.r1, o.perm, M.ptr, M.col, M.val, o.w,
+                                                                  o.out, o.b);
+      return;
+    }
+    const DLevel& L = *o.lev;
+    auto dir = [](int v) { return v == 1 ? 1 : v == 2 ? -1 : 0; };
+    csr_gs_small_kernel<VL><<<1, CSR_GS_SMALL_THREADS, (size_t)M.n * sizeof(double), s>>>(
+        M.n, (int)L.gcs.size() - 1, L.gcs_d, o.perm, M.ptr, M.col, M.val, o.w, o.out, o.b, o.epi & 1, (int)o.n,
+        dir((o.epi >> 1) & 3), dir((o.epi >> 3) & 3));
+  });
 }
 
 }  // namespace
@@ -6349,42 +6281,98 @@ void launch(const Op& o, hipStream_t s) {
   }
 }
 
+int TimedRun::run(size_t nops, const std::function<int(size_t)>& cls, const std::function<int(size_t)>& op, int reps,
+                  int mode, hipStream_t s, const std::function<int()>& queued, double* ms, double* kernel_ms,
+                  std::string* err) {
+  int rc;
+  inst.clear();
+  for (size_t k = 0; k < nops; ++k)
+    if (mode == 1 || cls(k) == C_L0_RESID || cls(k) == C_L0_SMOOTH) inst.push_back((int)k);
+  if ((rc = create(2 * inst.size() * (size_t)reps + 2, err))) return rc;
+  HIPCHK(hipEventRecord(ev[0], s));
+  size_t q = 2;
+  for (int rp = 0; rp < reps; ++rp) {
+    size_t ii = 0;
+    for (size_t k = 0; k < nops; ++k) {
+      const bool timed = ii < inst.size() && inst[ii] == (int)k;
+      if (timed) HIPCHK(hipEventRecord(ev[q], s));
+      if ((rc = op(k))) return rc;
+      if (timed) { HIPCHK(hipEventRecord(ev[q + 1], s)); q += 2; ++ii; }
+    }
+  }
+  HIPCHK(hipEventRecord(ev[1], s));
+  if (queued && (rc = queued())) return rc;
+  HIPCHK(hipEventSynchronize(ev[1]));
+  HIPCHK(hipGetLastError());
+  float tot = 0.f;
+  HIPCHK(hipEventElapsedTime(&tot, ev[0], ev[1]));
+  *ms = tot / reps;
+  if (kernel_ms) {
+    for (int c = 0; c < 16; ++c) kernel_ms[c] = 0.0;
+    for (int rp = 0; rp < reps; ++rp)
+      for (size_t ii = 0; ii < inst.size(); ++ii) {
+        float t = 0.f;
+        if ((rc = op_ms(rp, ii, &t, err))) return rc;
+        kernel_ms[cls((size_t)inst[ii])] += t / reps;
+      }
+  }
+  return MAMG_OK;
+}
+
+int IterGraph::alloc(size_t hist_doubles, std::string* err) {
+  if (raw_malloc((void**)&hist, hist_doubles * sizeof(double), "long") != hipSuccess) {
+    (void)hipGetLastError();
+    hist = nullptr;
+    *err = "PCG history allocation failed";
+    return MAMG_ERR_HIP;
+  }
+  for (hipEvent_t& e : ev) {
+    const hipError_t rc = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+    if (rc == hipSuccess) continue;
+    e = nullptr;
+    release();
+    *err = std::string("PCG events: ") + hipGetErrorString(rc);
+    return MAMG_ERR_HIP;
+  }
+  return MAMG_OK;
+}
+
+int pcg_finish(int status, int it, const PcgHist& d, double* residuals, double* rnorms, double* alphas,
+               double* betas, int* niters, std::string* err) {
+  if (status == PCG_NOT_POS) {
+    *niters = 0;
+    residuals[0] = 0.0;
+    *err = "Matrix is not positive";
+    return MAMG_ERR_BREAKDOWN;
+  }
+  HIPCHK(hipMemcpy(residuals, d.res, (it + 1) * sizeof(double), hipMemcpyDeviceToHost));
+  if (d.rn && rnorms) HIPCHK(hipMemcpy(rnorms, d.rn, (it + 1) * sizeof(double), hipMemcpyDeviceToHost));
+  if (it > 0) {
+    HIPCHK(hipMemcpy(alphas, d.al, it * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(betas, d.be, it * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  *niters = it;
+  if (status == PCG_DQ_ZERO) {   // the host loop's breakdown flag (krylov.py): same status here
+    *err = "ConjGrad stopped: <d,Ad> = 0";
+    return MAMG_ERR_BREAKDOWN;
+  }
+  if (status == PCG_RZ_NEG) {
+    *err = "ConjGrad breakdown (<r,Br> < 0)";
+    return MAMG_ERR_BREAKDOWN;
+  }
+  return MAMG_OK;
+}
+
 namespace {
 
-// handle ordering (DeviceHandle::last)
-int order_begin(DeviceHandle* h, hipStream_t s, std::string* err) {
-  if (!h->last) HIPCHK(hipEventCreateWithFlags(&h->last, hipEventDisableTiming));
-  HIPCHK(hipStreamWaitEvent(s, h->last, 0));
-  return MAMG_OK;
-}
-int order_end(DeviceHandle* h, hipStream_t s, std::string* err) {
-  if (!h->last) HIPCHK(hipEventCreateWithFlags(&h->last, hipEventDisableTiming));   // the upload's own mark
-  HIPCHK(hipEventRecord(h->last, s));
-  return MAMG_OK;
-}
-
+// the apply's graph for (r, z), from the handle's cache or captured now
 int get_graph(DeviceHandle* h, const double* r, double* z, hipGraphExec_t* exec, std::string* err) {
-  for (auto& g : h->graphs)
-    if (g.r == r && g.z == z) { *exec = g.exec; return MAMG_OK; }
-  if (h->graphs.size() >= 16) {   // evict oldest, after every launch on the handle finished
-    if (h->last) HIPCHK(hipEventSynchronize(h->last));
-    auto& g = h->graphs.front();
-    (void)hipGraphExecDestroy(g.exec);
-    (void)hipGraphDestroy(g.graph);
-    h->graphs.erase(h->graphs.begin());
-  }
-  std::vector<Op> ops;
-  apply_ops(h, r, z, &ops);
-  Graph g;
-  g.r = r; g.z = z;
-  std::lock_guard<std::recursive_mutex> capture_lock(capture_mutex());
-  HIPCHK(hipStreamBeginCapture(h->cap, hipStreamCaptureModeThreadLocal));
-  for (const Op& o : ops) launch(o, h->cap);
-  HIPCHK(hipStreamEndCapture(h->cap, &g.graph));
-  HIPCHK(graph_instantiate(&g.exec, g.graph));
-  h->graphs.push_back(g);
-  *exec = g.exec;
-  return MAMG_OK;
+  return h->graphs.get(r, z, h->last, [&](CapturedGraph* g) {
+    std::vector<Op> ops;
+    apply_ops(h, r, z, &ops);
+    return capture_graph(&h->cap, [&]() { for (const Op& o : ops) launch(o, h->cap); return (int)MAMG_OK; }, "apply",
+                         g, err);
+  }, exec, err);
 }
 
 // BSR2 layout usable: 2 fields, every level's smoother node-block diagonal
@@ -6811,8 +6799,8 @@ int dev_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, cons
   apply_k_layout_knob(h.get());
   set_tail_level(h.get());
   // every layout kernel and device-to-device copy (null stream) ordered
-  // before the handle's first use on any stream (order_begin waits on it)
-  if ((rc = order_end(h.get(), nullptr, err))) return rc;
+  // before the handle's first use on any stream (HandleOrder::wait waits on it)
+  if ((rc = h->mark(nullptr, err))) return rc;
   HIPCHK(hipEventSynchronize(h->last));
   debug_sums(h.get(), "upload", false);
   h->layout_ms[LT_FINISH] =
@@ -6994,7 +6982,7 @@ int dev_from_ghier(GHier* G, const DevMat& A0, const mamg_params& p, DeviceHandl
   const auto t2 = std::chrono::steady_clock::now();
   apply_k_layout_knob(h.get());
   set_tail_level(h.get());
-  if ((rc = order_end(h.get(), nullptr, err))) return rc;   // as in dev_upload
+  if ((rc = h->mark(nullptr, err))) return rc;   // as in dev_upload
   HIPCHK(hipEventSynchronize(h->last));
   debug_sums(h.get(), "upload", false);
   const auto t3 = std::chrono::steady_clock::now();
@@ -7218,13 +7206,8 @@ int dev_set_cycle_storage(DeviceHandle* h, int storage, std::string* err) {
   if (h->cap) HIPCHK(hipStreamSynchronize(h->cap));
   // the cached graphs hold the fp64 op list: dropped, the next apply captures anew
   auto drop_cached = [&]() {
-    for (auto& g : h->graphs) {
-      if (g.exec) (void)hipGraphExecDestroy(g.exec);
-      if (g.graph) (void)hipGraphDestroy(g.graph);
-    }
     h->graphs.clear();
-    for (auto& g : h->pcgs) g.release();
-    h->pcgs.clear();
+    release_all(&h->pcgs);
   };
   // the fp64 originals go back except A_0's (the Krylov operator)
   int rc = narrow_values(jobs, &h->allocs, drop_cached, [&](void* old) { release_owned(h, old); }, err);
@@ -7251,9 +7234,9 @@ int dev_apply(DeviceHandle* h, const double* d_r, double* d_z, void* stream, std
   hipGraphExec_t exec;
   int rc = get_graph(h, d_r, d_z, &exec, err);
   if (rc) return rc;
-  if ((rc = order_begin(h, (hipStream_t)stream, err))) return rc;
+  if ((rc = h->wait((hipStream_t)stream, err))) return rc;
   HIPCHK(hipGraphLaunch(exec, (hipStream_t)stream));
-  return order_end(h, (hipStream_t)stream, err);
+  return h->mark((hipStream_t)stream, err);
 }
 
 int dev_apply_host(DeviceHandle* h, const double* r, double* z, std::string* err) {
@@ -7262,22 +7245,22 @@ int dev_apply_host(DeviceHandle* h, const double* r, double* z, std::string* err
   hipGraphExec_t exec;
   int rc = get_graph(h, h->hr, h->hz, &exec, err);
   if (rc) return rc;
-  if ((rc = order_begin(h, h->cap, err))) return rc;   // after queued device-pointer applies
+  if ((rc = h->wait(h->cap, err))) return rc;   // after queued device-pointer applies
   HIPCHK(hipMemcpyAsync(h->hr, r, n * sizeof(double), hipMemcpyHostToDevice, h->cap));
   HIPCHK(hipGraphLaunch(exec, h->cap));
   HIPCHK(hipMemcpyAsync(z, h->hz, n * sizeof(double), hipMemcpyDeviceToHost, h->cap));
-  if ((rc = order_end(h, h->cap, err))) return rc;
+  if ((rc = h->mark(h->cap, err))) return rc;
   HIPCHK(hipStreamSynchronize(h->cap));
   return MAMG_OK;
 }
 
 int dev_spmv(DeviceHandle* h, const double* d_x, double* d_y, void* stream, std::string* err) {
   HIPCHK(hipSetDevice(h->device));
-  int rc = order_begin(h, (hipStream_t)stream, err);
+  int rc = h->wait((hipStream_t)stream, err);
   if (rc) return rc;
   launch(a0_op(h, EPI_Y, d_x, nullptr, d_y), (hipStream_t)stream);
   HIPCHK(hipGetLastError());
-  return order_end(h, (hipStream_t)stream, err);
+  return h->mark((hipStream_t)stream, err);
 }
 
 int dev_pcg(DeviceHandle* h, const double* d_b, double* d_x, double tol, int maxiter,
@@ -7305,7 +7288,7 @@ int dev_pcg(DeviceHandle* h, const double* d_b, double* d_x, double tol, int max
   PcgState* st = reinterpret_cast<PcgState*>(h->dres);
   PcgState* hst = reinterpret_cast<PcgState*>(h->hres);
   const unsigned g = nblocks(n);
-  if ((rc = order_begin(h, s, err))) return rc;
+  if ((rc = h->wait(s, err))) return rc;
   // the iteration graph for (x, maxiter), captured once and kept on the
   // handle (at most 4; the oldest evicted after the handle's work is done)
   PcgGraph* pg = nullptr;
@@ -7321,17 +7304,11 @@ int dev_pcg(DeviceHandle* h, const double* d_b, double* d_x, double tol, int max
     PcgGraph q;
     q.x = d_x;
     q.maxiter = maxiter;
-    if (raw_malloc((void**)&q.hist, (3 * (size_t)maxiter + 1) * sizeof(double), "long") != hipSuccess) {
-      (void)hipGetLastError();
-      *err = "PCG history allocation failed";
-      return MAMG_ERR_HIP;
-    }
+    if ((rc = q.alloc(3 * (size_t)maxiter + 1, err))) return rc;
     double *dres = q.hist, *dal = q.hist + maxiter + 1, *dbe = dal + maxiter;
     std::vector<Op> ops;
     apply_ops(h, h->cr, h->cz, &ops);
-    std::lock_guard<std::recursive_mutex> capture_lock(capture_mutex());
-    hipError_t e = hipStreamBeginCapture(h->cap, hipStreamCaptureModeThreadLocal);
-    if (e == hipSuccess) {
+    rc = capture_graph(&h->cap, [&]() {
       launch(a0_op(h, EPI_Y, h->cd, nullptr, h->cq), h->cap);           // q = A d
       dot_partial_kernel<<<DOT_BLOCKS, 256, 0, h->cap>>>(n, h->cd, h->cq, h->part);
       pcg_alpha_kernel<<<1, 256, 0, h->cap>>>(DOT_BLOCKS, h->part, st);
@@ -7340,15 +7317,11 @@ int dev_pcg(DeviceHandle* h, const double* d_b, double* d_x, double tol, int max
       dot_partial_kernel<<<DOT_BLOCKS, 256, 0, h->cap>>>(n, h->cr, h->cz, h->part);
       pcg_beta_kernel<<<1, 256, 0, h->cap>>>(DOT_BLOCKS, h->part, st, dres, dal, dbe);
       pcg_d_kernel<<<g, 256, 0, h->cap>>>(n, st, h->cz, h->cd, d_x);
-      e = hipStreamEndCapture(h->cap, &q.graph);
-    }
-    if (e == hipSuccess) e = graph_instantiate(&q.exec, q.graph);
-    for (hipEvent_t& x : q.ev)
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&x, hipEventDisableTiming);
-    if (e != hipSuccess) {
+      return (int)MAMG_OK;
+    }, "PCG iteration", &q, err);
+    if (rc) {
       q.release();
-      *err = std::string("PCG graph: ") + hipGetErrorString(e);
-      return MAMG_ERR_HIP;
+      return rc;
     }
     h->pcgs.push_back(q);
     pg = &h->pcgs.back();
@@ -7362,12 +7335,10 @@ int dev_pcg(DeviceHandle* h, const double* d_b, double* d_x, double tol, int max
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(&hst[0], st, sizeof(PcgState), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
+  const PcgHist hist{dres, nullptr, dal, dbe};
   if (hst[0].status == PCG_NOT_POS) {
-    *niters = 0;
-    residuals[0] = 0.0;
-    (void)order_end(h, s, err);
-    *err = "Matrix is not positive";
-    return MAMG_ERR_BREAKDOWN;
+    (void)h->mark(s, err);
+    return pcg_finish(PCG_NOT_POS, 0, hist, residuals, nullptr, alphas, betas, niters, err);
   }
   if (hst[0].active) {
     // iteration k's state lands in hst[k & 1]; iteration k + 1 is queued
@@ -7382,33 +7353,17 @@ int dev_pcg(DeviceHandle* h, const double* d_b, double* d_x, double tol, int max
     }
   }
   HIPCHK(hipMemcpyAsync(&hst[0], st, sizeof(PcgState), hipMemcpyDeviceToHost, s));
-  if ((rc = order_end(h, s, err))) return rc;
+  if ((rc = h->mark(s, err))) return rc;
   HIPCHK(hipStreamSynchronize(s));
   HIPCHK(hipGetLastError());
-  const PcgState fin = hst[0];
-  const int it = fin.it;
-  HIPCHK(hipMemcpy(residuals, dres, (it + 1) * sizeof(double), hipMemcpyDeviceToHost));
-  if (it > 0) {
-    HIPCHK(hipMemcpy(alphas, dal, it * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(betas, dbe, it * sizeof(double), hipMemcpyDeviceToHost));
-  }
-  *niters = it;
-  if (fin.status == PCG_DQ_ZERO) {   // the host loop's breakdown flag (krylov.py): same status here
-    *err = "ConjGrad stopped: <d,Ad> = 0";
-    return MAMG_ERR_BREAKDOWN;
-  }
-  if (fin.status == PCG_RZ_NEG) {
-    *err = "ConjGrad breakdown (<r,Br> < 0)";
-    return MAMG_ERR_BREAKDOWN;
-  }
-  return MAMG_OK;
+  return pcg_finish(hst[0].status, hst[0].it, hist, residuals, nullptr, alphas, betas, niters, err);
 }
 
 int dev_time_apply(DeviceHandle* h, const double* d_r, double* d_z, int reps, int mode, double* ms,
                    double* kernel_ms, double* class_bytes, void* stream, std::string* err) {
   HIPCHK(hipSetDevice(h->device));
   hipStream_t s = (hipStream_t)stream;
-  int rc = order_begin(h, s, err);
+  int rc = h->wait(s, err);
   if (rc) return rc;
   std::vector<Op> ops;
   apply_ops(h, d_r, d_z, &ops);
@@ -7417,55 +7372,23 @@ int dev_time_apply(DeviceHandle* h, const double* d_r, double* d_z, int reps, in
     for (const Op& o : ops) class_bytes[o.cls] += o.bytes;
   }
   if (reps <= 0) { *ms = 0.0; return MAMG_OK; }
-  // events: per rep, per instrumented op, one (start, end) pair
-  std::vector<int> inst;
-  for (size_t k = 0; k < ops.size(); ++k)
-    if (mode == 1 || ops[k].cls == C_L0_RESID || ops[k].cls == C_L0_SMOOTH) inst.push_back((int)k);
-  std::vector<hipEvent_t> ev(2 * inst.size() * (size_t)reps + 2);
-  for (auto& e : ev) HIPCHK(hipEventCreate(&e));
-  HIPCHK(hipEventRecord(ev[0], s));
-  size_t q = 2;
-  for (int rp = 0; rp < reps; ++rp) {
-    size_t ii = 0;
-    for (size_t k = 0; k < ops.size(); ++k) {
-      const bool timed = ii < inst.size() && inst[ii] == (int)k;
-      if (timed) HIPCHK(hipEventRecord(ev[q], s));
-      launch(ops[k], s);
-      if (timed) { HIPCHK(hipEventRecord(ev[q + 1], s)); q += 2; ++ii; }
-    }
-  }
-  HIPCHK(hipEventRecord(ev[1], s));
-  if ((rc = order_end(h, s, err))) return rc;
-  HIPCHK(hipEventSynchronize(ev[1]));
-  HIPCHK(hipGetLastError());
-  float tot = 0.f;
-  HIPCHK(hipEventElapsedTime(&tot, ev[0], ev[1]));
-  *ms = tot / reps;
-  if (kernel_ms) {
-    for (int c = 0; c < 16; ++c) kernel_ms[c] = 0.0;
-    q = 2;
-    for (int rp = 0; rp < reps; ++rp)
-      for (size_t ii = 0; ii < inst.size(); ++ii) {
-        float t = 0.f;
-        HIPCHK(hipEventElapsedTime(&t, ev[q], ev[q + 1]));
-        kernel_ms[ops[inst[ii]].cls] += t / reps;
-        q += 2;
-      }
-  }
+  TimedRun tr;
+  rc = tr.run(ops.size(), [&](size_t k) { return ops[k].cls; },
+              [&](size_t k) { launch(ops[k], s); return (int)MAMG_OK; }, reps, mode, s,
+              [&]() { return h->mark(s, err); }, ms, kernel_ms, err);
+  if (rc) return rc;
 #if MAMG_DIAG
   if (mode == 1 && std::getenv("MAMG_OP_PROFILE")) {
     // diagnosis: event time per (op kind, rows) summed over one apply
     std::map<std::pair<int, int64_t>, std::pair<int, double>> acc;
-    q = 2;
     for (int rp = 0; rp < reps; ++rp)
-      for (size_t ii = 0; ii < inst.size(); ++ii) {
+      for (size_t ii = 0; ii < tr.inst.size(); ++ii) {
         float t = 0.f;
-        HIPCHK(hipEventElapsedTime(&t, ev[q], ev[q + 1]));
-        const Op& o = ops[inst[ii]];
+        if ((rc = tr.op_ms(rp, ii, &t, err))) return rc;
+        const Op& o = ops[tr.inst[ii]];
         auto& a = acc[{o.kind, o.Mb ? o.Mb->nr : (o.M ? o.M->n : o.n)}];
         a.first += 1;
         a.second += t;
-        q += 2;
       }
     for (const auto& kv : acc)
       std::fprintf(stderr, "[mamg op] kind %d rows %lld launches/apply %.1f ms/apply %.4f us/launch %.2f\n",
@@ -7559,7 +7482,6 @@ int dev_time_apply(DeviceHandle* h, const double* d_r, double* d_z, int reps, in
     }
   }
 #endif  // MAMG_DIAG
-  for (auto& e : ev) (void)hipEventDestroy(e);
   return MAMG_OK;
 }
 

@@ -47,6 +47,66 @@ enum Epi { EPI_Y = 0, EPI_YADD = 1, EPI_RESID = 2, EPI_JACOBI = 3, EPI_BJAC = 4,
 // writing x1_c = W_c b_c: one launch and one b_c read fewer per coarse level;
 // the same two products as bd2_kernel, so the same bits)
 
+// ---- run-time value -> template argument (the launch ladder, device.hip).
+// Each helper hands f a std::integral_constant / std::bool_constant / TypeC
+// chosen by a run-time value, so a kernel family's launch statement is
+// written once, inside a generic lambda.  The mappings are checked below: a
+// wrong one fails the build.
+// v if it is one of Vs, else D
+template <int D, class F>
+constexpr decltype(auto) with_int(int, F&& f) { return f(std::integral_constant<int, D>{}); }
+template <int D, int V, int... Vs, class F>
+constexpr decltype(auto) with_int(int v, F&& f) {
+  if (v == V) return f(std::integral_constant<int, V>{});
+  return with_int<D, Vs...>(v, f);
+}
+// lanes of a lane-group kernel (DCsr / DBsr::lanes): 2, 4, 8, 16, 32, anything else 64
+template <class F>
+constexpr decltype(auto) with_lanes(int lanes, F&& f) { return with_int<64, 2, 4, 8, 16, 32>(lanes, f); }
+// lanes per row of the multi-lane SELL kernel (DBsr::lpr): 2, 4, 8, anything else 16
+template <class F>
+constexpr decltype(auto) with_lpr(int lpr, F&& f) { return with_int<16, 2, 4, 8>(lpr, f); }
+// the epilogue if it is one of Es, else Default
+template <int Default, int... Es, class F>
+constexpr decltype(auto) with_epi(int epi, F&& f) { return with_int<Default, Es...>(epi, f); }
+// f(std::bool_constant<b>...)
+template <bool... Bs, class F>
+constexpr decltype(auto) with_bools(F&& f) { return f(std::bool_constant<Bs>{}...); }
+template <bool... Bs, class F, class... Rest>
+constexpr decltype(auto) with_bools(F&& f, bool b, Rest... rest) {
+  if (b) return with_bools<Bs..., true>(f, rest...);
+  return with_bools<Bs..., false>(f, rest...);
+}
+// the stored value type of an operator (DBsr::f32)
+template <class T> struct TypeC { using type = T; };
+template <class F>
+constexpr decltype(auto) with_value_type(bool f32, F&& f) {
+  if (f32) return f(TypeC<float>{});
+  return f(TypeC<double>{});
+}
+
+struct DispatchProbe {   // what a helper handed over, as a number
+  template <class C> constexpr int operator()(C) const { return C::value; }
+  template <class A, class B> constexpr int operator()(A, B) const { return 2 * A::value + B::value; }
+  template <class T> constexpr int operator()(TypeC<T>) const { return (int)sizeof(T); }
+};
+static_assert(with_lanes(2, DispatchProbe{}) == 2 && with_lanes(4, DispatchProbe{}) == 4 &&
+              with_lanes(8, DispatchProbe{}) == 8 && with_lanes(16, DispatchProbe{}) == 16 &&
+              with_lanes(32, DispatchProbe{}) == 32 && with_lanes(64, DispatchProbe{}) == 64 &&
+              with_lanes(3, DispatchProbe{}) == 64 && with_lanes(0, DispatchProbe{}) == 64, "with_lanes");
+static_assert(with_lpr(2, DispatchProbe{}) == 2 && with_lpr(4, DispatchProbe{}) == 4 &&
+              with_lpr(8, DispatchProbe{}) == 8 && with_lpr(16, DispatchProbe{}) == 16 &&
+              with_lpr(5, DispatchProbe{}) == 16 && with_lpr(1, DispatchProbe{}) == 16, "with_lpr");
+static_assert(with_epi<EPI_JACOBI, EPI_Y, EPI_YADD, EPI_RESID>(EPI_YADD, DispatchProbe{}) == EPI_YADD &&
+              with_epi<EPI_JACOBI, EPI_Y, EPI_YADD, EPI_RESID>(EPI_KPOST, DispatchProbe{}) == EPI_JACOBI &&
+              with_epi<EPI_BJAC, EPI_Y, EPI_KPOST>(EPI_KPOST, DispatchProbe{}) == EPI_KPOST &&
+              with_epi<EPI_BJAC, EPI_Y, EPI_KPOST>(EPI_YBD, DispatchProbe{}) == EPI_BJAC, "with_epi");
+static_assert(with_bools(DispatchProbe{}, true) == 1 && with_bools(DispatchProbe{}, false) == 0 &&
+              with_bools(DispatchProbe{}, true, false) == 2 && with_bools(DispatchProbe{}, false, true) == 1 &&
+              with_bools(DispatchProbe{}, true, true) == 3, "with_bools keeps the order of its arguments");
+static_assert(with_value_type(true, DispatchProbe{}) == 4 && with_value_type(false, DispatchProbe{}) == 8,
+              "with_value_type");
+
 typedef double dv4 __attribute__((ext_vector_type(4)));
 typedef double dv2 __attribute__((ext_vector_type(2)));
 
@@ -341,29 +401,81 @@ struct Op {
 
 inline int remap_of(const Op& o) { return o.remap; }
 
-struct Graph {
-  const double* r = nullptr;
-  double* z = nullptr;
-  hipGraphExec_t exec = nullptr;
+// a captured stream as graph + exec (capture_graph, device.hip), owned by
+// whoever holds it: drop() destroys both
+struct CapturedGraph {
   hipGraph_t graph = nullptr;
-};
-
-// one PCG iteration captured for a solution vector x and a history length
-// (dev_pcg): reused by later solves into the same x (drivers, gamma sweeps)
-struct PcgGraph {
-  double* x = nullptr;
-  int maxiter = 0;
   hipGraphExec_t exec = nullptr;
-  hipGraph_t graph = nullptr;
-  double* hist = nullptr;          // residuals[maxiter + 1], alphas[maxiter], betas[maxiter]
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  void release() {
+  void drop() {
     if (exec) (void)hipGraphExecDestroy(exec);
     if (graph) (void)hipGraphDestroy(graph);
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    if (hist) (void)raw_free(hist);
-    *this = PcgGraph();
+    exec = nullptr; graph = nullptr;
   }
+};
+
+// `body` captured on *cap (created on first use) and instantiated: *out holds
+// graph and exec, or nothing is left behind -- on every failure what was made
+// is destroyed and the sticky HIP error cleared.  body's own code is returned
+// as it is; a HIP failure is MAMG_ERR_HIP with "stream capture of the <what>:
+// ..." or "hipGraphInstantiate of the <what>: ...".  The capture mutex is held
+// from before the begin until after the instantiate.
+int capture_graph(hipStream_t* cap, const std::function<int()>& body, const char* what, CapturedGraph* out,
+                  std::string* err);
+
+// A handle's apply graphs, one per (r, z) pair, at most 16: the oldest goes
+// once every launch on the handle has finished (`last`, HandleOrder below).
+struct GraphCache {
+  struct Entry { const double* r; double* z; CapturedGraph g; };
+  std::vector<Entry> v;
+  // the exec for (r, z): cached, or captured now by capture(CapturedGraph*)
+  template <class Capture>
+  int get(const double* r, double* z, hipEvent_t last, Capture&& capture, hipGraphExec_t* exec, std::string* err) {
+    for (Entry& e : v)
+      if (e.r == r && e.z == z) { *exec = e.g.exec; return MAMG_OK; }
+    if (v.size() >= 16) {   // evict the oldest, after every launch on the handle finished
+      if (last) HIPCHK(hipEventSynchronize(last));
+      v.front().g.drop();
+      v.erase(v.begin());
+    }
+    Entry e{r, z, {}};
+    const int rc = capture(&e.g);
+    if (rc) return rc;
+    v.push_back(e);
+    *exec = e.g.exec;
+    return MAMG_OK;
+  }
+  void clear() {
+    for (Entry& e : v) e.g.drop();
+    v.clear();
+  }
+};
+
+// one PCG iteration as a graph (none: the iteration runs eagerly), with the
+// device histories of a solve and the two events the host polls behind
+struct IterGraph : CapturedGraph {
+  double* hist = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  int alloc(size_t hist_doubles, std::string* err);   // hist and ev; nothing left behind on failure
+  void release() {
+    drop();
+    for (hipEvent_t& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    if (hist) (void)raw_free(hist);
+    hist = nullptr;
+  }
+};
+// a handle's iteration graphs or plans, all of them (destructor, set_cycle_storage)
+template <class V>
+void release_all(V* v) {
+  for (auto& q : *v) q.release();
+  v->clear();
+}
+
+// the iteration graph of a solution vector x and a history length (dev_pcg):
+// reused by later solves into the same x (drivers, gamma sweeps); hist holds
+// residuals[maxiter + 1], alphas[maxiter], betas[maxiter]
+struct PcgGraph : IterGraph {
+  double* x = nullptr;
+  int maxiter = 0;
 };
 
 // The memory side of a handle, single-GPU or rank: all that dalloc and the
@@ -375,7 +487,64 @@ struct HandleMem {
   size_t arena_left = 0;
 };
 
-struct DeviceHandle : HandleMem {
+// The ordering side of a handle, single-GPU or rank.  Every piece of work on
+// the handle's scratch, ghost, send, receive and level work buffers (apply,
+// host apply, spmv, PCG, timing) makes its stream wait for the handle's last
+// mark, whatever stream that was recorded on, and leaves its own mark behind:
+// work on one handle is serialized across streams (include/mamg.h).  A base
+// beside HandleMem and not part of it: the layout builders take a HandleMem
+// and order nothing, they run on the null stream before the handle's first
+// mark.  The handle's destructor owns `last` (a rank waits for it first).
+struct HandleOrder {
+  hipEvent_t last = nullptr;
+  int wait(hipStream_t s, std::string* err) {
+    if (last) HIPCHK(hipStreamWaitEvent(s, last, 0));   // never marked: nothing to wait for
+    return MAMG_OK;
+  }
+  int mark(hipStream_t s, std::string* err) {
+    if (!last) HIPCHK(hipEventCreateWithFlags(&last, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(last, s));
+    return MAMG_OK;
+  }
+};
+
+// `reps` runs of a list of ops on one stream between two events, with an
+// event pair around every op of the level-0 residual and smoothing classes
+// (mode 0) or around every op (mode 1).  The object owns the events: they go
+// with it on every path.
+struct TimedRun {
+  std::vector<int> inst;           // the instrumented ops
+  std::vector<hipEvent_t> ev;      // [0], [1]: the whole run; then per rep, per instrumented op, (start, end)
+  ~TimedRun() {
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+  }
+  int create(size_t n, std::string* err) {
+    ev.assign(n, nullptr);
+    for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+    return MAMG_OK;
+  }
+  // cls(k): the class of op k; op(k): queue it on s (the project's code);
+  // queued(): between the last record and the host's wait (may be empty).
+  // ms: per rep; kernel_ms (16 slots, may be null): per class and rep
+  int run(size_t nops, const std::function<int(size_t)>& cls, const std::function<int(size_t)>& op, int reps, int mode,
+          hipStream_t s, const std::function<int()>& queued, double* ms, double* kernel_ms, std::string* err);
+  // the time of instrumented op ii in rep rp
+  int op_ms(int rp, size_t ii, float* t, std::string* err) const {
+    const size_t q = 2 + 2 * ((size_t)rp * inst.size() + ii);
+    HIPCHK(hipEventElapsedTime(t, ev[q], ev[q + 1]));
+    return MAMG_OK;
+  }
+};
+
+// The end of a PCG solve, single-GPU or distributed, from the final state's
+// status and iteration count: "Matrix is not positive" (no iteration ran), or
+// the device histories (rn: nullptr without stop_type 1's ||r||) copied out,
+// niters set, and the two breakdown messages.
+struct PcgHist { const double *res, *rn, *al, *be; };
+int pcg_finish(int status, int it, const PcgHist& d, double* residuals, double* rnorms, double* alphas,
+               double* betas, int* niters, std::string* err);
+
+struct DeviceHandle : HandleMem, HandleOrder {
   mamg_params p;
   explicit DeviceHandle(const Switches& s) : HandleMem{s, {}, nullptr, 0} {}
   int device = 0;
@@ -384,7 +553,7 @@ struct DeviceHandle : HandleMem {
   char* arena0 = nullptr;          // the reservation's range [arena0, arena1)
   char* arena1 = nullptr;
   hipStream_t cap = nullptr;
-  std::vector<Graph> graphs;
+  GraphCache graphs;
   std::vector<PcgGraph> pcgs;
   // coarse tail (tail_kernel): first level run by it (0 = off) and the
   // device op lists built so far, one per (b, x) entry of that level
@@ -406,17 +575,10 @@ struct DeviceHandle : HandleMem {
   double apply_bytes = 0.0;
   double setup_ms[8] = {};         // GPU setup phase timings (dev_from_ghier)
   double layout_ms[4] = {};        // apply-layout phases: build, K region trials, re-homing, finish (LT_*)
-  // every piece of work on the handle's scratch buffers (apply, host apply,
-  // spmv, PCG, timing) waits for this event on its stream and re-records it
-  // afterwards: work on one handle is serialized across streams
-  hipEvent_t last = nullptr;
   ~DeviceHandle() {
     if (last) (void)hipEventDestroy(last);
-    for (auto& g : graphs) {
-      if (g.exec) (void)hipGraphExecDestroy(g.exec);
-      if (g.graph) (void)hipGraphDestroy(g.graph);
-    }
-    for (auto& g : pcgs) g.release();
+    graphs.clear();
+    release_all(&pcgs);
     for (auto& t : tails) (void)raw_free(t.prog);
     for (void* a : allocs) (void)raw_free(a);
     if (hres) (void)hipHostFree(hres);
@@ -662,7 +824,7 @@ struct DOp {
 // A_loc as the cycle reads it: level 0's fp32 copy once the rank is narrowed
 inline const DBsr& dcyc_A(const DDLevel& D) { return D.Ac.f32 ? D.Ac : D.A; }
 
-struct DistHandle : HandleMem {
+struct DistHandle : HandleMem, HandleOrder {   // last: marked after every apply / spmv / PCG (dist_destroy waits)
   mamg_params p;
   explicit DistHandle(const Switches& s) : HandleMem{s, {}, nullptr, 0} {}
   int rank = 0, nranks = 1, device = 0;
@@ -674,7 +836,6 @@ struct DistHandle : HandleMem {
   bool dry = false;                    // MAMG_DIST_TEST=dry: virtual rank skips its exchanges (timing only)
   hipStream_t side = nullptr;          // stream of the interior rows
   hipEvent_t ev_in = nullptr, ev_out = nullptr;
-  hipEvent_t last = nullptr;           // recorded after every apply / spmv / timing (dist_destroy waits)
   // host-staged exchange backend (mamg_dist_set_exchange): pinned staging
   // per level (sends, ghost payloads, receives of the reverse-add) and one
   // all-reduce buffer
@@ -686,22 +847,9 @@ struct DistHandle : HandleMem {
   // the apply replayed as a hipGraph (dist_apply_graph): one per (r, z) pair,
   // captured on `cap` with the RCCL calls inside; graph_err set when a
   // capture failed (the handle then stays eager)
-  struct Graph {
-    const double* r;
-    double* z;
-    hipGraph_t g;
-    hipGraphExec_t e;
-  };
-  std::vector<Graph> graphs;
+  GraphCache graphs;
   hipStream_t cap = nullptr;
   std::string graph_err;
-  void drop_graphs() {
-    for (auto& g : graphs) {
-      (void)hipGraphExecDestroy(g.e);
-      (void)hipGraphDestroy(g.g);
-    }
-    graphs.clear();
-  }
   // device-resident PCG (dist_pcg): r, z, d, q of w * nloc
   // doubles, the dots' block partials and P-vectors, the state with its
   // pinned mirror (two slots per rank whose state is read here), and one
@@ -711,26 +859,15 @@ struct DistHandle : HandleMem {
   DPcgState* pst = nullptr;
   DPcgState* hst = nullptr;
   int hst_ranks = 0;
-  struct PcgPlan {
+  struct PcgPlan : IterGraph {         // hist: residuals, ||r||, alphas, betas
     std::unique_ptr<DPcgCtx> c;
-    double* hist = nullptr;            // residuals, ||r||, alphas, betas
-    hipGraph_t g = nullptr;
-    hipGraphExec_t e = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    void release() {
-      if (e) (void)hipGraphExecDestroy(e);
-      if (g) (void)hipGraphDestroy(g);
-      for (hipEvent_t v : ev) if (v) (void)hipEventDestroy(v);
-      if (hist) (void)raw_free(hist);
-      e = nullptr; g = nullptr; hist = nullptr; ev[0] = ev[1] = nullptr;
-    }
   };
   std::vector<PcgPlan> pcgs;
   std::string pcg_graph_err;           // why the iteration runs eagerly on this handle
   ~DistHandle() {
     if (last) (void)hipEventSynchronize(last);
-    drop_graphs();
-    for (auto& q : pcgs) q.release();
+    graphs.clear();
+    release_all(&pcgs);
     if (hst) (void)hipHostFree(hst);
     if (cap) (void)hipStreamDestroy(cap);
     for (void* q : pinned) (void)hipHostFree(q);
@@ -755,8 +892,7 @@ int ddalloc(DistHandle* h, T** p, int64_t count, std::string* err) {
   return MAMG_OK;
 }
 
-// ---- device.hip
-hipError_t graph_instantiate(hipGraphExec_t* ex, hipGraph_t g);
+// ---- device.hip (and capture_graph, TimedRun::run, IterGraph::alloc, pcg_finish above)
 void wscale(int64_t n, double w, const double* in, double* out);
 void launch_patch_inv(int version, int64_t np, const int32_t* perm, const int64_t* ptr, const int32_t* col,
                       const int32_t* gcol, const dv4* val, int64_t ustride, double* U, int* bad);

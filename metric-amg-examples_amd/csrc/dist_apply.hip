@@ -849,9 +849,8 @@ int dist_set_cycle_storage(DistHandle* h, int storage, std::string* err) {
   if (h->cap) HIPCHK(hipStreamSynchronize(h->cap));
   // the cached graphs and PCG plans hold the fp64 op list: dropped, the next use captures anew
   auto drop_cached = [&]() {
-    h->drop_graphs();
-    for (auto& q : h->pcgs) q.release();
-    h->pcgs.clear();
+    h->graphs.clear();
+    release_all(&h->pcgs);
   };
   // the fp64 originals go back except level 0's A_loc (the Krylov operator)
   auto release = [&](void* old) {
@@ -867,21 +866,6 @@ int dist_set_cycle_storage(DistHandle* h, int storage, std::string* err) {
   dapply_ops(h, nullptr, nullptr, &ops);
   h->apply_bytes = 0.0;
   for (const DOp& d : ops) h->apply_bytes += d.bytes;
-  return MAMG_OK;
-}
-
-// handle ordering (DistHandle::last), as order_begin / order_end of a
-// DeviceHandle: every call that touches the rank's ghost, send, receive and
-// level work buffers first makes its stream wait for the handle's last mark,
-// whatever stream that was recorded on, and leaves its own mark behind
-int dist_wait(DistHandle* h, hipStream_t s, std::string* err) {
-  if (h->last) HIPCHK(hipStreamWaitEvent(s, h->last, 0));
-  return MAMG_OK;
-}
-
-int dist_mark(DistHandle* h, hipStream_t s, std::string* err) {
-  if (!h->last) HIPCHK(hipEventCreateWithFlags(&h->last, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(h->last, s));
   return MAMG_OK;
 }
 
@@ -937,13 +921,13 @@ int dist_apply(DistHandle* h, const double* d_r, double* d_z, void* stream, std:
   HIPCHK(hipSetDevice(h->device));
   std::vector<DOp> ops;
   dapply_ops(h, d_r, d_z, &ops);
-  int rc = dist_wait(h, (hipStream_t)stream, err);
+  int rc = h->wait((hipStream_t)stream, err);
   if (rc) return rc;
   for (const DOp& d : ops) {
     if ((rc = run_dop(h, d, (hipStream_t)stream, err))) return rc;
   }
   HIPCHK(hipGetLastError());
-  return dist_mark(h, (hipStream_t)stream, err);
+  return h->mark((hipStream_t)stream, err);
 }
 
 int dist_spmv(DistHandle* h, const double* d_x, double* d_y, void* stream, std::string* err) {
@@ -951,13 +935,13 @@ int dist_spmv(DistHandle* h, const double* d_x, double* d_y, void* stream, std::
   if (h->L.empty() || h->L[0].coarsest) { *err = "single-level hierarchy: no distributed operator"; return MAMG_ERR_ARG; }
   std::vector<DOp> ops;
   dspmv_ops(h, d_x, d_y, &ops);
-  int rc = dist_wait(h, (hipStream_t)stream, err);
+  int rc = h->wait((hipStream_t)stream, err);
   if (rc) return rc;
   for (const DOp& d : ops) {
     if ((rc = run_dop(h, d, (hipStream_t)stream, err))) return rc;
   }
   HIPCHK(hipGetLastError());
-  return dist_mark(h, (hipStream_t)stream, err);
+  return h->mark((hipStream_t)stream, err);
 }
 
 // The op list of one apply captured into a hipGraph on the handle's capture
@@ -965,32 +949,13 @@ int dist_spmv(DistHandle* h, const double* d_x, double* d_y, void* stream, std::
 // the RCCL send / receive groups and all-reduces inside the capture.  A
 // failed capture leaves nothing behind and is reported (the caller stays
 // eager).
-int dist_capture(DistHandle* h, const std::vector<DOp>& ops, hipGraph_t* gr, hipGraphExec_t* ex, std::string* err) {
-  *gr = nullptr;
-  *ex = nullptr;
-  std::lock_guard<std::recursive_mutex> capture_lock(capture_mutex());
-  if (!h->cap) HIPCHK(hipStreamCreateWithFlags(&h->cap, hipStreamNonBlocking));
-  HIPCHK(hipStreamBeginCapture(h->cap, hipStreamCaptureModeThreadLocal));
-  int rc = MAMG_OK;
-  for (const DOp& d : ops)
-    if ((rc = run_dop(h, d, h->cap, err))) break;
-  hipGraph_t g = nullptr;
-  const hipError_t e = hipStreamEndCapture(h->cap, &g);
-  if (rc || e != hipSuccess) {
-    if (g) (void)hipGraphDestroy(g);
-    (void)hipGetLastError();
-    if (!rc) *err = std::string("stream capture of the distributed apply: ") + hipGetErrorString(e);
-    return rc ? rc : MAMG_ERR_HIP;
-  }
-  const hipError_t ei = graph_instantiate(ex, g);
-  if (ei != hipSuccess) {
-    (void)hipGraphDestroy(g);
-    (void)hipGetLastError();
-    *err = std::string("hipGraphInstantiate of the distributed apply: ") + hipGetErrorString(ei);
-    return MAMG_ERR_HIP;
-  }
-  *gr = g;
-  return MAMG_OK;
+int dist_capture(DistHandle* h, const std::vector<DOp>& ops, CapturedGraph* g, std::string* err) {
+  return capture_graph(&h->cap, [&]() {
+    int rc = MAMG_OK;
+    for (const DOp& d : ops)
+      if ((rc = run_dop(h, d, h->cap, err))) break;
+    return rc;
+  }, "distributed apply", g, err);
 }
 
 int dist_graph_exec(DistHandle* h, const double* d_r, double* d_z, hipGraphExec_t* ex, std::string* err) {
@@ -999,25 +964,13 @@ int dist_graph_exec(DistHandle* h, const double* d_r, double* d_z, hipGraphExec_
     return MAMG_ERR_UNSUPPORTED;
   }
   if (!h->graph_err.empty()) { *err = "graph capture failed on this handle: " + h->graph_err; return MAMG_ERR_UNSUPPORTED; }
-  for (auto& g : h->graphs)
-    if (g.r == d_r && g.z == d_z) { *ex = g.e; return MAMG_OK; }
-  if (h->graphs.size() >= 16) {   // evict the oldest once every launch on the handle finished
-    if (h->last) HIPCHK(hipEventSynchronize(h->last));
-    (void)hipGraphExecDestroy(h->graphs.front().e);
-    (void)hipGraphDestroy(h->graphs.front().g);
-    h->graphs.erase(h->graphs.begin());
-  }
-  std::vector<DOp> ops;
-  dapply_ops(h, d_r, d_z, &ops);
-  DistHandle::Graph g{d_r, d_z, nullptr, nullptr};
-  const int rc = dist_capture(h, ops, &g.g, &g.e, err);
-  if (rc) {
-    h->graph_err = *err;
+  return h->graphs.get(d_r, d_z, h->last, [&](CapturedGraph* g) {
+    std::vector<DOp> ops;
+    dapply_ops(h, d_r, d_z, &ops);
+    const int rc = dist_capture(h, ops, g, err);
+    if (rc) h->graph_err = *err;
     return rc;
-  }
-  h->graphs.push_back(g);
-  *ex = g.e;
-  return MAMG_OK;
+  }, ex, err);
 }
 
 int dist_graph_prepare(DistHandle* h, const double* d_r, double* d_z, std::string* err) {
@@ -1031,9 +984,9 @@ int dist_apply_graph(DistHandle* h, const double* d_r, double* d_z, void* stream
   hipGraphExec_t ex = nullptr;
   int rc = dist_graph_exec(h, d_r, d_z, &ex, err);
   if (rc) return rc;
-  if ((rc = dist_wait(h, (hipStream_t)stream, err))) return rc;
+  if ((rc = h->wait((hipStream_t)stream, err))) return rc;
   HIPCHK(hipGraphLaunch(ex, (hipStream_t)stream));
-  return dist_mark(h, (hipStream_t)stream, err);
+  return h->mark((hipStream_t)stream, err);
 }
 
 int dist_time_apply(DistHandle* h, const double* d_r, double* d_z, int reps, int mode, double* ms,
@@ -1051,60 +1004,25 @@ int dist_time_apply(DistHandle* h, const double* d_r, double* d_z, int reps, int
     hipGraphExec_t ex = nullptr;
     int rc = dist_graph_exec(h, d_r, d_z, &ex, err);
     if (rc) return rc;
-    if ((rc = dist_wait(h, s, err))) return rc;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, s));
+    if ((rc = h->wait(s, err))) return rc;
+    TimedRun tr;
+    if ((rc = tr.create(2, err))) return rc;
+    HIPCHK(hipEventRecord(tr.ev[0], s));
     for (int rp = 0; rp < reps; ++rp) HIPCHK(hipGraphLaunch(ex, s));
-    HIPCHK(hipEventRecord(e1, s));
-    HIPCHK(hipEventSynchronize(e1));
+    HIPCHK(hipEventRecord(tr.ev[1], s));
+    HIPCHK(hipEventSynchronize(tr.ev[1]));
     float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, e0, e1));
+    HIPCHK(hipEventElapsedTime(&t, tr.ev[0], tr.ev[1]));
     *ms = t / reps;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     if (kernel_ms)
       for (int c = 0; c < 16; ++c) kernel_ms[c] = 0.0;
-    return dist_mark(h, s, err);
+    return h->mark(s, err);
   }
-  std::vector<int> inst;
-  for (size_t k = 0; k < ops.size(); ++k)
-    if (mode == 1 || ops[k].cls == C_L0_RESID || ops[k].cls == C_L0_SMOOTH) inst.push_back((int)k);
-  std::vector<hipEvent_t> ev(2 * inst.size() * (size_t)reps + 2);
-  for (auto& e : ev) HIPCHK(hipEventCreate(&e));
   int rc;
-  if ((rc = dist_wait(h, s, err))) return rc;
-  HIPCHK(hipEventRecord(ev[0], s));
-  size_t q = 2;
-  for (int rp = 0; rp < reps; ++rp) {
-    size_t ii = 0;
-    for (size_t k = 0; k < ops.size(); ++k) {
-      const bool timed = ii < inst.size() && inst[ii] == (int)k;
-      if (timed) HIPCHK(hipEventRecord(ev[q], s));
-      if ((rc = run_dop(h, ops[k], s, err))) return rc;
-      if (timed) { HIPCHK(hipEventRecord(ev[q + 1], s)); q += 2; ++ii; }
-    }
-  }
-  HIPCHK(hipEventRecord(ev[1], s));
-  HIPCHK(hipEventSynchronize(ev[1]));
-  HIPCHK(hipGetLastError());
-  float tot = 0.f;
-  HIPCHK(hipEventElapsedTime(&tot, ev[0], ev[1]));
-  *ms = tot / reps;
-  if (kernel_ms) {
-    for (int c = 0; c < 16; ++c) kernel_ms[c] = 0.0;
-    q = 2;
-    for (int rp = 0; rp < reps; ++rp)
-      for (size_t ii = 0; ii < inst.size(); ++ii) {
-        float t = 0.f;
-        HIPCHK(hipEventElapsedTime(&t, ev[q], ev[q + 1]));
-        kernel_ms[ops[inst[ii]].cls] += t / reps;
-        q += 2;
-      }
-  }
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  return MAMG_OK;
+  if ((rc = h->wait(s, err))) return rc;
+  TimedRun tr;
+  return tr.run(ops.size(), [&](size_t k) { return ops[k].cls; }, [&](size_t k) { return run_dop(h, ops[k], s, err); },
+                reps, mode, s, nullptr, ms, kernel_ms, err);
 }
 
 // ---------------------------------------------------------------------------
@@ -1204,7 +1122,7 @@ int virtual_run(const std::vector<DistHandle*>& hs, const std::vector<std::vecto
   HIPCHK(hipGetLastError());
   if (mark)
     for (DistHandle* h : hs) {
-      const int rc = dist_mark(h, s, err);
+      const int rc = h->mark(s, err);
       if (rc) return rc;
     }
   return MAMG_OK;
@@ -1257,7 +1175,7 @@ int dist_virtual_apply(const std::vector<DistHandle*>& hs, const std::vector<con
   for (int p = 0; p < P; ++p) dapply_ops(hs[p], r[p], z[p], &ops[p]);
   int rc;
   for (DistHandle* h : hs)
-    if ((rc = dist_wait(h, (hipStream_t)stream, err))) return rc;
+    if ((rc = h->wait((hipStream_t)stream, err))) return rc;
   return virtual_run(hs, ops, (hipStream_t)stream, err);
 }
 
@@ -1271,37 +1189,21 @@ int dist_virtual_apply_graph(const std::vector<DistHandle*>& hs, const std::vect
   std::vector<std::vector<DOp>> ops(P);
   for (int p = 0; p < P; ++p) dapply_ops(hs[p], r[p], z[p], &ops[p]);
   DistHandle* h0 = hs[0];
-  std::lock_guard<std::recursive_mutex> capture_lock(capture_mutex());
-  if (!h0->cap) HIPCHK(hipStreamCreateWithFlags(&h0->cap, hipStreamNonBlocking));
-  HIPCHK(hipStreamBeginCapture(h0->cap, hipStreamCaptureModeThreadLocal));
-  int rc = virtual_run(hs, ops, h0->cap, err, false);
-  hipGraph_t g = nullptr;
-  const hipError_t e = hipStreamEndCapture(h0->cap, &g);
-  if (rc || e != hipSuccess) {
-    if (g) (void)hipGraphDestroy(g);
-    (void)hipGetLastError();
-    if (!rc) *err = std::string("stream capture of the virtual apply: ") + hipGetErrorString(e);
-    return rc ? rc : MAMG_ERR_HIP;
-  }
-  hipGraphExec_t ex = nullptr;
-  const hipError_t ei = graph_instantiate(&ex, g);
-  if (ei != hipSuccess) {
-    (void)hipGraphDestroy(g);
-    *err = std::string("hipGraphInstantiate of the virtual apply: ") + hipGetErrorString(ei);
-    return MAMG_ERR_HIP;
-  }
+  CapturedGraph g;
+  int rc = capture_graph(&h0->cap, [&]() { return virtual_run(hs, ops, h0->cap, err, false); }, "virtual apply", &g,
+                         err);
+  if (rc) return rc;
   for (DistHandle* h : hs)
-    if (h->last) (void)hipStreamWaitEvent((hipStream_t)stream, h->last, 0);
-  const hipError_t el = hipGraphLaunch(ex, (hipStream_t)stream);
+    if ((rc = h->wait((hipStream_t)stream, err))) { g.drop(); return rc; }
+  const hipError_t el = hipGraphLaunch(g.exec, (hipStream_t)stream);
   const hipError_t es = hipStreamSynchronize((hipStream_t)stream);
-  (void)hipGraphExecDestroy(ex);
-  (void)hipGraphDestroy(g);
+  g.drop();
   if (el != hipSuccess || es != hipSuccess) {
     *err = std::string("virtual apply graph launch: ") + hipGetErrorString(el != hipSuccess ? el : es);
     return MAMG_ERR_HIP;
   }
   for (DistHandle* h : hs)
-    if ((rc = dist_mark(h, (hipStream_t)stream, err))) return rc;
+    if ((rc = h->mark((hipStream_t)stream, err))) return rc;
   return MAMG_OK;
 }
 
@@ -1316,7 +1218,7 @@ int dist_virtual_spmv(const std::vector<DistHandle*>& hs, const std::vector<cons
   }
   int rc;
   for (DistHandle* h : hs)
-    if ((rc = dist_wait(h, (hipStream_t)stream, err))) return rc;
+    if ((rc = h->wait((hipStream_t)stream, err))) return rc;
   return virtual_run(hs, ops, (hipStream_t)stream, err);
 }
 
@@ -1424,19 +1326,7 @@ int dpcg_plan(DistHandle* h, double* x, int maxiter, int stop, int slots, DistHa
     h->pcgs.erase(h->pcgs.begin());
   }
   DistHandle::PcgPlan q;
-  if (raw_malloc((void**)&q.hist, (4 * (size_t)maxiter + 2) * sizeof(double), "long") != hipSuccess) {
-    (void)hipGetLastError();
-    *err = "PCG history allocation failed";
-    return MAMG_ERR_HIP;
-  }
-  hipError_t e = hipSuccess;
-  for (hipEvent_t& v : q.ev)
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&v, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    q.release();
-    *err = std::string("PCG events: ") + hipGetErrorString(e);
-    return MAMG_ERR_HIP;
-  }
+  if ((rc = q.alloc(4 * (size_t)maxiter + 2, err))) return rc;
   q.c.reset(new DPcgCtx());
   DPcgCtx& c = *q.c;
   c.st = h->pst; c.n = n; c.P = h->nranks; c.rank = h->rank; c.stop = stop; c.maxiter = maxiter;
@@ -1447,20 +1337,11 @@ int dpcg_plan(DistHandle* h, double* x, int maxiter, int stop, int slots, DistHa
   return MAMG_OK;
 }
 
-// histories and the return code from the final state (dev_pcg's messages)
+// histories and the return code from the final state (pcg_finish, device.hip)
 int dpcg_finish(const DPcgCtx& c, const DPcgState& fin, double* residuals, double* rnorms, double* alphas,
                 double* betas, int* niters, std::string* err) {
-  const int it = fin.it;
-  HIPCHK(hipMemcpy(residuals, c.res, (it + 1) * sizeof(double), hipMemcpyDeviceToHost));
-  if (c.stop && rnorms) HIPCHK(hipMemcpy(rnorms, c.rn, (it + 1) * sizeof(double), hipMemcpyDeviceToHost));
-  if (it > 0) {
-    HIPCHK(hipMemcpy(alphas, c.al, it * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(betas, c.be, it * sizeof(double), hipMemcpyDeviceToHost));
-  }
-  *niters = it;
-  if (fin.status == PCG_DQ_ZERO) { *err = "ConjGrad stopped: <d,Ad> = 0"; return MAMG_ERR_BREAKDOWN; }
-  if (fin.status == PCG_RZ_NEG) { *err = "ConjGrad breakdown (<r,Br> < 0)"; return MAMG_ERR_BREAKDOWN; }
-  return MAMG_OK;
+  return pcg_finish(fin.status, fin.it, {c.res, c.stop ? c.rn : nullptr, c.al, c.be}, residuals, rnorms, alphas, betas,
+                    niters, err);
 }
 
 }  // namespace
@@ -1496,15 +1377,11 @@ int dist_pcg(DistHandle* h, const double* d_b, double* d_x, double tol, int maxi
   // single-rank handle; a failed capture is recorded and the same op list
   // runs eagerly -- the RCCL sequence of a rank is the same either way
   const bool graphable = (h->comm || h->nranks == 1) && h->graph_err.empty() && h->pcg_graph_err.empty();
-  if (graphable && !pl->e) {
+  if (graphable && !pl->exec) {
     std::string cerr;
-    if (dist_capture(h, ops, &pl->g, &pl->e, &cerr)) {
-      h->pcg_graph_err = cerr;
-      pl->g = nullptr;
-      pl->e = nullptr;
-    }
+    if (dist_capture(h, ops, pl, &cerr)) h->pcg_graph_err = cerr;
   }
-  if (h->last) HIPCHK(hipStreamWaitEvent(s, h->last, 0));   // the work buffers are the handle's
+  if ((rc = h->wait(s, err))) return rc;   // the work buffers are the handle's
   std::vector<DOp> start;
   dpcg_start_ops(h, &c, &start);
   for (const DOp& d : start)
@@ -1513,11 +1390,8 @@ int dist_pcg(DistHandle* h, const double* d_b, double* d_x, double tol, int maxi
   HIPCHK(hipMemcpyAsync(&hst[0], st, sizeof(DPcgState), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   if (hst[0].status == PCG_NOT_POS) {
-    *niters = 0;
-    residuals[0] = 0.0;
-    (void)dist_mark(h, s, err);
-    *err = "Matrix is not positive";
-    return MAMG_ERR_BREAKDOWN;
+    (void)h->mark(s, err);
+    return dpcg_finish(c, hst[0], residuals, rnorms, alphas, betas, niters, err);
   }
   if (hst[0].active) {
     // iteration k's state lands in hst[k & 1].  The host-staged exchange
@@ -1527,8 +1401,8 @@ int dist_pcg(DistHandle* h, const double* d_b, double* d_x, double tol, int maxi
     // depends on all-reduced state only: the same on every rank.
     const bool ahead = !(h->host_ex && !h->comm);
     for (int k = 0; k < maxiter; ++k) {
-      if (pl->e) {
-        HIPCHK(hipGraphLaunch(pl->e, s));
+      if (pl->exec) {
+        HIPCHK(hipGraphLaunch(pl->exec, s));
       } else {
         for (const DOp& d : ops)
           if ((rc = run_dop(h, d, s, err))) return rc;
@@ -1542,7 +1416,7 @@ int dist_pcg(DistHandle* h, const double* d_b, double* d_x, double tol, int maxi
     }
   }
   HIPCHK(hipMemcpyAsync(&hst[0], st, sizeof(DPcgState), hipMemcpyDeviceToHost, s));
-  if ((rc = dist_mark(h, s, err))) return rc;
+  if ((rc = h->mark(s, err))) return rc;
   HIPCHK(hipStreamSynchronize(s));
   HIPCHK(hipGetLastError());
   return dpcg_finish(c, hst[0], residuals, rnorms, alphas, betas, niters, err);
@@ -1572,7 +1446,7 @@ int dist_virtual_pcg(const std::vector<DistHandle*>& hs, const std::vector<const
     c.b = b[p]; c.tol = tol; c.relconv = relativeconv;
     dpcg_start_ops(hs[p], &c, &start[p]);
     dpcg_iter_ops(hs[p], &c, &ops[p]);
-    if (hs[p]->last) HIPCHK(hipStreamWaitEvent(s, hs[p]->last, 0));
+    if ((rc = hs[p]->wait(s, err))) return rc;
   }
   DPcgState* hst = h0->hst;                    // [2][P]
   auto read_states = [&](int slot) -> int {
@@ -1589,32 +1463,11 @@ int dist_virtual_pcg(const std::vector<DistHandle*>& hs, const std::vector<const
       }
     return MAMG_OK;
   };
-  hipGraph_t g = nullptr;
-  hipGraphExec_t ex = nullptr;
-  auto drop = [&]() {
-    if (ex) (void)hipGraphExecDestroy(ex);
-    if (g) (void)hipGraphDestroy(g);
-    ex = nullptr; g = nullptr;
-  };
-  if (graph && maxiter > 0) {
-    std::lock_guard<std::recursive_mutex> capture_lock(capture_mutex());
-    if (!h0->cap) HIPCHK(hipStreamCreateWithFlags(&h0->cap, hipStreamNonBlocking));
-    HIPCHK(hipStreamBeginCapture(h0->cap, hipStreamCaptureModeThreadLocal));
-    rc = virtual_run(hs, ops, h0->cap, err, false);
-    const hipError_t e = hipStreamEndCapture(h0->cap, &g);
-    if (rc || e != hipSuccess) {
-      drop();
-      (void)hipGetLastError();
-      if (!rc) *err = std::string("stream capture of the virtual PCG iteration: ") + hipGetErrorString(e);
-      return rc ? rc : MAMG_ERR_HIP;
-    }
-    const hipError_t ei = graph_instantiate(&ex, g);
-    if (ei != hipSuccess) {
-      drop();
-      *err = std::string("hipGraphInstantiate of the virtual PCG iteration: ") + hipGetErrorString(ei);
-      return MAMG_ERR_HIP;
-    }
-  }
+  CapturedGraph g;
+  if (graph && maxiter > 0 &&
+      (rc = capture_graph(&h0->cap, [&]() { return virtual_run(hs, ops, h0->cap, err, false); },
+                          "virtual PCG iteration", &g, err)))
+    return rc;
   // from here on every exit drains the stream and drops the graph
   auto body = [&]() -> int {
     int r;
@@ -1624,7 +1477,7 @@ int dist_virtual_pcg(const std::vector<DistHandle*>& hs, const std::vector<const
     if ((r = same_states(0, 0))) return r;
     if (hst[0].status == PCG_NOT_POS || !hst[0].active) return MAMG_OK;
     for (int k = 0; k < maxiter; ++k) {
-      if (ex) HIPCHK(hipGraphLaunch(ex, s));
+      if (g.exec) HIPCHK(hipGraphLaunch(g.exec, s));
       else if ((r = virtual_run(hs, ops, s, err, false))) return r;
       if ((r = read_states(k & 1))) return r;
       HIPCHK(hipEventRecord(pl[0]->ev[k & 1], s));
@@ -1641,18 +1494,12 @@ int dist_virtual_pcg(const std::vector<DistHandle*>& hs, const std::vector<const
   rc = body();
   for (DistHandle* h : hs) {
     std::string merr;
-    (void)dist_mark(h, s, &merr);
+    (void)h->mark(s, &merr);
   }
   (void)hipStreamSynchronize(s);
-  drop();
+  g.drop();
   if (rc) return rc;
   HIPCHK(hipGetLastError());
-  if (hst[0].status == PCG_NOT_POS) {
-    *niters = 0;
-    residuals[0] = 0.0;
-    *err = "Matrix is not positive";
-    return MAMG_ERR_BREAKDOWN;
-  }
   return dpcg_finish(*pl[0]->c, hst[0], residuals, rnorms, alphas, betas, niters, err);
 }
 
