@@ -44,7 +44,23 @@ enum {
 
 /* ---- parameter enums (HAZmath names, build-defined values) ---------- */
 enum { MAMG_UA_AMG = 1, MAMG_SA_AMG = 2 };                       /* AMG_type   */
-enum { MAMG_V_CYCLE = 1, MAMG_W_CYCLE = 2 };                     /* cycle_type */
+enum {                                                           /* cycle_type */
+  MAMG_V_CYCLE = 1, MAMG_W_CYCLE = 2,
+  /* 3 (HAZmath's linear AMLI) is not built: MAMG_ERR_UNSUPPORTED.
+   * Nonlinear AMLI (K-cycle; HAZmath's NL_AMLI with its GCG inner solver):
+   * on every level but the coarsest, the coarse problem A_c e = b_c is solved
+   * by amli_degree steps of flexible (generalised) CG preconditioned by the
+   * cycle of that level; the coarsest level is the one dense solve, as in V
+   * and W.  The step count is fixed (no residual-based early exit, so an apply
+   * stays one graph), and a direction with <p, A p> <= 0 is dropped (no update;
+   * K(0) = 0).  The preconditioner is nonlinear in r, homogeneous of degree 1.
+   * amli_degree in [1, MAMG_NL_AMLI_MAX], else MAMG_ERR_ARG.  Single GPU:
+   * mamg_setup_dist returns MAMG_ERR_UNSUPPORTED before the rank touches its
+   * GPU; mamg_set_cycle_storage(MAMG_STORE_F32) on such a handle returns
+   * MAMG_ERR_UNSUPPORTED and leaves it as it was. */
+  MAMG_NL_AMLI_CYCLE = 4
+};
+#define MAMG_NL_AMLI_MAX 4   /* largest amli_degree of MAMG_NL_AMLI_CYCLE */
 enum {                                                          /* smoother   */
   MAMG_SMOOTHER_JACOBI = 1,      /* x += w D^-1 r, w = relaxation             */
   MAMG_SMOOTHER_L1DIAG = 2,      /* x += w L1^-1 r, L1_ii = sum_j |a_ij|      */
@@ -149,7 +165,7 @@ enum { MAMG_COARSE_DENSE = 32 };  /* coarse_solver: 32 (UMFPACK in HAZmath)  */
 typedef struct mamg_params {
   int32_t abi_version;       /* = MAMG_ABI_VERSION                           */
   int32_t AMG_type;          /* MAMG_SA_AMG (default) | MAMG_UA_AMG          */
-  int32_t cycle_type;        /* MAMG_V_CYCLE (default) | MAMG_W_CYCLE        */
+  int32_t cycle_type;        /* MAMG_V_CYCLE (default) | MAMG_W_CYCLE | MAMG_NL_AMLI_CYCLE */
   int32_t max_levels;        /* 20                                           */
   int32_t maxit;             /* cycles per apply, 1                          */
   int32_t smoother;          /* MAMG_SMOOTHER_JACOBI_RHO (mamg_params_default) */
@@ -162,7 +178,8 @@ typedef struct mamg_params {
   int32_t aggregation_type;  /* MAMG_MIS (parallel MIS-2) | MAMG_HEM | MAMG_VMB */
   double strong_coupled;     /* SoC threshold theta, 0.0                     */
   int32_t max_aggregation;   /* accepted, unused by MIS-2 (documented)       */
-  int32_t amli_degree;       /* accepted, unused (no AMLI cycle)             */
+  int32_t amli_degree;       /* MAMG_NL_AMLI_CYCLE: inner flexible-CG steps per coarse
+                                visit, 1 .. MAMG_NL_AMLI_MAX; V / W: accepted, unused */
   int32_t Schwarz_levels;    /* 1: seed-block Jacobi on level 0 if idofs     */
   int32_t Schwarz_mmsize;    /* max dofs per seed block, 100                 */
   int32_t Schwarz_maxlvl;    /* 1: seed + joined 1-ring; 0: seed node only   */

@@ -2973,6 +2973,136 @@ __global__ __launch_bounds__(256) void cscale_kernel(int64_t n, int nb, const do
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) e[i] = a * e[i];
 }
 
+// ---- nonlinear AMLI (K-cycle, mamg.h MAMG_NL_AMLI_CYCLE): step j of the inner
+// flexible CG on a level, after z = M(r) and w = A z (tests/kcycle_ref.py):
+//   beta_i = d_i > 0 ? <z, q_i> / d_i : 0 (i < j), p_j = z - sum beta_i p_i,
+//   q_j = w - sum beta_i q_i, d_j = <p_j, q_j>, alpha = d_j > 0 ? <p_j, r> / d_j : 0,
+//   e (+)= alpha p_j, r -= alpha q_j.
+// As the coarse scaling above: block partials in fixed slots, and every block
+// of the consuming launch reduces them in one fixed order, so all blocks agree
+// on a scalar and a replay gives the same bits.  nb: the producing launch's
+// blocks.  The scalars stay in HBM (DLevel::kpart, KP_*).
+struct KDirs {
+  const double* p[MAMG_NL_AMLI_MAX - 1];
+  const double* q[MAMG_NL_AMLI_MAX - 1];
+};
+
+// the 256 threads' values summed, the same on every thread (red: 4 * NV doubles)
+template <int NV>
+__device__ __forceinline__ void kblock_sum(double (&v)[NV], double* red) {
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < NV; ++k) red[4 * k + (threadIdx.x >> 6)] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < NV; ++k) v[k] = (red[4 * k] + red[4 * k + 1]) + (red[4 * k + 2] + red[4 * k + 3]);
+}
+
+// part[KP_DOT + i * SCALE_BLOCKS + block] = the block's share of <z, q_i>, i < J
+template <int J>
+__global__ __launch_bounds__(256) void kdot_kernel(int64_t n, const double* __restrict__ z, KDirs D,
+                                                   double* __restrict__ part) {
+  __shared__ double red[4 * J];
+  double s[J];
+#pragma unroll
+  for (int i = 0; i < J; ++i) s[i] = 0.0;
+#pragma unroll 2
+  for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (int64_t)gridDim.x * 256) {
+    const double zk = z[k];
+#pragma unroll
+    for (int i = 0; i < J; ++i) s[i] += zk * D.q[i][k];
+  }
+  kblock_sum<J>(s, red);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 0; i < J; ++i) part[KP_DOT + i * SCALE_BLOCKS + blockIdx.x] = s[i];
+  }
+}
+
+// J > 0: p_j, q_j from z, w and the J earlier directions (the beta's in
+// registers); J = 0: p_0 = z and q_0 = w are in place already.  Both: the
+// block's shares of <p_j, q_j> and <p_j, r>.
+template <int J>
+__global__ __launch_bounds__(256) void korth_kernel(int64_t n, int nb, const double* __restrict__ z,
+                                                    const double* __restrict__ w, KDirs D,
+                                                    double* __restrict__ pj, double* __restrict__ qj,
+                                                    const double* __restrict__ r, double* __restrict__ part) {
+  __shared__ double red[4 * (J > 2 ? J : 2)];
+  double beta[J > 0 ? J : 1];
+  if constexpr (J > 0) {
+    double s[J];
+#pragma unroll
+    for (int i = 0; i < J; ++i) {
+      s[i] = 0.0;
+      for (int b = threadIdx.x; b < nb; b += 256) s[i] += part[KP_DOT + i * SCALE_BLOCKS + b];
+    }
+    kblock_sum<J>(s, red);
+#pragma unroll
+    for (int i = 0; i < J; ++i) {
+      const double d = part[KP_D + i];
+      beta[i] = d > 0.0 ? s[i] / d : 0.0;
+    }
+    __syncthreads();   // red is used again below
+  }
+  double a[2] = {0.0, 0.0};
+#pragma unroll 2
+  for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (int64_t)gridDim.x * 256) {
+    double pk, qk;
+    if constexpr (J > 0) {
+      pk = z[k];
+      qk = w[k];
+#pragma unroll
+      for (int i = 0; i < J; ++i) {
+        pk -= beta[i] * D.p[i][k];
+        qk -= beta[i] * D.q[i][k];
+      }
+      pj[k] = pk;
+      qj[k] = qk;
+    } else {
+      pk = pj[k];
+      qk = qj[k];
+    }
+    a[0] += pk * qk;
+    a[1] += pk * r[k];
+  }
+  kblock_sum<2>(a, red);
+  if (threadIdx.x == 0) {
+    part[KP_PQ + 2 * blockIdx.x] = a[0];
+    part[KP_PQ + 2 * blockIdx.x + 1] = a[1];
+  }
+}
+
+// d_j and alpha from korth_kernel's nb block partials; e = alpha p (FIRST) or
+// e += alpha p; rout = rin - alpha q unless LAST (step 0 reads the visit's
+// right-hand side and writes the level's own r)
+template <bool FIRST, bool LAST>
+__global__ __launch_bounds__(256) void kupd_kernel(int64_t n, int nb, int j, double* __restrict__ part,
+                                                   const double* __restrict__ p, const double* __restrict__ q,
+                                                   double* __restrict__ e, const double* rin, double* rout) {
+  __shared__ double red[8];
+  double a[2] = {0.0, 0.0};
+  for (int b = threadIdx.x; b < nb; b += 256) {
+    a[0] += part[KP_PQ + 2 * b];
+    a[1] += part[KP_PQ + 2 * b + 1];
+  }
+  kblock_sum<2>(a, red);
+  const double d = a[0];
+  const double alpha = d > 0.0 ? a[1] / d : 0.0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) part[KP_D + j] = d;
+#pragma unroll 2
+  for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (int64_t)gridDim.x * 256) {
+    const double pk = p[k];
+    e[k] = FIRST ? alpha * pk : e[k] + alpha * pk;
+    if (!LAST) rout[k] = rin[k] - alpha * q[k];
+  }
+}
+
 // Fixed by measurement (round 1 A/Bs; the variants
 // measured slower were removed in round 2): XCD-contiguous restriction rows,
 // SELL chunks of 8 blocks (K: 6), half-symmetric chunks of 4 with
@@ -5093,6 +5223,29 @@ namespace {
 
 void scale_ops(const DeviceHandle* h, int lc, std::vector<Op>* ops);
 
+inline bool kcycle(const mamg_params& p) { return p.cycle_type == MAMG_NL_AMLI_CYCLE; }
+
+// nonlinear AMLI: the vector ops of step j of level lc's inner flexible CG,
+// after z = M(r) and w = A_c z (step 0: straight into p_0 / q_0): the j dots
+// <z, q_i> in one pass over z; p_j, q_j and the partials of <p_j, q_j>,
+// <p_j, r> in one pass; then e (+)= alpha p_j and, but for the last step,
+// r -= alpha q_j (step 0 reads the visit's right-hand side C.b, writes C.kr)
+void kstep_ops(const DeviceHandle* h, int lc, int j, std::vector<Op>* ops) {
+  const DLevel& C = h->L[lc];
+  const int m = h->p.amli_degree;
+  const bool last = j == m - 1;
+  Op o;
+  o.cls = C_MISC; o.n = C.n; o.lev = &C; o.r0 = j; o.r1 = m; o.part = C.kpart;
+  if (j > 0) {
+    o.kind = OP_KDOT; o.bytes = 8.0 * (1 + j) * C.n;
+    ops->push_back(o);
+  }
+  o.kind = OP_KORTH; o.bytes = 8.0 * (j > 0 ? 2 + 2 * j + 2 + 1 : 3) * C.n;
+  ops->push_back(o);
+  o.kind = OP_KUPD; o.bytes = 8.0 * ((j > 0 ? 3 : 2) + (last ? 0 : 3)) * C.n;
+  ops->push_back(o);
+}
+
 // algorithmic bytes of one point-wise GS colour step (mamg.h mamg_apply_bytes):
 // values + columns, pointers, perm, 1 / a_ii, b, own x read and written, and
 // the gathered x (every entry once per sweep, spread over the colours)
@@ -5180,6 +5333,31 @@ void ring_csr_step_ops(const DLevel& L, double* x, const double* b, std::vector<
 // CSR cycle below (W: a second visit), coarse scaling, x += P e, nu2 steps;
 // the step is palindromic, so it serves both sides; in place on xout
 void cycle_ops_csr(const DeviceHandle* h, int l, const double* b, double* xout, std::vector<Op>* ops);
+
+// the coarse visit of a CSR cycle: C.x ~ A_c^-1 C.b on level c.  V: the cycle
+// of level c; W: a second one on the updated residual; nonlinear AMLI (c not
+// the coarsest): amli_degree steps of flexible CG preconditioned by that
+// cycle, step 0 on C.b itself and straight into p_0 / q_0, e in C.x
+void coarse_visit_ops_csr(const DeviceHandle* h, int c, std::vector<Op>* ops) {
+  const DLevel& C = h->L[c];
+  const mamg_params& p = h->p;
+  if (kcycle(p) && !C.coarsest) {
+    for (int j = 0; j < p.amli_degree; ++j) {
+      double* z = j == 0 ? C.kp[0] : C.kz;
+      cycle_ops_csr(h, c, j == 0 ? C.b : C.kr, z, ops);
+      ops->push_back(csr_op(C.A, EPI_Y, C_MISC, 1, z, nullptr, nullptr, nullptr, j == 0 ? C.kq[0] : C.kw));
+      kstep_ops(h, c, j, ops);
+    }
+    return;
+  }
+  cycle_ops_csr(h, c, C.b, C.x, ops);
+  if (p.cycle_type == MAMG_W_CYCLE && !C.coarsest) {
+    ops->push_back(csr_op(C.A, EPI_RESID, C_MISC, 1, C.x, nullptr, C.b, nullptr, C.c));
+    cycle_ops_csr(h, c, C.c, C.e, ops);
+    ops->push_back(axpy_op(C.n, C.e, C.x));
+  }
+}
+
 void cycle_ops_csr_rings(const DeviceHandle* h, const double* b, double* xout, std::vector<Op>* ops) {
   const DLevel& L = h->L[0];
   const DLevel& C = h->L[1];
@@ -5191,12 +5369,7 @@ void cycle_ops_csr_rings(const DeviceHandle* h, const double* b, double* xout, s
   for (int s = 0; s < p.presmooth_iter; ++s) ring_csr_step_ops(L, X, b, ops);
   ops->push_back(csr_op(L.A, EPI_RESID, C_L0_RESID, 0, X, nullptr, b, nullptr, L.r));
   ops->push_back(csr_op(L.R, EPI_Y, C_L0_R, 0, L.r, nullptr, nullptr, nullptr, C.b));
-  cycle_ops_csr(h, 1, C.b, C.x, ops);
-  if (p.cycle_type == MAMG_W_CYCLE && !C.coarsest) {
-    ops->push_back(csr_op(C.A, EPI_RESID, C_MISC, 1, C.x, nullptr, C.b, nullptr, C.c));
-    cycle_ops_csr(h, 1, C.c, C.e, ops);
-    ops->push_back(axpy_op(C.n, C.e, C.x));
-  }
+  coarse_visit_ops_csr(h, 1, ops);
   if (p.coarse_scaling) scale_ops(h, 1, ops);
   ops->push_back(csr_op(L.P, EPI_YADD, C_L0_P, 0, C.x, X, nullptr, nullptr, X));
   for (int s = 0; s < p.postsmooth_iter; ++s) ring_csr_step_ops(L, X, b, ops);
@@ -5218,12 +5391,7 @@ void cycle_ops_csr_gs(const DeviceHandle* h, int l, const double* b, double* xou
   cgs_smooth_ops(L, true, p.presmooth_iter, 1, sgs ? -1 : 0, X, b, clsS, clsW, ops);
   ops->push_back(csr_op(L.A, EPI_RESID, l0 ? C_L0_RESID : C_COARSE, tagA, X, nullptr, b, nullptr, L.r));
   ops->push_back(csr_op(L.R, EPI_Y, l0 ? C_L0_R : C_COARSE, tagA, L.r, nullptr, nullptr, nullptr, C.b));
-  cycle_ops_csr(h, l + 1, C.b, C.x, ops);
-  if (p.cycle_type == MAMG_W_CYCLE && !C.coarsest) {
-    ops->push_back(csr_op(C.A, EPI_RESID, C_MISC, 1, C.x, nullptr, C.b, nullptr, C.c));
-    cycle_ops_csr(h, l + 1, C.c, C.e, ops);
-    ops->push_back(axpy_op(C.n, C.e, C.x));
-  }
+  coarse_visit_ops_csr(h, l + 1, ops);
   if (p.coarse_scaling) scale_ops(h, l + 1, ops);
   ops->push_back(csr_op(L.P, EPI_YADD, l0 ? C_L0_P : C_COARSE, tagA, C.x, X, nullptr, nullptr, X));
   cgs_smooth_ops(L, false, p.postsmooth_iter, sgs ? 1 : 0, -1, X, b, clsS, clsW, ops);
@@ -5265,12 +5433,7 @@ void cycle_ops_csr(const DeviceHandle* h, int l, const double* b, double* xout, 
   }
   ops->push_back(csr_op(L.A, EPI_RESID, l0 ? C_L0_RESID : C_COARSE, tagA, X, nullptr, b, nullptr, L.r));
   ops->push_back(csr_op(L.R, EPI_Y, l0 ? C_L0_R : C_COARSE, tagA, L.r, nullptr, nullptr, nullptr, C.b));
-  cycle_ops_csr(h, l + 1, C.b, C.x, ops);
-  if (p.cycle_type == MAMG_W_CYCLE && !C.coarsest) {
-    ops->push_back(csr_op(C.A, EPI_RESID, C_MISC, 1, C.x, nullptr, C.b, nullptr, C.c));
-    cycle_ops_csr(h, l + 1, C.c, C.e, ops);
-    ops->push_back(axpy_op(C.n, C.e, C.x));
-  }
+  coarse_visit_ops_csr(h, l + 1, ops);
   if (p.coarse_scaling) scale_ops(h, l + 1, ops);
   ops->push_back(csr_op(L.P, EPI_YADD, l0 ? C_L0_P : C_COARSE, tagA, C.x, X, nullptr, nullptr, X));
   for (int s = 0; s < npost; ++s) {
@@ -5414,6 +5577,9 @@ int64_t tail_lds_plan(const DeviceHandle* h, int l, std::vector<TOp>* prog, int6
   for (size_t ll = l; ll < h->L.size(); ++ll) {
     const DLevel& L = h->L[ll];
     for (double* v : {L.b, L.x, L.t, L.t2, L.r, L.c, L.e, L.q})
+      if (v) vecs.push_back({v, L.n});
+    // nonlinear AMLI: the cycle of a Krylov level runs on its r and writes its z or p_0
+    for (double* v : {L.kr, L.kz, L.kw, L.kp[0], L.kq[0]})
       if (v) vecs.push_back({v, L.n});
     if (L.part2) vecs.push_back({L.part2, 2 * SCALE_BLOCKS});
   }
@@ -5775,6 +5941,30 @@ bool starts_with_bd(const DeviceHandle* h, int l) {
 // A_l as the cycle reads it: level 0's fp32 copy once the handle is narrowed
 inline const DBsr& cyc_A(const DLevel& L) { return L.Ac.f32 ? L.Ac : L.Ab; }
 
+// the coarse visit of a BSR2 cycle (coarse_visit_ops_csr restated): ybd: the
+// restriction's epilogue has written the first sweep X = W C.b into C.t, which
+// the visit's first cycle (V, W: the first visit; nonlinear AMLI: step 0, which
+// preconditions C.b itself) then skips
+void coarse_visit_ops_bsr(const DeviceHandle* h, int c, std::vector<Op>* ops, bool tail_ok, bool ybd) {
+  const DLevel& C = h->L[c];
+  const mamg_params& p = h->p;
+  if (kcycle(p) && !C.coarsest) {
+    for (int j = 0; j < p.amli_degree; ++j) {
+      double* z = j == 0 ? C.kp[0] : C.kz;
+      cycle_ops_bsr(h, c, j == 0 ? C.b : C.kr, 0, z, 0, ops, tail_ok, j == 0 && ybd);
+      ops->push_back(bsr_op(C.Ab, EPI_Y, C_MISC, 1, z, 0, nullptr, nullptr, 0, nullptr, j == 0 ? C.kq[0] : C.kw, 0));
+      kstep_ops(h, c, j, ops);
+    }
+    return;
+  }
+  cycle_ops_bsr(h, c, C.b, 0, C.x, 0, ops, tail_ok, ybd);
+  if (p.cycle_type == MAMG_W_CYCLE && !C.coarsest) {
+    ops->push_back(bsr_op(C.Ab, EPI_RESID, C_MISC, 1, C.x, 0, nullptr, C.b, 0, nullptr, C.c, 0));
+    cycle_ops_bsr(h, c, C.c, 0, C.e, 0, ops, tail_ok);
+    ops->push_back(axpy_op(C.n, C.e, C.x));
+  }
+}
+
 void cycle_ops_bsr(const DeviceHandle* h, int l, const double* b, int64_t bs, double* xout,
                    int64_t os, std::vector<Op>* ops, bool tail_ok, bool x1_ready) {
   if (tail_ok && l > 0 && l == h->tail_level && bs == 0 && os == 0 && tail_ops(h, l, b, xout, ops)) return;
@@ -5839,12 +6029,7 @@ void cycle_ops_bsr(const DeviceHandle* h, int l, const double* b, int64_t bs, do
     r.y = C.t;
     r.bytes += 48.0 * (double)(C.n / 2);   // W_c read, x1_c written
   }
-  cycle_ops_bsr(h, l + 1, C.b, 0, C.x, 0, ops, tail_ok, ybd);
-  if (p.cycle_type == MAMG_W_CYCLE && !C.coarsest) {
-    ops->push_back(bsr_op(C.Ab, EPI_RESID, C_MISC, 1, C.x, 0, nullptr, C.b, 0, nullptr, C.c, 0));
-    cycle_ops_bsr(h, l + 1, C.c, 0, C.e, 0, ops, tail_ok);
-    ops->push_back(axpy_op(C.n, C.e, C.x));
-  }
+  coarse_visit_ops_bsr(h, l + 1, ops, tail_ok, ybd);
   if (p.coarse_scaling) scale_ops(h, l + 1, ops);
   if (gs) {   // prolongate, then backward (SGS: forward then backward) sweeps
     ops->push_back(bsr_op(L.Pb, EPI_YADD, l0 ? C_L0_P : C_COARSE, tagA, C.x, 0, X, nullptr, 0, nullptr, X, 0));
@@ -6178,6 +6363,50 @@ void launch_cgs(const Op& o, hipStream_t s) {
   });
 }
 
+// nonlinear AMLI: the inner flexible CG's work space of level l (DLevel::kr
+// ..), on the levels that can be a Krylov level: 1 .. coarsest - 1
+int kcycle_alloc(DeviceHandle* h, int l, std::string* err) {
+  DLevel& D = h->L[l];
+  if (!kcycle(h->p) || l == 0 || D.coarsest) return MAMG_OK;
+  int rc;
+  const int m = h->p.amli_degree;
+  for (double** v : {&D.kr, &D.kz, &D.kw})
+    if ((rc = dalloc(h, v, D.n, err))) return rc;
+  for (int i = 0; i < m; ++i)
+    if ((rc = dalloc(h, &D.kp[i], D.n, err)) || (rc = dalloc(h, &D.kq[i], D.n, err))) return rc;
+  return dalloc(h, &D.kpart, KP_SIZE, err);
+}
+
+// one op of a nonlinear AMLI step (kstep_ops): step r0 of r1 on level o.lev
+void launch_kstep(const Op& o, hipStream_t s) {
+  const DLevel& C = *o.lev;
+  const int j = (int)o.r0;
+  const bool first = j == 0, last = j == (int)o.r1 - 1;
+  const int nb = (int)std::min<int64_t>(SCALE_BLOCKS, nblocks(o.n));
+  KDirs D = {};
+  for (int i = 0; i < j; ++i) { D.p[i] = C.kp[i]; D.q[i] = C.kq[i]; }
+  const double* r = first ? C.b : C.kr;
+  if (o.kind == OP_KDOT) {
+    switch (j) {
+      case 1: kdot_kernel<1><<<nb, 256, 0, s>>>(o.n, C.kz, D, o.part); break;
+      case 2: kdot_kernel<2><<<nb, 256, 0, s>>>(o.n, C.kz, D, o.part); break;
+      default: kdot_kernel<3><<<nb, 256, 0, s>>>(o.n, C.kz, D, o.part); break;
+    }
+  } else if (o.kind == OP_KORTH) {
+    switch (j) {
+      case 0: korth_kernel<0><<<nb, 256, 0, s>>>(o.n, nb, C.kz, C.kw, D, C.kp[0], C.kq[0], r, o.part); break;
+      case 1: korth_kernel<1><<<nb, 256, 0, s>>>(o.n, nb, C.kz, C.kw, D, C.kp[1], C.kq[1], r, o.part); break;
+      case 2: korth_kernel<2><<<nb, 256, 0, s>>>(o.n, nb, C.kz, C.kw, D, C.kp[2], C.kq[2], r, o.part); break;
+      default: korth_kernel<3><<<nb, 256, 0, s>>>(o.n, nb, C.kz, C.kw, D, C.kp[3], C.kq[3], r, o.part); break;
+    }
+  } else {
+    with_bools([&](auto f, auto l) {
+      kupd_kernel<decltype(f)::value, decltype(l)::value><<<nb, 256, 0, s>>>(o.n, nb, j, o.part, C.kp[j], C.kq[j],
+                                                                            C.x, r, C.kr);
+    }, first, last);
+  }
+}
+
 }  // namespace
 
 void launch(const Op& o, hipStream_t s) {
@@ -6238,6 +6467,11 @@ void launch(const Op& o, hipStream_t s) {
       break;
     case OP_DOT2:
       if (o.n) dot2_partial_kernel<<<SCALE_BLOCKS, 256, 0, s>>>(o.n, o.b, o.x, o.y, o.part);
+      break;
+    case OP_KDOT:
+    case OP_KORTH:
+    case OP_KUPD:
+      if (o.n) launch_kstep(o, s);
       break;
     case OP_TAIL:   // r1: bit 0 = every gathered x in LDS, bit 1 = register-resident rows
       if (o.n) tail_launch<false>((int)o.r1, o.prog, (int)o.n, o.tail_pl, (size_t)o.r0, nullptr, s);
@@ -6781,6 +7015,7 @@ int dev_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, cons
       if ((rc = dalloc(h.get(), &D.q, D.n, err))) return rc;
       if ((rc = dalloc(h.get(), &D.part2, 2 * SCALE_BLOCKS, err))) return rc;
     }
+    if ((rc = kcycle_alloc(h.get(), l, err))) return rc;
   }
   const int64_t n0 = h->L[0].n;
   double** v0[] = {&h->hr, &h->hz};
@@ -6964,6 +7199,7 @@ int dev_from_ghier(GHier* G, const DevMat& A0, const mamg_params& p, DeviceHandl
       if ((rc = dalloc(h.get(), &D.q, D.n, err))) return rc;
       if ((rc = dalloc(h.get(), &D.part2, 2 * SCALE_BLOCKS, err))) return rc;
     }
+    if ((rc = kcycle_alloc(h.get(), l, err))) return rc;
   }
   const int64_t n0 = h->L[0].n;
   double** v0[] = {&h->hr, &h->hz};
@@ -7166,6 +7402,10 @@ int dev_set_cycle_storage(DeviceHandle* h, int storage, std::string* err) {
     return MAMG_ERR_UNSUPPORTED;
   }
   if (narrowed) return MAMG_OK;
+  if (h->p.cycle_type == MAMG_NL_AMLI_CYCLE) {
+    *err = "cycle storage: fp32 is not available with the nonlinear AMLI cycle";
+    return MAMG_ERR_UNSUPPORTED;
+  }
   if (!h->bsr) {
     *err = "cycle storage: fp32 needs the BSR2 layout (this handle holds the CSR layout)";
     return MAMG_ERR_UNSUPPORTED;

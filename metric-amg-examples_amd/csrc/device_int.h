@@ -112,6 +112,15 @@ typedef double dv2 __attribute__((ext_vector_type(2)));
 
 constexpr int SCALE_BLOCKS = 256;   // partial-sum blocks of the coarse-scaling dots
 
+// nonlinear AMLI (K-cycle) work space of a Krylov level, DLevel::kpart: the
+// stored d_i = <p_i, q_i> (KP_D), OP_KDOT's block partials of <z, q_i>, slot
+// [KP_DOT + i * SCALE_BLOCKS + block], and OP_KORTH's block partials of
+// <p_j, q_j> and <p_j, r>, interleaved from KP_PQ
+constexpr int KP_D = 0;
+constexpr int KP_DOT = 8;
+constexpr int KP_PQ = KP_DOT + (MAMG_NL_AMLI_MAX - 1) * SCALE_BLOCKS;
+constexpr int KP_SIZE = KP_PQ + 2 * SCALE_BLOCKS;
+
 // partial-sum blocks of the PCG dots
 constexpr int DOT_BLOCKS = 1024;
 
@@ -351,6 +360,13 @@ struct DLevel {
   // q = A_l e, partial sums of <b, e>, <q, e>
   double* q = nullptr;
   double* part2 = nullptr;
+  // nonlinear AMLI (K-cycle handles, levels 1 .. coarsest - 1): the inner
+  // flexible CG's residual, preconditioned residual and A z, its amli_degree
+  // directions p_i and q_i = A p_i, and the scalar / partials block (KP_*).
+  // The level's cycle scribbles on t / t2 / r / c / e / q: these are their own.
+  double *kr = nullptr, *kz = nullptr, *kw = nullptr;
+  double *kp[MAMG_NL_AMLI_MAX] = {}, *kq[MAMG_NL_AMLI_MAX] = {};
+  double* kpart = nullptr;
 };
 
 enum OpKind { OP_CSR = 0, OP_SCALE = 1, OP_GEMV = 2, OP_AXPY = 3, OP_BSR = 4, OP_BD = 5, OP_POST = 6, OP_ILV = 7,
@@ -363,7 +379,12 @@ enum OpKind { OP_CSR = 0, OP_SCALE = 1, OP_GEMV = 2, OP_AXPY = 3, OP_BSR = 4, OP
               OP_PDOT = 19,    // block partials of <x, y> over the owned entries
               OP_PSLOT = 20,   // n dots' partials -> slot [rank] of their P-vectors
               OP_PR0 = 21,     // r = b - q (start-up)
-              OP_PINIT = 22, OP_PALPHA = 23, OP_PXR = 24, OP_PBETA = 25, OP_PD = 26 };
+              OP_PINIT = 22, OP_PALPHA = 23, OP_PXR = 24, OP_PBETA = 25, OP_PD = 26,
+              // nonlinear AMLI: step r0 of r1 of the inner flexible CG on level Op::lev (kdot_kernel,
+              // korth_kernel, kupd_kernel)
+              OP_KDOT = 27,    // block partials of <z, q_i>, i < r0
+              OP_KORTH = 28,   // beta_i from them; p_j, q_j; block partials of <p_j, q_j>, <p_j, r>
+              OP_KUPD = 29 };  // d_j stored, alpha; e (+)= alpha p_j, r -= alpha q_j
 // kernel classes (kernel_ms / class_bytes slots)
 enum Cls {
   C_L0_RESID = 0,   // dominant: r = b - A0 x (once per apply)

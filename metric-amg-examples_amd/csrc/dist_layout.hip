@@ -875,6 +875,10 @@ int dist_check(const mamg_params& p, std::string* err) {
     *err = "multi-GPU apply supports maxit 1 (one cycle per application, src/amg_parameters.py:71)";
     return MAMG_ERR_UNSUPPORTED;
   }
+  if (p.cycle_type == MAMG_NL_AMLI_CYCLE) {
+    *err = "multi-GPU apply supports the V and W cycles: the nonlinear AMLI cycle (K-cycle) is single-GPU";
+    return MAMG_ERR_UNSUPPORTED;
+  }
   if (int rc = dist_layout_check(p, err)) return rc;   // scalar (CSR) or nodal (BSR2) hierarchies (dist.cpp)
   return MAMG_OK;
 }

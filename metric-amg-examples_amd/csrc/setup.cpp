@@ -1078,7 +1078,14 @@ mamg_params resolve_like(const mamg_params& in, const mamg_params& built) {
 int check_params(const mamg_params& p, std::string* err) {
   if (p.abi_version != MAMG_ABI_VERSION) { *err = "mamg_params.abi_version mismatch"; return MAMG_ERR_ARG; }
   if (p.AMG_type != MAMG_SA_AMG && p.AMG_type != MAMG_UA_AMG) { *err = "AMG_type must be SA_AMG or UA_AMG"; return MAMG_ERR_UNSUPPORTED; }
-  if (p.cycle_type != MAMG_V_CYCLE && p.cycle_type != MAMG_W_CYCLE) { *err = "cycle_type must be V_CYCLE or W_CYCLE (AMLI/NL_AMLI/ADD not implemented)"; return MAMG_ERR_UNSUPPORTED; }
+  if (p.cycle_type != MAMG_V_CYCLE && p.cycle_type != MAMG_W_CYCLE && p.cycle_type != MAMG_NL_AMLI_CYCLE) {
+    *err = "cycle_type must be V_CYCLE, W_CYCLE or NL_AMLI_CYCLE (linear AMLI and the additive cycle are not implemented)";
+    return MAMG_ERR_UNSUPPORTED;
+  }
+  if (p.cycle_type == MAMG_NL_AMLI_CYCLE && (p.amli_degree < 1 || p.amli_degree > MAMG_NL_AMLI_MAX)) {
+    *err = "NL_AMLI_CYCLE needs amli_degree in [1, 4] (the inner flexible-CG steps per coarse visit)";
+    return MAMG_ERR_ARG;
+  }
   if (p.smoother != MAMG_SMOOTHER_JACOBI && p.smoother != MAMG_SMOOTHER_L1DIAG && p.smoother != MAMG_SMOOTHER_JACOBI_RHO &&
       p.smoother != MAMG_SMOOTHER_GS && p.smoother != MAMG_SMOOTHER_SGS && p.smoother != MAMG_SMOOTHER_POLY &&
       !point_gs(p)) {

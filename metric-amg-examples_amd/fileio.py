@@ -89,7 +89,7 @@ def read_dat(path: str) -> dict:
 
 
 _AMG_TYPE = {'UA': P.UA_AMG, 'SA': P.SA_AMG, 'MUA': P.UA_AMG, 'MSA': P.SA_AMG}
-_CYCLE = {'V': P.V_CYCLE, 'W': P.W_CYCLE}
+_CYCLE = {'V': P.V_CYCLE, 'W': P.W_CYCLE, 'NA': P.NL_AMLI_CYCLE}
 _SMOOTHER = {'JACOBI': P.SMOOTHER_JACOBI, 'L1DIAG': P.SMOOTHER_L1DIAG, 'GS': P.SMOOTHER_GS,
              'SGS': P.SMOOTHER_SGS, 'SOR': P.SMOOTHER_GS, 'SSOR': P.SMOOTHER_SGS}
 _AGG = {1: P.VMB, 2: P.MIS, 3: P.MWM, 4: P.HEC, 5: P.HEM}
@@ -117,9 +117,13 @@ def dat_to_parameters(d: dict, multiplicative: bool = False):
     if 'AMG_cycle_type' in d:
         t = word('AMG_cycle_type', _CYCLE, 'V')
         if t is None:
-            raise ValueError('AMG_cycle_type %r (AMLI / nonlinear AMLI / additive) is not implemented'
-                             % d['AMG_cycle_type'])
+            raise ValueError('AMG_cycle_type %r (linear AMLI / additive) is not implemented: V, W and NA '
+                             '(nonlinear AMLI) are' % d['AMG_cycle_type'])
         prm['cycle_type'] = t
+        # the K-cycle's inner solver is HAZmath's GCG (5); GCR (6) is not built
+        if t == P.NL_AMLI_CYCLE and int(d.get('AMG_nl_amli_krylov_type', 5)) != 5:
+            raise ValueError('AMG_nl_amli_krylov_type %r: the nonlinear AMLI cycle runs 5 (GCG) only'
+                             % d['AMG_nl_amli_krylov_type'])
     direct = {'AMG_levels': 'max_levels', 'AMG_maxit': 'maxit', 'AMG_relaxation': 'relaxation',
               'AMG_presmooth_iter': 'presmooth_iter', 'AMG_postsmooth_iter': 'postsmooth_iter',
               'AMG_coarse_dof': 'coarse_dof', 'AMG_coarse_solver': 'coarse_solver',

@@ -57,6 +57,8 @@ from . import _lib
 # ---- enums (names as haznics exposes them) --------------------------------
 UA_AMG, SA_AMG = 1, 2
 V_CYCLE, W_CYCLE = 1, 2
+NL_AMLI_CYCLE = 4             # nonlinear AMLI (K-cycle): amli_degree steps of flexible CG per coarse visit,
+                              # preconditioned by the coarse level's cycle (3, linear AMLI, is not built)
 SMOOTHER_JACOBI, SMOOTHER_L1DIAG, SMOOTHER_JACOBI_RHO = 1, 2, 3
 SMOOTHER_GS, SMOOTHER_SGS = 10, 11
 SMOOTHER_POLY = 12            # Chebyshev polynomial in W A (HAZmath/FASP SMOOTHER_POLY)
@@ -167,6 +169,15 @@ parameters_metric = {
 parameters_metric_schwarz = dict(
     parameters_metric, Schwarz_levels=1, Schwarz_mmsize=100, Schwarz_maxlvl=1,
     Schwarz_type=SCHWARZ_SYMMETRIC, Schwarz_blksolver=32)
+# the reference's family with the K-cycle in place of W (DESIGN.md section
+# 2.13): on every level but the coarsest the coarse problem gets amli_degree
+# steps of flexible CG preconditioned by that level's cycle.  Degree 2 visits
+# the coarse levels as often as W does and adds a few vector kernels per
+# visit.  Degree 3 (the reference dicts' amli_degree) on a pairwise (HEM)
+# hierarchy, which coarsens by about 2 per level, makes the work per level
+# grow as 1.5^level: it is accepted (up to 4) but is not the preset.  Single
+# GPU, fp64 operator storage.
+parameters_metric_kcycle = dict(parameters_metric, cycle_type=NL_AMLI_CYCLE, amli_degree=2)
 # the defaults the reference's factories fall back to when called without
 # parameters: get_hazmath_metric_precond(_mono) (src/utils.py:60-82; the EMI
 # drivers' call, src/emi_3d.py:139, src/emi_2d.py:207) and
