@@ -91,8 +91,10 @@ enum {                                                          /* smoother   */
 enum {                                                   /* aggregation_type  */
   MAMG_VMB = 1, MAMG_MIS = 2, MAMG_MWM = 3, MAMG_HEC = 4, MAMG_HEM = 5
 };  /* accepted: MIS (deterministic parallel MIS-2), HEM (parallel heavy-edge
-       matching) and VMB (sequential Vanek-Mandel-
-       Brezina; mamg_setup_gpu runs that one step on the host);
+       matching) and VMB (Vanek-Mandel-Brezina in
+       index order; mamg_setup_gpu reaches the sequential loop's aggregates
+       by worklist rounds on the device on its large levels, DESIGN.md
+       section 2.10);
        MWM/HEC -> MAMG_ERR_UNSUPPORTED */
 enum {                                                   /* Schwarz_type      */
   /* The reference's names (src/amg_parameters.py:83-87, src/utils.py:84):
@@ -484,8 +486,10 @@ int mamg_dist_set_exchange(mamg_dhandle* h, const mamg_exchange* ex);
 int mamg_setup(const mamg_csr* A, const int32_t* idofs, int64_t n_idofs,
                const mamg_params* params, mamg_handle** out);
 /* GPU setup: the same hierarchy as mamg_setup, bit
- * for bit, built by gfx950 kernels -- strength, MIS-2 / HEM aggregation (VMB:
- * its one sequential step on the host), smoothers, SA prolongator, Galerkin
+ * for bit, built by gfx950 kernels -- strength, MIS-2 / HEM / VMB aggregation (VMB: a
+ * level of fewer than 131072 nodes, or one whose device rounds pass the cap
+ * of DESIGN.md section 2.10, one long chain in index order, is aggregated by
+ * the host loop instead, the same numbers), smoothers, SA prolongator, Galerkin
  * products, coarsest inverse -- and the apply layouts built in HBM (no host
  * round trip).  Covers num_functions 1 and 2 with every smoother the host
  * setup builds: node blocks, general (not node-aligned) seed blocks,

@@ -89,6 +89,38 @@ int mamg_test_set_rowdict(int64_t min_rows, int max_types, int hash_bits);
  *   3 longest row in blocks      4 bytes of the type table */
 int mamg_rowdict_info(const mamg_handle* h, int64_t* info, int cap);
 
+/* Where the GPU setups run the Vanek-Mandel-Brezina aggregation
+ * (aggregation_type VMB), for the process.
+ *   mode 1, the default: on the device, by worklist rounds that reach the
+ *     sequential loop's aggregates exactly, on levels of at least 131072
+ *     nodes; smaller levels, where the rounds measured slower than the round
+ *     trip, send the strong graph to the host and run the loop there;
+ *   mode 2: on the device whatever the level's size (tests);
+ *   mode 0: on the host.
+ * Every path gives the same hierarchy bit for bit.  max_rounds: the device
+ * rounds of one level after which that level is abandoned to the host path;
+ * a negative value restores the default rule (the rounds that cost what the
+ * host path would, from the graph's entries).  Read by every setup at its
+ * entry, with the switches.  MAMG_ERR_ARG for another mode. */
+int mamg_test_set_vmb(int mode, int64_t max_rounds);
+
+/* What the VMB aggregation of one level did in the calling thread's most
+ * recent GPU setup.  Writes up to cap values, returns how many there are (8),
+ * 0 when that level ran no VMB aggregation, MAMG_ERR_ARG for a bad argument.
+ * info[]:
+ *   0 path: 0 host by request, 1 device, 2 device abandoned at the round cap,
+ *     then host, 3 host because the level is below the size threshold
+ *   1 device rounds (path 2: those run before the cap)
+ *   2 root-rule evaluations summed over the rounds
+ *   3 roots (aggregates)         4 non-isolated nodes
+ *   5 nodes joined in phase 2 (to their strongest aggregated neighbour)
+ *     (3 and 5: path 1 only; 4: paths 1 and 2; 0 otherwise)
+ *   6 bytes the aggregation step copied to the host (after the strength
+ *     graph is built: the round counters, or the graph itself)
+ *   7 microseconds of that step, to the aggregate numbers in device memory
+ *     (bench/vmb_setup.py: cost per round and the host path's time per level) */
+int mamg_test_vmb_info(int level, int64_t* info, int cap);
+
 #ifdef __cplusplus
 }
 #endif

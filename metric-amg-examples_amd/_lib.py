@@ -156,6 +156,8 @@ SIGNATURES = {
     'mamg_tail_info': (C.c_int, [VP, C.c_int, P_I64, C.c_int]),
     'mamg_test_set_rowdict': (C.c_int, [C.c_int64, C.c_int, C.c_int]),
     'mamg_rowdict_info': (C.c_int, [VP, P_I64, C.c_int]),
+    'mamg_test_set_vmb': (C.c_int, [C.c_int, C.c_int64]),
+    'mamg_test_vmb_info': (C.c_int, [C.c_int, P_I64, C.c_int]),
     'mamg_apply': (C.c_int, [VP, P_F64, P_F64]),
     'mamg_apply_device': (C.c_int, [VP, VP, VP, VP]),
     'mamg_spmv_device': (C.c_int, [VP, VP, VP, VP]),
@@ -205,6 +207,26 @@ def set_rowdict(min_rows=-1, max_types=-1, hash_bits=-1):
     """mamg_test_set_rowdict (include/mamg_test.h): thresholds of the
     row-pattern dictionary for the setups that follow (negative: default)."""
     check(lib().mamg_test_set_rowdict(int(min_rows), int(max_types), int(hash_bits)))
+
+
+VMB_INFO_KEYS = ('path', 'rounds', 'evaluations', 'roots', 'nonisolated', 'joiners', 'host_bytes', 'micros')
+
+
+def set_vmb(mode=1, max_rounds=-1):
+    """mamg_test_set_vmb (include/mamg_test.h): where the GPU setups that
+    follow run the VMB aggregation (1, the default: device from the size
+    threshold up, host below; 2 device on every level; 0 host) and the cap on
+    a level's device rounds (negative: the default rule)."""
+    check(lib().mamg_test_set_vmb(int(mode), int(max_rounds)))
+
+
+def vmb_info(level):
+    """mamg_test_vmb_info as a dict (VMB_INFO_KEYS) for one level of this
+    thread's most recent GPU setup; None when the level ran no VMB."""
+    v = (C.c_int64 * len(VMB_INFO_KEYS))()
+    n = lib().mamg_test_vmb_info(int(level), v, len(VMB_INFO_KEYS))
+    check(min(n, 0))
+    return dict(zip(VMB_INFO_KEYS, v)) if n else None
 
 
 def option_names():

@@ -11,6 +11,7 @@
 
 #include "device.h"
 #include "dist.h"
+#include "gsetup.h"
 #include "host.h"
 #include "mamg_test.h"
 #include "opts.h"
@@ -1070,6 +1071,27 @@ int mamg_test_set_rowdict(int64_t min_rows, int max_types, int hash_bits) {
   GUARD_BEGIN
   mamg::set_rowdict_hook(min_rows, max_types, hash_bits);
   return MAMG_OK;
+  GUARD_END
+}
+
+int mamg_test_set_vmb(int mode, int64_t max_rounds) {
+  GUARD_BEGIN
+  if (mode < 0 || mode > 2) {
+    set_error("mamg_test_set_vmb: mode must be 0 (host), 1 (device from the size threshold up) or 2 (device)");
+    return MAMG_ERR_ARG;
+  }
+  mamg::set_vmb_hook(mode, max_rounds);
+  return MAMG_OK;
+  GUARD_END
+}
+
+int mamg_test_vmb_info(int level, int64_t* info, int cap) {
+  GUARD_BEGIN
+  if (level < 0 || cap < 0 || (cap > 0 && !info)) {
+    set_error("mamg_test_vmb_info: bad level or buffer");
+    return MAMG_ERR_ARG;
+  }
+  return mamg::vmb_info(level, info, cap);
   GUARD_END
 }
 

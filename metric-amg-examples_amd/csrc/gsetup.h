@@ -2,6 +2,7 @@
 // (gsetup.hip) and consumed by the apply-layout builder (device.hip).
 // Plain pointers only (no HIP types), so host translation units can include it.
 #pragma once
+#include <array>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -96,6 +97,14 @@ int gen_bidomain_dev(int dim, int64_t n, double gamma, double k1, double k2, int
                      int32_t* colind, double* values, std::string* err);
 // host CSR -> HBM, buffers owned by G (G->device selects the GPU)
 int upload_a0(const CsrView& A, GHier* G, DevMat* D, std::string* err);
+
+// what the VMB aggregation of one level did (mamg_test.h mamg_test_vmb_info)
+enum VmbInfo { VMB_PATH = 0, VMB_ROUNDS, VMB_EVALS, VMB_ROOTS, VMB_NONISOL, VMB_JOINERS, VMB_HOST_BYTES, VMB_MICROS,
+               VMB_INFO_N };
+enum VmbPath { VMB_PATH_HOST = 0, VMB_PATH_DEVICE = 1, VMB_PATH_ABANDONED = 2, VMB_PATH_SMALL = 3 };
+// of the calling thread's most recent gpu_setup: up to cap values into info,
+// returns VMB_INFO_N, or 0 when that level ran no VMB aggregation
+int vmb_info(int level, int64_t* info, int cap);
 
 // phase_ms slots
 enum { GS_AGGREGATE = 0, GS_SMOOTHER = 1, GS_PROLONG = 2, GS_GALERKIN = 3, GS_COARSEST = 4,

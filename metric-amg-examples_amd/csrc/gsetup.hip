@@ -143,11 +143,20 @@ int galloc(GHier* G, T** p, int64_t count, std::string* err) {
   return MAMG_OK;
 }
 
+thread_local int64_t t_to_host_bytes = 0;   // bytes this thread's setups copied to the host (vmb_info)
+
 template <class T>
 int to_host(T* dst, const T* src, int64_t count, std::string* err) {
-  if (count > 0) HIPCHK(hipMemcpy(dst, src, count * sizeof(T), hipMemcpyDeviceToHost));
+  if (count > 0) {
+    HIPCHK(hipMemcpy(dst, src, count * sizeof(T), hipMemcpyDeviceToHost));
+    t_to_host_bytes += count * (int64_t)sizeof(T);
+  }
   return MAMG_OK;
 }
+
+// what the VMB aggregation of each level did in this thread's most recent
+// GPU setup (mamg_test.h mamg_test_vmb_info)
+thread_local std::vector<std::array<int64_t, VMB_INFO_N>> t_vmb_info;
 
 // ---------------------------------------------------------------------------
 // node graph (setup.cpp node_graph, nf = 2): s_IJ = sqrt(sum of squares over
@@ -486,6 +495,191 @@ __global__ __launch_bounds__(256) void agg_phase3_kernel(int64_t n, const int64_
   }
   if (ba < 0) atomicAdd(bad, 1);
   agg3[i] = ba;
+}
+
+// ---------------------------------------------------------------------------
+// Vanek-Mandel-Brezina aggregation (setup.cpp aggregate_vmb), DESIGN.md 2.10.
+// Phase 1 of the sequential loop picks the lexicographically first maximal
+// independent set of the squared strong graph: node i starts an aggregate
+// iff no earlier root lies within two strong hops.  That set is the unique
+// fixpoint of two local rules (ST_IN: root)
+//   i -> ST_IN  when every node of smaller index within two hops is ST_OUT,
+//   i -> ST_OUT when a root lies within two hops,
+// reached here by rounds over worklists: the active nodes test the root rule
+// (vmb_root_kernel), the new roots put their two-hop neighbourhood out
+// (vmb_out_kernel), and the undecided nodes within two hops of a node put out
+// form the next round's list (vmb_next_kernel; a per-node round stamp admits a
+// node once).  One wave per list item, its lanes over the item's strong
+// neighbours; the lists grow by one atomicAdd per wave and append.  List
+// lengths stay on the device: the kernels read them there and stride a
+// bounded grid, the host reads the four counters once per round.
+// ---------------------------------------------------------------------------
+constexpr int VMB_GRID = 4096;   // blocks at most of a list kernel (4 waves each)
+enum { VC_ROOTS = 0, VC_OUT = 1, VC_LIST = 2, VC_N = 4 };   // counters: roots, nodes put out (both running totals), the two lists
+
+// all lanes of the wave call it; the lanes that want append v
+__device__ __forceinline__ void vmb_append(bool want, int32_t v, int32_t* __restrict__ list,
+                                           unsigned long long* cnt) {
+  const unsigned long long b = __ballot(want);
+  if (!b) return;
+  const int lane = threadIdx.x & 63, leader = __ffsll((long long)b) - 1;
+  unsigned long long base = 0;
+  if (lane == leader) base = atomicAdd(cnt, (unsigned long long)__popcll(b));
+  base = __shfl(base, leader);
+  if (want) list[base + __popcll(b & ((1ull << lane) - 1))] = v;
+}
+
+// state, isolated flags and their count (one atomic per workgroup)
+__global__ __launch_bounds__(256) void vmb_init_kernel(int64_t n, const int64_t* __restrict__ ptr,
+                                                       const uint8_t* __restrict__ flag,
+                                                       uint64_t* __restrict__ state, uint8_t* __restrict__ nonisol,
+                                                       unsigned long long* total) {
+  __shared__ unsigned int c;
+  if (threadIdx.x == 0) c = 0;
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  bool any = false;
+  if (i < n) {
+    for (int64_t k = ptr[i]; k < ptr[i + 1]; ++k) any |= flag[k] != 0;
+    nonisol[i] = any;
+    state[i] = any ? ST_UND : ST_OUT;
+  }
+  const unsigned long long b = __ballot(any);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(&c, (unsigned int)__popcll(b));
+  __syncthreads();
+  if (threadIdx.x == 0 && c) atomicAdd(total, (unsigned long long)c);
+}
+
+// the root rule on the items of a list (list == nullptr: on every undecided
+// node, round 1).  A concurrent ST_UND -> ST_IN of another node does not
+// change the outcome: the rule asks only which nodes are ST_OUT, and no node
+// goes out in this kernel (hence relaxed atomic loads and stores of state).
+// *zero: the counter of the list the round builds.
+__global__ __launch_bounds__(256) void vmb_root_kernel(int64_t n, const int32_t* __restrict__ list,
+                                                       const unsigned long long* nlist,
+                                                       const int64_t* __restrict__ ptr,
+                                                       const int32_t* __restrict__ col,
+                                                       const uint8_t* __restrict__ flag, uint64_t* state,
+                                                       int32_t* __restrict__ roots, unsigned long long* cnt,
+                                                       unsigned long long* zero) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *zero = 0;
+  const int lane = threadIdx.x & 63;
+  const int64_t nw = (int64_t)gridDim.x * 4, items = list ? (int64_t)*nlist : n;
+  for (int64_t it = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); it < items; it += nw) {
+    const int64_t i = list ? (int64_t)list[it] : it;
+    if (!list && state[i] != ST_UND) continue;
+    const int64_t b = ptr[i], e = ptr[i + 1];
+    bool blocked = false;
+    for (int64_t k = b + lane; k < e; k += 64)   // one hop
+      if (flag[k]) {
+        const int64_t j = col[k];
+        if (j < i && __atomic_load_n(&state[j], __ATOMIC_RELAXED) != ST_OUT) blocked = true;
+      }
+    if (__any(blocked)) continue;
+    for (int64_t k0 = b; k0 < e; k0 += 64) {     // two hops
+      const int64_t k = k0 + lane;
+      if (k < e && flag[k]) {
+        const int64_t j = col[k];
+        for (int64_t q = ptr[j], qe = ptr[j + 1]; q < qe; ++q)
+          if (flag[q]) {
+            const int64_t m = col[q];
+            if (m < i && __atomic_load_n(&state[m], __ATOMIC_RELAXED) != ST_OUT) { blocked = true; break; }
+          }
+      }
+      if (__any(blocked)) break;
+    }
+    if (__any(blocked)) continue;
+    if (lane == 0) {
+      __atomic_store_n(&state[i], ST_IN, __ATOMIC_RELAXED);
+      roots[atomicAdd(&cnt[VC_ROOTS], 1ull)] = (int32_t)i;
+    }
+  }
+}
+
+__device__ __forceinline__ bool vmb_put_out(uint64_t* state, int64_t j) {
+  return atomicCAS((unsigned long long*)&state[j], (unsigned long long)ST_UND, (unsigned long long)ST_OUT) ==
+         (unsigned long long)ST_UND;
+}
+
+// every undecided node within two hops of a root of roots[r0 .. cnt[VC_ROOTS])
+// goes out and onto the list of the nodes put out
+__global__ __launch_bounds__(256) void vmb_out_kernel(int64_t r0, const int32_t* __restrict__ roots,
+                                                      const int64_t* __restrict__ ptr,
+                                                      const int32_t* __restrict__ col,
+                                                      const uint8_t* __restrict__ flag, uint64_t* state,
+                                                      int32_t* __restrict__ outl, unsigned long long* cnt) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nw = (int64_t)gridDim.x * 4, r1 = (int64_t)cnt[VC_ROOTS];
+  for (int64_t it = r0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); it < r1; it += nw) {
+    const int64_t r = roots[it], b = ptr[r], e = ptr[r + 1];
+    for (int64_t k0 = b; k0 < e; k0 += 64) {
+      const int64_t k = k0 + lane;
+      const bool valid = k < e && flag[k];
+      const int64_t j = valid ? (int64_t)col[k] : 0;
+      vmb_append(valid && vmb_put_out(state, j), (int32_t)j, outl, &cnt[VC_OUT]);
+      int64_t q = valid ? ptr[j] : 0;
+      const int64_t qe = valid ? ptr[j + 1] : 0;
+      while (__any(q < qe)) {
+        bool won = false;
+        int64_t m = 0;
+        if (q < qe) {
+          if (flag[q]) { m = col[q]; won = vmb_put_out(state, m); }
+          ++q;
+        }
+        vmb_append(won, (int32_t)m, outl, &cnt[VC_OUT]);
+      }
+    }
+  }
+}
+
+// next round's list: the undecided nodes within two hops of a node of
+// outl[c0 .. cnt[VC_OUT]); stamp admits a node once per round
+__global__ __launch_bounds__(256) void vmb_next_kernel(int64_t c0, const int32_t* __restrict__ outl,
+                                                       const int64_t* __restrict__ ptr,
+                                                       const int32_t* __restrict__ col,
+                                                       const uint8_t* __restrict__ flag,
+                                                       const uint64_t* __restrict__ state, int* stamp, int round,
+                                                       int32_t* __restrict__ next, const unsigned long long* cnt,
+                                                       unsigned long long* nnext) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nw = (int64_t)gridDim.x * 4, c1 = (int64_t)cnt[VC_OUT];
+  for (int64_t it = c0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); it < c1; it += nw) {
+    const int64_t c = outl[it], b = ptr[c], e = ptr[c + 1];
+    for (int64_t k0 = b; k0 < e; k0 += 64) {
+      const int64_t k = k0 + lane;
+      const bool valid = k < e && flag[k];
+      const int64_t j = valid ? (int64_t)col[k] : 0;
+      vmb_append(valid && state[j] == ST_UND && atomicMax(&stamp[j], round) < round, (int32_t)j, next, nnext);
+      int64_t q = valid ? ptr[j] : 0;
+      const int64_t qe = valid ? ptr[j + 1] : 0;
+      while (__any(q < qe)) {
+        bool add = false;
+        int64_t m = 0;
+        if (q < qe) {
+          if (flag[q]) {
+            m = col[q];
+            add = state[m] == ST_UND && atomicMax(&stamp[m], round) < round;
+          }
+          ++q;
+        }
+        vmb_append(add, (int32_t)m, next, nnext);
+      }
+    }
+  }
+}
+
+// nodes that phase 2 assigns (non-isolated, no phase-1 aggregate)
+__global__ __launch_bounds__(256) void vmb_joiners_kernel(int64_t n, const uint8_t* __restrict__ nonisol,
+                                                          const int64_t* __restrict__ agg1,
+                                                          unsigned long long* total) {
+  __shared__ unsigned int c;
+  if (threadIdx.x == 0) c = 0;
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const unsigned long long b = __ballot(i < n && nonisol[i] && agg1[i] < 0);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(&c, (unsigned int)__popcll(b));
+  __syncthreads();
+  if (threadIdx.x == 0 && c) atomicAdd(total, (unsigned long long)c);
 }
 
 // ---------------------------------------------------------------------------
@@ -2245,6 +2439,150 @@ int aggregate_hem_dev(GHier* G, const DevMat& Gr, const uint8_t* flag, int level
   return MAMG_OK;
 }
 
+// VMB with its sequential loop on the host (setup.cpp aggregate_vmb): the
+// strong graph built on the device goes to the host, the loop numbers the
+// aggregates, and they come back.  The path of mamg_test_set_vmb mode 0, and
+// of a level whose device rounds passed the cap.
+int aggregate_vmb_host(GHier* G, const DevMat& Gr, const uint8_t* flag, int64_t** agg_out, int64_t* nagg_out,
+                       std::string* err) {
+  const int64_t nv = Gr.n;
+  std::vector<int64_t> hptr(nv + 1);
+  std::vector<int32_t> hcol(Gr.nnz);
+  std::vector<double> hval(Gr.nnz);
+  std::vector<uint8_t> hflag(Gr.nnz);
+  RCHK(to_host(hptr.data(), Gr.ptr, nv + 1, err));
+  if (Gr.nnz) {
+    RCHK(to_host(hcol.data(), Gr.col, Gr.nnz, err));
+    RCHK(to_host(hval.data(), Gr.val, Gr.nnz, err));
+    RCHK(to_host(hflag.data(), flag, Gr.nnz, err));
+  }
+  CsrView V;
+  V.n = V.m = nv;
+  V.ptr = hptr.data();
+  V.col = hcol.data();
+  V.val = hval.data();
+  std::vector<int64_t> hagg;
+  int64_t nagg = 0;
+  int rc = aggregate_vmb_flags(V, hflag.data(), &hagg, &nagg, err);
+  if (rc) return rc;
+  int64_t* agg = nullptr;
+  RCHK(galloc(G, &agg, nv, err));
+  HIPCHK(hipMemcpy(agg, hagg.data(), nv * sizeof(int64_t), hipMemcpyHostToDevice));
+  *agg_out = agg;
+  *nagg_out = nagg;
+  return MAMG_OK;
+}
+
+// Where the device path runs and when it gives up (measured on
+// bidomain_3d n = 64 and 128, nodal and point-wise).  The host path costs
+// about 100 us plus 1.5 to 6 ns per entry of the level's graph; a device round
+// costs 65 to 120 us on a small level (three launches and a blocking
+// readback) and grows with the lists only on levels of millions of nodes.
+// Levels of 79,507 nodes and fewer lost to the host path (by 1.6 x to 6 x),
+// levels of 266,175 nodes and more won (by 3.3 x to 7 x): below
+// VMB_MIN_NODES the default mode takes the host path without trying.
+// Above it a level is abandoned once its rounds have cost what the host path
+// would have: rounds x VMB_ROUND_US against entries x VMB_HOST_NS, so a
+// chain-ordered level loses at most about twice the host path's time.
+constexpr int64_t VMB_MIN_NODES = (int64_t)1 << 17;
+constexpr double VMB_ROUND_US = 60.0, VMB_HOST_NS = 5.0;
+int64_t vmb_round_cap(const Switches& sw, int64_t nnz) {
+  if (sw.vmb_max_rounds >= 0) return sw.vmb_max_rounds;
+  return std::max<int64_t>(1, (int64_t)((double)nnz * VMB_HOST_NS / (1e3 * VMB_ROUND_US)));
+}
+
+// VMB on the device: phase 1 by worklist rounds (the vmb_* kernels), the
+// roots numbered by a scan in index order, then MIS-2's two joining kernels
+// (a root's neighbours; the rest to the strongest aggregated neighbour, from
+// a snapshot).  *abandoned: the rounds passed the cap, nothing was produced.
+int aggregate_vmb_dev(GHier* G, const DevMat& Gr, const uint8_t* flag, int64_t* info, bool* abandoned,
+                      int64_t** agg_out, int64_t* nagg_out, std::string* err) {
+  Scratch S;
+  const int64_t nv = Gr.n;
+  uint64_t* state = nullptr;
+  uint8_t* nonisol = nullptr;
+  int* stamp = nullptr;
+  int32_t *roots = nullptr, *outl = nullptr, *list[2] = {nullptr, nullptr};
+  unsigned long long* cnt = nullptr;   // VC_N counters, then the non-isolated and the joiner counts
+  RCHK(S.alloc(&state, nv, err));
+  RCHK(S.alloc(&nonisol, nv, err));
+  RCHK(S.alloc(&stamp, nv, err));
+  RCHK(S.alloc(&roots, nv, err));
+  RCHK(S.alloc(&outl, nv, err));
+  RCHK(S.alloc(&list[0], nv, err));
+  RCHK(S.alloc(&list[1], nv, err));
+  RCHK(S.alloc(&cnt, VC_N + 2, err));
+  HIPCHK(dev_memset(stamp, 0, nv * sizeof(int)));
+  HIPCHK(dev_memset(cnt, 0, (VC_N + 2) * sizeof(unsigned long long)));
+  vmb_init_kernel<<<nblk(nv), 256>>>(nv, Gr.ptr, flag, state, nonisol, cnt + VC_N);
+  HIPCHK(hipGetLastError());
+  unsigned long long h1 = 0;
+  RCHK(to_host(&h1, (const unsigned long long*)cnt + VC_N, 1, err));
+  const int64_t nonisolated = (int64_t)h1, cap = vmb_round_cap(G->sw, Gr.nnz);
+  int64_t und = nonisolated, nact = nonisolated, nroots = 0, nout = 0, rounds = 0, evals = 0;
+  info[VMB_NONISOL] = nonisolated;
+  auto grid = [](int64_t items) { return (unsigned)std::min<int64_t>(nblk(items, 4), VMB_GRID); };
+  while (und > 0) {
+    if (rounds >= cap) {
+      info[VMB_ROUNDS] = rounds;
+      info[VMB_EVALS] = evals;
+      *abandoned = true;
+      return MAMG_OK;
+    }
+    ++rounds;
+    evals += nact;
+    const int cur = (int)(rounds & 1), nxt = cur ^ 1;
+    const bool first = rounds == 1;   // round 1: every non-isolated node, no list
+    vmb_root_kernel<<<grid(first ? nv : nact), 256>>>(nv, first ? nullptr : list[cur],
+                                                      first ? nullptr : cnt + VC_LIST + cur, Gr.ptr, Gr.col, flag,
+                                                      state, roots, cnt, cnt + VC_LIST + nxt);
+    vmb_out_kernel<<<grid(nact), 256>>>(nroots, roots, Gr.ptr, Gr.col, flag, state, outl, cnt);
+    vmb_next_kernel<<<grid(und), 256>>>(nout, outl, Gr.ptr, Gr.col, flag, state, stamp, (int)(rounds + 1),
+                                        list[nxt], cnt, cnt + VC_LIST + nxt);
+    HIPCHK(hipGetLastError());
+    unsigned long long h[VC_N];
+    RCHK(to_host(h, (const unsigned long long*)cnt, VC_N, err));
+    const int64_t newr = (int64_t)h[VC_ROOTS] - nroots, newo = (int64_t)h[VC_OUT] - nout;
+    nroots = (int64_t)h[VC_ROOTS];
+    nout = (int64_t)h[VC_OUT];
+    und -= newr + newo;
+    nact = (int64_t)h[VC_LIST + nxt];
+    if (newr == 0 || und < 0 || (und > 0 && nact == 0) || nact > nv) {
+      *err = "VMB aggregation: the device rounds made no progress (round " + std::to_string(rounds) + ")";
+      return MAMG_ERR_SETUP;
+    }
+  }
+  info[VMB_ROUNDS] = rounds;
+  info[VMB_EVALS] = evals;
+  int64_t *f = nullptr, *agg = nullptr, *agg2 = nullptr, *agg3 = nullptr;
+  int* bad = nullptr;
+  RCHK(S.alloc(&f, nv, err));
+  RCHK(S.alloc(&agg, nv, err));
+  RCHK(S.alloc(&agg2, nv, err));
+  RCHK(S.alloc(&bad, 1, err));
+  RCHK(galloc(G, &agg3, nv, err));
+  HIPCHK(dev_memset(bad, 0, sizeof(int)));
+  root_flag_kernel<<<nblk(nv), 256>>>(nv, state, f);
+  RCHK(dscan_incl_i64(f, f, nv, nullptr, err));
+  int64_t nagg = 0;
+  RCHK(to_host(&nagg, (const int64_t*)f + nv - 1, 1, err));
+  if (nagg != nroots) { *err = "VMB aggregation: root count and root scan differ"; return MAMG_ERR_SETUP; }
+  root_number_kernel<<<nblk(nv), 256>>>(nv, state, f, agg);
+  agg_phase2_kernel<<<nblk(nv), 256>>>(nv, Gr.ptr, Gr.col, flag, state, agg, agg2);
+  vmb_joiners_kernel<<<nblk(nv), 256>>>(nv, nonisol, agg2, cnt + VC_N + 1);
+  agg_phase3_kernel<<<nblk(nv), 256>>>(nv, Gr.ptr, Gr.col, Gr.val, flag, nonisol, agg2, agg3, bad);
+  HIPCHK(hipGetLastError());
+  int hb = 0;
+  RCHK(read_int(bad, &hb, err));
+  RCHK(to_host(&h1, (const unsigned long long*)cnt + VC_N + 1, 1, err));
+  info[VMB_ROOTS] = nroots;
+  info[VMB_JOINERS] = (int64_t)h1;
+  if (hb) { *err = "VMB aggregation left a non-isolated node unassigned"; return MAMG_ERR_SETUP; }
+  *agg_out = agg3;
+  *nagg_out = nagg;
+  return MAMG_OK;
+}
+
 // aggregation of the node graph of A (setup.cpp node_graph + strength +
 // aggregate_mis2 / aggregate_hem); scalar: of A itself (num_functions 1)
 int aggregate(GHier* G, const DevMat& A, int64_t nv, int level, double theta, bool scalar, int64_t** agg_out,
@@ -2300,35 +2638,24 @@ int aggregate(GHier* G, const DevMat& A, int64_t nv, int level, double theta, bo
   }
   if (G->params.aggregation_type == MAMG_HEM) return aggregate_hem_dev(G, Gr, flag, level, agg_out, nagg_out, err);
   if (G->params.aggregation_type == MAMG_VMB) {
-    // sequential by definition: the strong graph built here goes to the
-    // host, setup.cpp's aggregate_vmb (bitwise the host setup's, which
-    // builds the same graph and flags) numbers the aggregates, and they come
-    // back; every other setup step stays on the device
-    std::vector<int64_t> hptr(nv + 1);
-    std::vector<int32_t> hcol(Gr.nnz);
-    std::vector<double> hval(Gr.nnz);
-    std::vector<uint8_t> hflag(Gr.nnz);
-    RCHK(to_host(hptr.data(), Gr.ptr, nv + 1, err));
-    if (Gr.nnz) {
-      RCHK(to_host(hcol.data(), Gr.col, Gr.nnz, err));
-      RCHK(to_host(hval.data(), Gr.val, Gr.nnz, err));
-      RCHK(to_host(hflag.data(), flag, Gr.nnz, err));
+    std::array<int64_t, VMB_INFO_N> info{};
+    int rc = MAMG_OK;
+    const auto t0 = std::chrono::steady_clock::now();   // the strength kernels are done (nextra was read)
+    const int64_t bytes0 = t_to_host_bytes;
+    if (G->sw.vmb_mode == 0 || (G->sw.vmb_mode == 1 && nv < VMB_MIN_NODES)) {
+      info[VMB_PATH] = G->sw.vmb_mode == 0 ? VMB_PATH_HOST : VMB_PATH_SMALL;
+      rc = aggregate_vmb_host(G, Gr, flag, agg_out, nagg_out, err);
+    } else {
+      bool abandoned = false;
+      rc = aggregate_vmb_dev(G, Gr, flag, info.data(), &abandoned, agg_out, nagg_out, err);
+      info[VMB_PATH] = abandoned ? VMB_PATH_ABANDONED : VMB_PATH_DEVICE;
+      if (rc == MAMG_OK && abandoned) rc = aggregate_vmb_host(G, Gr, flag, agg_out, nagg_out, err);
     }
-    CsrView V;
-    V.n = V.m = nv;
-    V.ptr = hptr.data();
-    V.col = hcol.data();
-    V.val = hval.data();
-    std::vector<int64_t> hagg;
-    int64_t nagg = 0;
-    int rc = aggregate_vmb_flags(V, hflag.data(), &hagg, &nagg, err);
-    if (rc) return rc;
-    int64_t* agg = nullptr;
-    RCHK(galloc(G, &agg, nv, err));
-    HIPCHK(hipMemcpy(agg, hagg.data(), nv * sizeof(int64_t), hipMemcpyHostToDevice));
-    *agg_out = agg;
-    *nagg_out = nagg;
-    return MAMG_OK;
+    info[VMB_HOST_BYTES] = t_to_host_bytes - bytes0;
+    info[VMB_MICROS] = (int64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    if (t_vmb_info.size() <= (size_t)level) t_vmb_info.resize(level + 1, std::array<int64_t, VMB_INFO_N>{{-1}});
+    t_vmb_info[level] = info;
+    return rc;
   }
   uint64_t *state = nullptr, *low = nullptr, *key = nullptr, *m1 = nullptr;
   unsigned long long* und = nullptr;
@@ -2829,6 +3156,12 @@ struct ModuleWarm {
   }
 };
 
+int vmb_info(int level, int64_t* info, int cap) {
+  if (level < 0 || (size_t)level >= t_vmb_info.size() || t_vmb_info[level][VMB_PATH] < 0) return 0;
+  for (int k = 0; k < std::min<int>(cap, VMB_INFO_N); ++k) info[k] = t_vmb_info[level][k];
+  return VMB_INFO_N;
+}
+
 int gpu_setup(const DevMat& A0, const int32_t* idofs, int64_t n_idofs, const mamg_params& p, GHier* G,
               std::string* err) {
   int rc = check_params(p, err);
@@ -2870,6 +3203,7 @@ int gpu_setup(const DevMat& A0, const int32_t* idofs, int64_t n_idofs, const mam
   G->levels.clear();
   G->seeds.clear();
   G->generic = false;
+  t_vmb_info.clear();
   HIPCHK(hipSetDevice(p.device));
   Clock clk, tot;
   {

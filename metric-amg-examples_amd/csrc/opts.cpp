@@ -29,6 +29,8 @@ struct Table {
   std::string names;
   int64_t rd_min_rows = -1;            // set_rowdict_hook (negative: default)
   int rd_max_types = -1, rd_hash_bits = -1;
+  int vmb_mode = 1;                    // set_vmb_hook
+  int64_t vmb_max_rounds = -1;
 };
 Table& table() {
   static Table t;
@@ -113,6 +115,8 @@ Switches read_switches() {
     if (t.rd_min_rows >= 0) s.rowdict_min_rows = t.rd_min_rows;
     if (t.rd_max_types >= 0) s.rowdict_max_types = std::max(1, std::min(2048, t.rd_max_types));
     if (t.rd_hash_bits >= 0) s.rowdict_hash_bits = std::max(1, std::min(62, t.rd_hash_bits));
+    s.vmb_mode = t.vmb_mode;
+    s.vmb_max_rounds = t.vmb_max_rounds;
   }
   s.tail_vl = std::max(1, std::min(64, s.tail_vl));
   s.upload_threads = std::max(1, std::min(16, s.upload_threads));
@@ -129,6 +133,13 @@ void set_rowdict_hook(int64_t min_rows, int max_types, int hash_bits) {
   t.rd_min_rows = min_rows;
   t.rd_max_types = max_types;
   t.rd_hash_bits = hash_bits;
+}
+
+void set_vmb_hook(int mode, int64_t max_rounds) {
+  Table& t = table();
+  std::lock_guard<std::mutex> g(t.m);
+  t.vmb_mode = mode;
+  t.vmb_max_rounds = max_rounds < 0 ? -1 : max_rounds;
 }
 
 std::string format_switches(const Switches& s) {

@@ -79,11 +79,21 @@ struct Switches {
   int64_t rowdict_min_rows = ROWDICT_MIN_ROWS;
   int rowdict_max_types = ROWDICT_MAX_TYPES;
   int rowdict_hash_bits = ROWDICT_HASH_BITS;
+  // where the GPU setup runs the VMB aggregation (mamg_test.h
+  // mamg_test_set_vmb; a test hook as the three above): 1 on the device from
+  // VMB_MIN_NODES nodes up and on the host below, 2 on the device whatever the
+  // size, 0 on the host; the cap on the device rounds of one level (negative:
+  // the default rule, gsetup.hip vmb_round_cap)
+  int vmb_mode = 1;
+  int64_t vmb_max_rounds = -1;
 };
 
 // process-wide thresholds of the row-pattern dictionary, read by the next
 // read_switches() (a negative value: the default)
 void set_rowdict_hook(int64_t min_rows, int max_types, int hash_bits);
+// process-wide path and round cap of the GPU setup's VMB aggregation, read
+// likewise
+void set_vmb_hook(int mode, int64_t max_rounds);
 
 // the switch's value (nullptr: unset, the built-in default applies)
 const char* opt(const char* name);
