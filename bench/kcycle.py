@@ -4,6 +4,7 @@ the bidomain_3d driver's meshes: setup time, ms per apply (graph replays),
 PCG iterations to 1e-8, time to solution, ops (launches) per apply.
 
     python bench/kcycle.py --nrefs 4,5 --degrees 2,3                 # the DESIGN table
+    python bench/kcycle.py --nrefs 4,5 --degrees 2 --tail 0,1        # ... with the K ops in the coarse tail
     MAMG_LIB=.../libmamg_diag.so MAMG_OP_PROFILE=1 python bench/kcycle.py --nrefs 4 --ops
 
 One JSON line per (mesh, profile) on stdout.  ms per apply: the median of
@@ -11,7 +12,11 @@ One JSON line per (mesh, profile) on stdout.  ms per apply: the median of
 events after a warm-up window.  Time to solution: the device-resident PCG,
 warmed by one solve, median of three.  --ops (diagnosis build with
 MAMG_OP_PROFILE): the per-kind launch counts the library prints are summed
-into ops_per_apply (a coarse-tail program counts as one).
+into ops_per_apply (a coarse-tail program counts as one).  launches_per_apply
+is the same count from the handle's op list (mamg_apply_launches), which needs
+no diagnosis build.  --tail: the K profiles run once per listed state of
+MetricAMG.set_kcycle_tail (0: the inner CG's steps as launches, 1: inside the
+coarse tail; tagged "K(m)+tail"); W runs once.
 """
 import argparse
 import json
@@ -52,7 +57,7 @@ def count_ops(B, r, z):
     return int(round(sum(counts))) if counts else None
 
 
-def measure(nrefs, tag, prm, reps, trials, ops):
+def measure(nrefs, tag, prm, reps, trials, ops, ktail=False):
     import numpy as np
     import torch
     import metric_amg_examples_amd as M
@@ -61,7 +66,7 @@ def measure(nrefs, tag, prm, reps, trials, ops):
     b = M.problems.bidomain_mms_rhs(3, n, 1e6)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    B = M.MetricAMG(s, s.W, idofs=s.idofs, parameters=prm)
+    B = M.MetricAMG(s, s.W, idofs=s.idofs, parameters=prm, kcycle_tail=ktail)
     torch.cuda.synchronize()
     setup_s = time.perf_counter() - t0
     r = torch.as_tensor(np.asarray(b, np.float64)).cuda()
@@ -93,7 +98,8 @@ def measure(nrefs, tag, prm, reps, trials, ops):
                setup_s=round(setup_s, 4), ms_per_apply=round(statistics.median(ms), 4),
                ms_per_apply_trials=[round(v, 4) for v in ms], niters=len(solver.residuals) - 1,
                solve_s=round(statistics.median(solve_s), 4), apply_bytes=B.apply_bytes,
-               tail=B.tail_info().get('tail_level'),
+               tail=B.tail_info().get('tail_level'), kcycle_tail=int(B.kcycle_tail),
+               tail_programs=len(B.tail_info()['programs']), launches_per_apply=B.apply_launches(),
                ops_per_apply=count_ops(B, r, z) if ops else None)
     B.close()
     return out
@@ -106,11 +112,17 @@ def main():
     ap.add_argument('--reps', type=int, default=50)
     ap.add_argument('--trials', type=int, default=5)
     ap.add_argument('--ops', action='store_true')
+    ap.add_argument('--tail', default='0', help="states of set_kcycle_tail for the K profiles, e.g. 0,1")
     args = ap.parse_args()
     degrees = [int(v) for v in args.degrees.split(',') if v]
+    tails = [int(v) for v in args.tail.split(',') if v]
+    if not tails or any(v not in (0, 1) for v in tails):
+        ap.error('--tail takes 0, 1 or 0,1')
     for nrefs in (int(v) for v in args.nrefs.split(',')):
         for tag, prm in profiles(degrees):
-            print(json.dumps(measure(nrefs, tag, prm, args.reps, args.trials, args.ops)), flush=True)
+            for kt in ([0] if tag == 'W' else tails):
+                print(json.dumps(measure(nrefs, tag + ('+tail' if kt else ''), prm, args.reps, args.trials, args.ops,
+                                         bool(kt))), flush=True)
 
 
 if __name__ == '__main__':

@@ -57,7 +57,10 @@ enum {                                                           /* cycle_type *
    * amli_degree in [1, MAMG_NL_AMLI_MAX], else MAMG_ERR_ARG.  Single GPU:
    * mamg_setup_dist returns MAMG_ERR_UNSUPPORTED before the rank touches its
    * GPU; mamg_set_cycle_storage(MAMG_STORE_F32) on such a handle returns
-   * MAMG_ERR_UNSUPPORTED and leaves it as it was. */
+   * MAMG_ERR_UNSUPPORTED and leaves it as it was.
+   * The inner CG's vector steps are launches unless the handle opts in with
+   * mamg_set_kcycle_tail(h, 1): the steps of the Krylov levels below the coarse
+   * tail's first level then run inside the tail's programs. */
   MAMG_NL_AMLI_CYCLE = 4
 };
 #define MAMG_NL_AMLI_MAX 4   /* largest amli_degree of MAMG_NL_AMLI_CYCLE */
@@ -604,6 +607,37 @@ enum { MAMG_STORE_F64 = 0, MAMG_STORE_F32 = 1 };
 int mamg_set_cycle_storage(mamg_handle* h, int storage);
 /* bit 0: A_l as the cycle reads it, bit 1: K_l / P_l, bit 2: R_l stored fp32; 0 before narrowing */
 int mamg_level_storage(const mamg_handle* h, int level);
+
+/* ---- the nonlinear AMLI cycle's inner CG inside the coarse tail --------
+ * (DESIGN.md sections 2.13, 4.2).  The coarse tail runs the cycle of the small
+ * levels as one single-workgroup program per visit.  After setup (state 0) a
+ * MAMG_NL_AMLI_CYCLE handle keeps every level with a Krylov level below it out
+ * of the tail, because the flexible CG's steps (dots, orthogonalisation,
+ * update) exist as launches only.  on = 1: those steps become tail ops, so the
+ * tail starts at the level its size rule picks (MAMG_TAIL_NODES), Krylov levels
+ * inside it included; on = 0: back to launches.  Both states compute the same
+ * steps with the same reduction order; the results agree to summation order of
+ * the tail's SpMVs (1e-11 relative on the tested systems, 1e-10 against the
+ * restatement tests/kcycle_ref.py).  The call is made after setup, waits for
+ * the handle's queued work, drops its cached apply graphs, PCG graphs and tail
+ * programs, and the next apply plans again; nothing is destroyed, so it is
+ * reversible.  MAMG_OK and no effect on the apply for a K-cycle BSR2 handle
+ * without a tail level.  MAMG_ERR_UNSUPPORTED, the handle untouched and the
+ * message naming the reason, for a handle whose cycle is not
+ * MAMG_NL_AMLI_CYCLE and for a CSR-layout handle (the tail is BSR2 only).
+ * MAMG_ERR_ARG for a NULL handle or another value of on.  Single GPU (rank
+ * handles refuse the cycle itself); mamg_set_cycle_storage(MAMG_STORE_F32)
+ * keeps refusing the handle in either state.  It must not run concurrently
+ * with other calls on the same handle. */
+int mamg_set_kcycle_tail(mamg_handle* h, int on);
+/* the state: 1 / 0; MAMG_ERR_ARG for a NULL handle */
+int mamg_kcycle_tail(const mamg_handle* h);
+
+/* What one mamg_apply_device issues: the launches (kernels and memsets) of the
+ * handle's op list as it stands, a coarse-tail program counting as one.
+ * Counted from the list, nothing is launched (a tail program not planned yet
+ * is planned); as mamg_dist_apply_launches on a rank handle. */
+int mamg_apply_launches(const mamg_handle* h, int64_t* launches);
 
 /* The same on a rank handle, after its setup.  The
  * call needs no communication and every rank of a communicator (every

@@ -67,7 +67,9 @@ int mamg_sharded_galerkin_check(const mamg_csr* A, const mamg_csr* P, const mamg
  *  15 largest lane count of the ops in 14
  *  16 a residency plan was made and discarded (its LDS region did not fit next
  *     to the vectors; values 5, 7, 8 then describe the replanned program)
- *  17.. per dense solve: n, 1 if its matrix is in the LDS region (else global) */
+ *  17 nonlinear AMLI step ops (T_KDOT / T_KORTH / T_KUPD; mamg_set_kcycle_tail);
+ *     their operands count in 9 and 10
+ *  18.. per dense solve: n, 1 if its matrix is in the LDS region (else global) */
 int mamg_tail_info(const mamg_handle* h, int index, int64_t* info, int cap);
 
 /* Thresholds of the row-pattern dictionary of a level-0 A (DESIGN.md section

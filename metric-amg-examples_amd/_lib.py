@@ -149,6 +149,9 @@ SIGNATURES = {
     'mamg_apply_bytes': (C.c_int, [VP, P_F64]),
     'mamg_set_cycle_storage': (C.c_int, [VP, C.c_int]),
     'mamg_level_storage': (C.c_int, [VP, C.c_int]),
+    'mamg_set_kcycle_tail': (C.c_int, [VP, C.c_int]),
+    'mamg_kcycle_tail': (C.c_int, [VP]),
+    'mamg_apply_launches': (C.c_int, [VP, P_I64]),
     'mamg_dist_set_cycle_storage': (C.c_int, [VP, C.c_int]),
     'mamg_dist_level_storage': (C.c_int, [VP, C.c_int]),
     'mamg_dist_num_levels': (C.c_int, [VP]),

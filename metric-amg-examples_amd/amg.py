@@ -115,6 +115,13 @@ def _storage_code(storage):
     return codes[storage]
 
 
+def _kcycle_tail_flag(on):
+    """True / False (or 1 / 0) -> bool; anything else is refused."""
+    if isinstance(on, (bool, int, np.integer)) and on in (0, 1):
+        return bool(on)
+    raise ValueError('kcycle_tail must be True or False')
+
+
 def gpu_setup_supported(p) -> bool:
     """The GPU setup (mamg_setup_gpu) covers num_functions 1 and 2: node-block,
     general seed-block, overlapping-ring (SCHWARZ_ADDITIVE) and point smoothers,
@@ -157,12 +164,16 @@ class MetricAMG:
        setup covers, else 'host'.  ``setup_path`` records what ran and why.
     cycle_storage: 'f64' (default) or 'f32': after the setup, narrow the
        operators the cycle streams to fp32 storage (``set_cycle_storage``).
+    kcycle_tail: False (default) or True: after the setup, run the nonlinear
+       AMLI cycle's inner CG steps inside the coarse tail (``set_kcycle_tail``;
+       K-cycle handles on the BSR2 layout only).
     """
 
     def __init__(self, A, W=None, idofs=None, parameters=None, setup='auto', cycle_storage='f64',
-                 **overrides):
+                 kcycle_tail=False, **overrides):
         self._L = _lib.lib()
         _storage_code(cycle_storage)                     # a bad value before any GPU work
+        kcycle_tail = _kcycle_tail_flag(kcycle_tail)
         ov, self.notes = _with_functions(W, parameters, overrides)
         self.params = make_params(parameters, **ov)
         if idofs is not None:
@@ -189,6 +200,8 @@ class MetricAMG:
             self._h = h
             self.setup_path = 'gpu'
             self.set_cycle_storage(cycle_storage)
+            if kcycle_tail:
+                self.set_kcycle_tail(True)
             return
         indptr, indices, data, n, m = csr_arrays(A)
         if n != m:
@@ -213,6 +226,8 @@ class MetricAMG:
             _lib.check(self._L.mamg_setup(C.byref(csr), ip, ni, C.byref(self.params), C.byref(h)))
         self._h = h
         self.set_cycle_storage(cycle_storage)
+        if kcycle_tail:
+            self.set_kcycle_tail(True)
 
     @property
     def setup_timings(self) -> dict:
@@ -281,6 +296,32 @@ class MetricAMG:
         the device PCG's A d) stay fp64."""
         _lib.check(self._L.mamg_set_cycle_storage(self._h, _storage_code(storage)))
 
+    def set_kcycle_tail(self, on):
+        """Run the K-cycle's inner CG steps of the Krylov levels below the
+        coarse tail's first level inside the tail's programs (True) or as
+        launches (False, the state after setup); mamg_set_kcycle_tail.
+        Reversible; cached graphs and tail programs are dropped and the next
+        apply plans again.  Raises (code -4) for a handle that is not a
+        K-cycle handle on the BSR2 layout."""
+        if not isinstance(on, (bool, int, np.integer)):
+            raise ValueError('kcycle_tail must be True or False')
+        _lib.check(self._L.mamg_set_kcycle_tail(self._h, int(on)))
+
+    @property
+    def kcycle_tail(self) -> bool:
+        """The state ``set_kcycle_tail`` left (mamg_kcycle_tail)."""
+        v = self._L.mamg_kcycle_tail(self._h)
+        _lib.check(min(v, 0))
+        return bool(v)
+
+    def apply_launches(self) -> int:
+        """What one apply issues: kernels and memsets of the handle's op list,
+        a coarse-tail program counting as one (mamg_apply_launches; counted,
+        nothing is launched)."""
+        n = C.c_int64()
+        _lib.check(self._L.mamg_apply_launches(self._h, C.byref(n)))
+        return n.value
+
     def level_storage(self, level: int) -> dict:
         """Which operators of level ``level`` are stored fp32
         (mamg_level_storage): A as the cycle reads it, K / P, R."""
@@ -305,7 +346,7 @@ class MetricAMG:
         ``programs`` (empty before the first apply, with the tail off, or
         when the planner refused the level)."""
         keys = ('ops', 'lds_bytes', 'xl', 'res', 'prog_lds', 'resident_rows', 'nov', 'vec_lds', 'vec_global',
-                'refused', 'gemvs', 'ops_res', 'ops_global', 'max_vl', 'replanned')
+                'refused', 'gemvs', 'ops_res', 'ops_global', 'max_vl', 'replanned', 'ops_k')
         out = {'programs': []}
         index = 0
         while True:
@@ -321,7 +362,7 @@ class MetricAMG:
             if n == 0:
                 return out
             p = {k: int(v[2 + i]) for i, k in enumerate(keys) if k != 'refused'}
-            p['gemv'] = [(int(v[17 + 2 * i]), 'lds' if v[18 + 2 * i] else 'global') for i in range(p.pop('gemvs'))]
+            p['gemv'] = [(int(v[18 + 2 * i]), 'lds' if v[19 + 2 * i] else 'global') for i in range(p.pop('gemvs'))]
             out['programs'].append(p)
             index += 1
 

@@ -1049,6 +1049,35 @@ int mamg_set_cycle_storage(mamg_handle* h, int storage) {
   GUARD_END
 }
 
+int mamg_set_kcycle_tail(mamg_handle* h, int on) {
+  GUARD_BEGIN
+  if (!h) { set_error("null handle"); return MAMG_ERR_ARG; }
+  if (on != 0 && on != 1) {
+    set_error("mamg_set_kcycle_tail: on must be 0 or 1");
+    return MAMG_ERR_ARG;
+  }
+  std::string err;
+  const int rc = mamg::dev_set_kcycle_tail(h->d, on, &err);
+  if (rc) set_error(err);
+  return rc;
+  GUARD_END
+}
+
+int mamg_kcycle_tail(const mamg_handle* h) {
+  if (!h) { mamg::set_error("null handle"); return MAMG_ERR_ARG; }
+  return mamg::dev_kcycle_tail(h->d);
+}
+
+int mamg_apply_launches(const mamg_handle* h, int64_t* launches) {
+  GUARD_BEGIN
+  if (!h || !launches) { set_error("mamg_apply_launches: null handle or result"); return MAMG_ERR_ARG; }
+  std::string err;
+  const int rc = mamg::dev_apply_launches(h->d, launches, &err);
+  if (rc) set_error(err);
+  return rc;
+  GUARD_END
+}
+
 int mamg_level_storage(const mamg_handle* h, int level) {
   if (!h || level < 0 || level >= mamg::dev_num_levels(h->d)) {
     mamg::set_error("mamg_level_storage: bad handle or level");

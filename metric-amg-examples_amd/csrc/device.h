@@ -43,6 +43,11 @@ int dev_level_format(const DeviceHandle* h, int level);
 // fp32 storage of the operators the cycle streams (mamg.h mamg_set_cycle_storage)
 int dev_set_cycle_storage(DeviceHandle* h, int storage, std::string* err);
 int dev_level_storage(const DeviceHandle* h, int level);
+// nonlinear AMLI: the inner CG's steps inside the coarse tail (mamg.h
+// mamg_set_kcycle_tail), the state, and what one apply issues (mamg_apply_launches)
+int dev_set_kcycle_tail(DeviceHandle* h, int on, std::string* err);
+int dev_kcycle_tail(const DeviceHandle* h);
+int dev_apply_launches(const DeviceHandle* h, int64_t* launches, std::string* err);
 // the coarse tail's plan (mamg_test.h mamg_tail_info)
 int dev_tail_info(const DeviceHandle* h, int index, int64_t* info, int cap);
 // the row-pattern dictionary's decision for level 0's A (mamg_test.h mamg_rowdict_info)

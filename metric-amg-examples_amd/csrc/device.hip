@@ -1713,6 +1713,148 @@ __device__ __forceinline__ void tail_res(const TOp& o, const TOpnd& V, const TRe
   V.out.st(2 * node + 1, o1);
 }
 
+// ---- nonlinear AMLI inside the tail (T_KDOT / T_KORTH / T_KUPD): the launch
+// path's kdot_kernel / korth_kernel / kupd_kernel as one workgroup.  The
+// workgroup's two halves stand for two of the launch path's 256-thread blocks
+// at a time (as T_DOT2 does): the same elements per thread, the same shuffle
+// tree, the same (w0 + w1) + (w2 + w3) over a block's four waves, the partials
+// in the same DLevel::kpart slots and summed by the consumer in the same
+// order -- so a scalar has the launch path's bits, and a replay its own.
+// One vector operand of a K op from its level's table (KTable; uniform)
+__device__ __forceinline__ TVec tail_kvec(const TOp& o, int slot, char* lds) {
+  const uint64_t v = gload(reinterpret_cast<const uint64_t*>(o.ptr) + slot);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+  return tvec(reinterpret_cast<const double*>(((uint64_t)hi << 32) | lo), lds);
+}
+// kblock_sum of each half of the workgroup: the 256 threads' values summed,
+// the same on every thread of the half (kred: one row per wave; free again on return)
+template <int NV>
+__device__ __forceinline__ void tail_half_sum(double (&v)[NV], double (*kred)[MAMG_NL_AMLI_MAX - 1]) {
+  static_assert(NV <= MAMG_NL_AMLI_MAX - 1, "kred's row");
+  const int t = (int)threadIdx.x, w0 = (t >> 8) * 4;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+  }
+  if ((t & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < NV; ++k) kred[t >> 6][k] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < NV; ++k) v[k] = (kred[w0][k] + kred[w0 + 1][k]) + (kred[w0 + 2][k] + kred[w0 + 3][k]);
+  __syncthreads();
+}
+// the launch path's grid: min(SCALE_BLOCKS, ceil(n / 256)) blocks (launch_kstep)
+__device__ __forceinline__ int tail_kblocks(int64_t n) {
+  const int64_t b = (n + 255) / 256;
+  return (int)(b < SCALE_BLOCKS ? b : SCALE_BLOCKS);
+}
+
+// A K op resolves an operand where it uses it (tail_kvec in the loop bodies)
+// and walks the earlier directions in a run-time loop, one dot or one
+// direction at a time: a step names up to twelve vectors, and holding them all
+// as TVecs costs more scalar registers than the kernel has next to the
+// register-resident rows (it spilled).
+
+// kdot_kernel<J>: part[KP_DOT + i * SCALE_BLOCKS + block] = the block's share of <z, q_i>, i < J = o.r0
+__device__ __forceinline__ void tail_kdot(const TOp& o, char* lds, double (*kred)[MAMG_NL_AMLI_MAX - 1]) {
+  const int J = (int)o.r0, t = (int)threadIdx.x, tt = t & 255, nbl = tail_kblocks(o.n);
+  for (int i = 0; i < J; ++i) {
+    for (int vb0 = 0; vb0 < nbl; vb0 += TAIL_THREADS / 256) {
+      const int vb = vb0 + (t >> 8);
+      double s[1] = {0.0};
+      if (vb < nbl) {
+        const TVec z = tail_kvec(o, KT_Z, lds), q = tail_kvec(o, KT_Q + i, lds);
+        for (int64_t k = (int64_t)vb * 256 + tt; k < o.n; k += (int64_t)nbl * 256) s[0] += z.ld(k) * q.ld(k);
+      }
+      tail_half_sum<1>(s, kred);
+      if (tt == 0 && vb < nbl) tail_kvec(o, KT_PART, lds).st(KP_DOT + i * SCALE_BLOCKS + vb, s[0]);
+    }
+  }
+}
+
+__device__ __forceinline__ double tail_ksel(int i, double b0, double b1, double b2) {
+  return i == 0 ? b0 : i == 1 ? b1 : b2;
+}
+
+// korth_kernel<J>: the beta's from T_KDOT's partials and the stored d_i (a
+// dead direction's beta is 0, never 0 / 0); J > 0: p_J, q_J written; J = 0:
+// p_0 = z, q_0 = w are in place; both: the blocks' shares of <p_J, q_J>, <p_J, r>
+__device__ __forceinline__ void tail_korth(const TOp& o, char* lds, double (*kred)[MAMG_NL_AMLI_MAX - 1]) {
+  static_assert(MAMG_NL_AMLI_MAX - 1 == 3, "tail_ksel holds three beta's");
+  const int J = (int)o.r0, t = (int)threadIdx.x, tt = t & 255, nbl = tail_kblocks(o.n);
+  double b0 = 0.0, b1 = 0.0, b2 = 0.0;
+  for (int i = 0; i < J; ++i) {
+    const TVec part = tail_kvec(o, KT_PART, lds);
+    double s[1] = {0.0};
+    for (int b = tt; b < nbl; b += 256) s[0] += part.ld(KP_DOT + i * SCALE_BLOCKS + b);
+    tail_half_sum<1>(s, kred);
+    const double d = part.ld(KP_D + i);
+    const double be = d > 0.0 ? s[0] / d : 0.0;
+    if (i == 0) b0 = be;
+    else if (i == 1) b1 = be;
+    else b2 = be;
+  }
+  for (int vb0 = 0; vb0 < nbl; vb0 += TAIL_THREADS / 256) {
+    const int vb = vb0 + (t >> 8);
+    double a[2] = {0.0, 0.0};
+    if (vb < nbl) {
+      for (int64_t k = (int64_t)vb * 256 + tt; k < o.n; k += (int64_t)nbl * 256) {
+        double pk, qk;
+        if (J > 0) {
+          pk = tail_kvec(o, KT_Z, lds).ld(k);
+          for (int i = 0; i < J; ++i) pk -= tail_ksel(i, b0, b1, b2) * tail_kvec(o, KT_P + i, lds).ld(k);
+          tail_kvec(o, KT_P + J, lds).st(k, pk);
+          qk = tail_kvec(o, KT_W, lds).ld(k);
+          for (int i = 0; i < J; ++i) qk -= tail_ksel(i, b0, b1, b2) * tail_kvec(o, KT_Q + i, lds).ld(k);
+          tail_kvec(o, KT_Q + J, lds).st(k, qk);
+        } else {
+          pk = tail_kvec(o, KT_P, lds).ld(k);
+          qk = tail_kvec(o, KT_Q, lds).ld(k);
+        }
+        a[0] += pk * qk;
+        a[1] += pk * tail_kvec(o, J == 0 ? KT_B : KT_R, lds).ld(k);
+      }
+    }
+    tail_half_sum<2>(a, kred);
+    if (tt == 0 && vb < nbl) {
+      const TVec part = tail_kvec(o, KT_PART, lds);
+      part.st(KP_PQ + 2 * vb, a[0]);
+      part.st(KP_PQ + 2 * vb + 1, a[1]);
+    }
+  }
+}
+
+// kupd_kernel: d_j (stored by one thread) and alpha from T_KORTH's partials
+// (alpha = 0 for a dead direction); e = alpha p_j (step 0) or e += alpha p_j;
+// r_out = r_in - alpha q_j unless this is the last step
+__device__ __forceinline__ void tail_kupd(const TOp& o, char* lds, double (*kred)[MAMG_NL_AMLI_MAX - 1]) {
+  const int j = (int)o.r0, t = (int)threadIdx.x, tt = t & 255, nbl = tail_kblocks(o.n);
+  const bool first = j == 0, last = j == (int)o.r1 - 1;
+  double a[2] = {0.0, 0.0};
+  {
+    const TVec part = tail_kvec(o, KT_PART, lds);
+    for (int b = tt; b < nbl; b += 256) {
+      a[0] += part.ld(KP_PQ + 2 * b);
+      a[1] += part.ld(KP_PQ + 2 * b + 1);
+    }
+  }
+  tail_half_sum<2>(a, kred);
+  const double d = a[0];
+  const double alpha = d > 0.0 ? a[1] / d : 0.0;
+  if (t == 0) tail_kvec(o, KT_PART, lds).st(KP_D + j, d);
+  for (int64_t k = t; k < o.n; k += TAIL_THREADS) {
+    const TVec e = tail_kvec(o, KT_X, lds);
+    const double pk = tail_kvec(o, KT_P + j, lds).ld(k);
+    e.st(k, first ? alpha * pk : e.ld(k) + alpha * pk);
+    if (!last)
+      tail_kvec(o, KT_R, lds).st(k, tail_kvec(o, first ? KT_B : KT_R, lds).ld(k) - alpha * tail_kvec(o, KT_Q + j, lds).ld(k));
+  }
+}
+
 // STAMP: thread 0 records the 100 MHz wall clock at the start and after every
 // op's barrier (stamps[0..nops]; MAMG_TAIL_PROFILE diagnosis, dev_time_apply)
 // dynamic LDS: the tail levels' work vectors (tail_lds_plan)
@@ -1721,10 +1863,14 @@ extern __shared__ double tail_lds[];
 // XL: every SpMV / GS op of the program gathers from an LDS-resident x
 // (tail_lds_plan placed all of them), so the gathers are ds_reads
 // RES: the program has register-resident rows (T_RLOAD, res ops)
-template <bool STAMP, bool XL, bool RES>
+// KOPS: the program has nonlinear AMLI steps (T_KDOT / T_KORTH / T_KUPD).  A
+// flag of their own: compiled into every variant they cost the W-cycle's
+// programs, which hold none, 2.7 % per apply
+template <bool STAMP, bool XL, bool RES, bool KOPS = false>
 __global__ __launch_bounds__(TAIL_THREADS) void tail_kernel(const TOp* __restrict__ gprog, int nops, int prog_lds,
                                                            uint64_t* __restrict__ stamps) {
   __shared__ double red[TAIL_THREADS / 64][2];
+  __shared__ double kred[TAIL_THREADS / 64][MAMG_NL_AMLI_MAX - 1];
   TRes R;
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
   char* lds = reinterpret_cast<char*>(tail_lds);
@@ -1884,6 +2030,15 @@ __global__ __launch_bounds__(TAIL_THREADS) void tail_kernel(const TOp* __restric
         for (int64_t i = t; i < o.n; i += TAIL_THREADS) V.out.st(i, al * V.out.ld(i));
         break;
       }
+      case T_KDOT:
+        if (KOPS) tail_kdot(o, lds, kred);
+        break;
+      case T_KORTH:
+        if (KOPS) tail_korth(o, lds, kred);
+        break;
+      case T_KUPD:
+        if (KOPS) tail_kupd(o, lds, kred);
+        break;
       default: break;
     }
     __syncthreads();   // the next op reads what this one wrote (workgroup-scope visibility)
@@ -1891,10 +2046,14 @@ __global__ __launch_bounds__(TAIL_THREADS) void tail_kernel(const TOp* __restric
   }
 }
 
-// one tail_kernel launch; flags bit 0: XL, bit 1: RES
+// one tail_kernel launch; flags bit 0: XL, bit 1: RES, bit 2: KOPS
 template <bool STAMP>
 void tail_launch(int flags, const TOp* prog, int n, int prog_lds, size_t lds, uint64_t* stamps, hipStream_t s) {
-  switch (flags & 3) {
+  switch (flags & 7) {
+    case 4: tail_kernel<STAMP, false, false, true><<<1, TAIL_THREADS, lds, s>>>(prog, n, prog_lds, stamps); break;
+    case 5: tail_kernel<STAMP, true, false, true><<<1, TAIL_THREADS, lds, s>>>(prog, n, prog_lds, stamps); break;
+    case 6: tail_kernel<STAMP, false, true, true><<<1, TAIL_THREADS, lds, s>>>(prog, n, prog_lds, stamps); break;
+    case 7: tail_kernel<STAMP, true, true, true><<<1, TAIL_THREADS, lds, s>>>(prog, n, prog_lds, stamps); break;
     case 0: tail_kernel<STAMP, false, false><<<1, TAIL_THREADS, lds, s>>>(prog, n, prog_lds, stamps); break;
     case 1: tail_kernel<STAMP, true, false><<<1, TAIL_THREADS, lds, s>>>(prog, n, prog_lds, stamps); break;
     case 2: tail_kernel<STAMP, false, true><<<1, TAIL_THREADS, lds, s>>>(prog, n, prog_lds, stamps); break;
@@ -5526,8 +5685,10 @@ void scale_ops(const DeviceHandle* h, int lc, std::vector<Op>* ops) {
 // (stride nv0); all other vectors are node-interleaved (stride 0).
 // one op of the launch path as a coarse-tail op (tail_kernel; at most vl_cap
 // lanes per row, MAMG_TAIL_VL); false if the tail cannot express it (level-0
-// formats and strides, patches, CSR)
-bool to_tail(const Op& o, int vl_cap, TOp* t) {
+// formats and strides, patches, CSR; the nonlinear AMLI steps unless the
+// handle has opted in: ktail, mamg_set_kcycle_tail).  A K op's operands are
+// its level's (o.lev): the caller gives it the level's table (TOp::nb)
+bool to_tail(const Op& o, int vl_cap, bool ktail, TOp* t) {
   *t = TOp();
   switch (o.kind) {
     case OP_BSR:
@@ -5550,6 +5711,13 @@ bool to_tail(const Op& o, int vl_cap, TOp* t) {
     case OP_ZERO: t->kind = T_ZERO; t->n = o.n; t->out = o.out; return true;
     case OP_DOT2: t->kind = T_DOT2; t->n = o.n; t->b = o.b; t->x = o.x; t->y = o.y; t->part = o.part; return true;
     case OP_CSCALE: t->kind = T_CSCALE; t->n = o.n; t->part = o.part; t->out = o.out; return true;
+    case OP_KDOT:
+    case OP_KORTH:
+    case OP_KUPD:
+      if (!ktail || !o.lev) return false;
+      t->kind = o.kind == OP_KDOT ? T_KDOT : o.kind == OP_KORTH ? T_KORTH : T_KUPD;
+      t->n = o.n; t->r0 = o.r0; t->r1 = o.r1;
+      return true;
     default: return false;
   }
 }
@@ -5565,7 +5733,38 @@ constexpr int64_t TAIL_LDS_MAX = 160 * 1024 - 1024;   // gfx950: 160 KB per work
 // to tagged LDS offsets, vectors read before written are copied in first and
 // written ones copied out last.  Returns the dynamic LDS bytes, or 0 (program
 // unchanged: global vectors) when the plan exceeds the LDS.
-int64_t tail_lds_plan(const DeviceHandle* h, int l, std::vector<TOp>* prog, int64_t reserve = 0) {
+// the vectors step j of m reads, then the ones it writes, as slots of its level's table (kstep_ops, tail_k*)
+void kop_touches(const TOp& o, std::vector<int>* rd, std::vector<int>* wr) {
+  const int j = (int)o.r0;
+  const bool first = j == 0, last = j == (int)o.r1 - 1;
+  rd->clear();
+  wr->clear();
+  if (o.kind == T_KDOT) {
+    rd->push_back(KT_Z);
+    for (int i = 0; i < j; ++i) rd->push_back(KT_Q + i);
+    wr->push_back(KT_PART);
+  } else if (o.kind == T_KORTH) {
+    if (j > 0) rd->push_back(KT_PART);
+    for (int i = 0; i < j; ++i) { rd->push_back(KT_P + i); rd->push_back(KT_Q + i); }
+    if (j > 0) { rd->push_back(KT_Z); rd->push_back(KT_W); }
+    else { rd->push_back(KT_P); rd->push_back(KT_Q); }
+    rd->push_back(first ? KT_B : KT_R);
+    if (j > 0) { wr->push_back(KT_P + j); wr->push_back(KT_Q + j); }
+    wr->push_back(KT_PART);
+  } else {   // T_KUPD
+    rd->push_back(KT_PART);
+    rd->push_back(KT_P + j);
+    if (!first) rd->push_back(KT_X);
+    if (!last) { rd->push_back(KT_Q + j); rd->push_back(first ? KT_B : KT_R); }
+    wr->push_back(KT_PART);
+    wr->push_back(KT_X);
+    if (!last) wr->push_back(KT_R);
+  }
+}
+inline bool is_kop(const TOp& o) { return o.kind == T_KDOT || o.kind == T_KORTH || o.kind == T_KUPD; }
+
+int64_t tail_lds_plan(const DeviceHandle* h, int l, std::vector<TOp>* prog, std::vector<KTable>* ktabs,
+                      int64_t reserve = 0) {
   if (!h->sw.tail_lds) return 0;
   struct Vec {
     double* base;
@@ -5582,6 +5781,11 @@ int64_t tail_lds_plan(const DeviceHandle* h, int l, std::vector<TOp>* prog, int6
     for (double* v : {L.kr, L.kz, L.kw, L.kp[0], L.kq[0]})
       if (v) vecs.push_back({v, L.n});
     if (L.part2) vecs.push_back({L.part2, 2 * SCALE_BLOCKS});
+    // the Krylov levels inside the program: the later directions and the steps' scalars and partials
+    for (int i = 1; i < MAMG_NL_AMLI_MAX; ++i)
+      for (double* v : {L.kp[i], L.kq[i]})
+        if (v) vecs.push_back({v, L.n});
+    if (L.kpart) vecs.push_back({L.kpart, KP_SIZE});
   }
   auto find = [&](const double* p) -> Vec* {
     for (auto& v : vecs)
@@ -5597,7 +5801,15 @@ int64_t tail_lds_plan(const DeviceHandle* h, int l, std::vector<TOp>* prog, int6
     v->seen = true;
     if (write) v->out = true;
   };
+  std::vector<int> krd, kwr;
   for (const TOp& o : *prog) {   // reads of an op before its writes
+    if (is_kop(o)) {
+      const KTable& T = (*ktabs)[(size_t)o.nb];
+      kop_touches(o, &krd, &kwr);
+      for (int sl : krd) touch(T.v[sl], false);
+      for (int sl : kwr) touch(T.v[sl], true);
+      continue;
+    }
     const bool rmw = o.kind == T_GS || o.kind == T_AXPY || o.kind == T_CSCALE;
     for (const double* r : {o.x, o.y, o.b}) if (r) touch(r, false);
     if (o.part) touch(o.part, o.kind != T_CSCALE ? true : false);
@@ -5624,9 +5836,13 @@ int64_t tail_lds_plan(const DeviceHandle* h, int l, std::vector<TOp>* prog, int6
   if (!(attr_devices >> dev & 1)) {
     const void* fns[] = {(const void*)tail_kernel<false, false, false>, (const void*)tail_kernel<false, true, false>,
                          (const void*)tail_kernel<false, false, true>, (const void*)tail_kernel<false, true, true>,
+                         (const void*)tail_kernel<false, false, false, true>, (const void*)tail_kernel<false, true, false, true>,
+                         (const void*)tail_kernel<false, false, true, true>, (const void*)tail_kernel<false, true, true, true>,
 #if MAMG_DIAG   // the stamped (profiling) variants
                          (const void*)tail_kernel<true, false, false>, (const void*)tail_kernel<true, true, false>,
                          (const void*)tail_kernel<true, false, true>, (const void*)tail_kernel<true, true, true>,
+                         (const void*)tail_kernel<true, false, false, true>, (const void*)tail_kernel<true, true, false, true>,
+                         (const void*)tail_kernel<true, false, true, true>, (const void*)tail_kernel<true, true, true, true>,
 #endif
     };
     bool ok = true;
@@ -5646,6 +5862,8 @@ int64_t tail_lds_plan(const DeviceHandle* h, int l, std::vector<TOp>* prog, int6
   for (TOp& o : *prog) {
     o.x = tag(o.x); o.y = tag(o.y); o.b = tag(o.b); o.out = tag(o.out); o.part = tag(o.part);
   }
+  for (KTable& T : *ktabs)
+    for (const double*& v : T.v) v = tag(v);
   std::vector<TOp> full;
   for (const auto& v : vecs)
     if (v.lds && v.in) {
@@ -5815,10 +6033,25 @@ bool tail_ops(const DeviceHandle* h, int l, const double* b, double* xout, std::
     std::vector<Op> sub;
     cycle_ops_bsr(h, l, b, 0, xout, 0, &sub, false);
     std::vector<TOp> prog(sub.size());
+    std::vector<KTable> ktabs;            // one per Krylov level inside the program
+    std::vector<const DLevel*> klev;
     double bytes = 0.0;
     for (size_t k = 0; k < sub.size(); ++k) {
-      if (!to_tail(sub[k], h->sw.tail_vl, &prog[k])) { h->tail_refused = true; return false; }
+      if (!to_tail(sub[k], h->sw.tail_vl, h->kcycle_tail, &prog[k])) { h->tail_refused = true; return false; }
       bytes += sub[k].bytes;
+      if (!is_kop(prog[k])) continue;
+      const DLevel* C = sub[k].lev;
+      size_t at = 0;
+      while (at < klev.size() && klev[at] != C) ++at;
+      if (at == klev.size()) {
+        KTable T = {};
+        T.v[KT_R] = C->kr; T.v[KT_Z] = C->kz; T.v[KT_W] = C->kw; T.v[KT_B] = C->b; T.v[KT_X] = C->x;
+        T.v[KT_PART] = C->kpart;
+        for (int i = 0; i < MAMG_NL_AMLI_MAX; ++i) { T.v[KT_P + i] = C->kp[i]; T.v[KT_Q + i] = C->kq[i]; }
+        klev.push_back(C);
+        ktabs.push_back(T);
+      }
+      prog[k].nb = (int64_t)at;
     }
     h->tail_refused = false;
     bool replanned = false;   // a residency plan was made, did not fit the LDS and was discarded
@@ -5826,11 +6059,12 @@ bool tail_ops(const DeviceHandle* h, int l, const double* b, double* xout, std::
     int64_t nov = 0;
     int rrows = 0;
     const std::vector<TOp> plain = prog;
+    const std::vector<KTable> kplain = ktabs;
     bool res = tail_res_plan(h, l, &prog, &img, &nov, &rrows);
     int64_t region = 0;   // the resident rows' LDS region, kept free of vectors
     for (const TOp& t : prog)
       if (t.kind == T_RLOAD) region = t.n;
-    int64_t lds = tail_lds_plan(h, l, &prog, region + 16);
+    int64_t lds = tail_lds_plan(h, l, &prog, &ktabs, region + 16);
     // the program itself into the LDS after the vectors when it fits
     // (TAIL_LDS_MAX); the dynamic LDS then covers both
     int prog_lds = -1;
@@ -5866,7 +6100,8 @@ bool tail_ops(const DeviceHandle* h, int l, const double* b, double* xout, std::
         rrows = 0;
         img.clear();
         prog = plain;
-        lds = tail_lds_plan(h, l, &prog);
+        ktabs = kplain;
+        lds = tail_lds_plan(h, l, &prog, &ktabs);
         prog_lds = -1;
         pbytes = (int64_t)(prog.size() * sizeof(TOp));
         if (lds > 0 && h->sw.tail_prog_lds) {
@@ -5887,10 +6122,17 @@ bool tail_ops(const DeviceHandle* h, int l, const double* b, double* xout, std::
     std::vector<int64_t> info(TAIL_INFO_HEAD, 0);
     info[TI_OPS] = (int64_t)prog.size(); info[TI_LDS] = lds; info[TI_XL] = xl ? 1 : 0; info[TI_RES] = res ? 1 : 0;
     info[TI_PROG_LDS] = prog_lds; info[TI_ROWS] = rrows; info[TI_NOV] = nov; info[TI_REPLANNED] = replanned ? 1 : 0;
+    std::vector<int> krd, kwr;
     for (const TOp& t : prog) {
       if (t.kind != T_RLOAD && t.kind != T_COPY)   // a copy in or out is one of each by construction
         for (const double* v : {t.x, t.y, t.b, (const double*)t.out, (const double*)t.part})
           if (v) ++info[((uintptr_t)v & 1) ? TI_VEC_LDS : TI_VEC_GLOBAL];
+      if (is_kop(t)) {   // its operands are its table's
+        ++info[TI_OPS_K];
+        kop_touches(t, &krd, &kwr);
+        for (const std::vector<int>* sl : {&krd, &kwr})
+          for (int q : *sl) ++info[((uintptr_t)ktabs[(size_t)t.nb].v[q] & 1) ? TI_VEC_LDS : TI_VEC_GLOBAL];
+      }
       if (t.kind == T_BSR || t.kind == T_GS) {
         ++info[t.res ? TI_OPS_RES : TI_OPS_BSR];
         if (!t.res) info[TI_MAX_VL] = std::max<int64_t>(info[TI_MAX_VL], t.vl);
@@ -5901,29 +6143,38 @@ bool tail_ops(const DeviceHandle* h, int l, const double* b, double* xout, std::
         info.push_back(((uintptr_t)t.w & 1) ? 1 : 0);
       }
     }
+    // one allocation: the ops, the K ops' tables, the resident rows' image
     void* d = nullptr;
-    const int64_t ioff = (pbytes + 15) / 16 * 16;
+    const int64_t koff = (pbytes + 15) / 16 * 16;
+    const size_t kbytes = ktabs.size() * sizeof(KTable);
+    const int64_t ioff = (koff + (int64_t)kbytes + 15) / 16 * 16;
     const size_t tbytes = img.size();
     if (raw_malloc(&d, (size_t)ioff + tbytes, "long") != hipSuccess) { (void)hipGetLastError(); return false; }
     char* dimg = static_cast<char*>(d) + ioff;
+    for (TOp& t : prog)
+      if (is_kop(t)) {
+        t.ptr = reinterpret_cast<const int64_t*>(static_cast<char*>(d) + koff + (size_t)t.nb * sizeof(KTable));
+        t.nb = 0;
+      }
     auto fix = [&](auto*& f) {
       if (f) f = reinterpret_cast<std::remove_reference_t<decltype(f)>>(dimg + ((uintptr_t)f - 1));
     };
     for (TOp& t : prog)
       if (t.kind == T_RLOAD) { fix(t.val); fix(t.col); fix(t.ridx); fix(t.b); }
     if (hipMemcpy(d, prog.data(), prog.size() * sizeof(TOp), hipMemcpyHostToDevice) != hipSuccess ||
+        (kbytes && hipMemcpy(static_cast<char*>(d) + koff, ktabs.data(), kbytes, hipMemcpyHostToDevice) != hipSuccess) ||
         (tbytes && hipMemcpy(dimg, img.data(), tbytes, hipMemcpyHostToDevice) != hipSuccess)) {
       (void)hipGetLastError();
       (void)raw_free(d);
       return false;
     }
-    h->tails.push_back({b, xout, (TOp*)d, (int)prog.size(), bytes, lds, xl, prog_lds, res, std::move(info)});
+    h->tails.push_back({b, xout, (TOp*)d, (int)prog.size(), bytes, lds, xl, prog_lds, res, !ktabs.empty(), std::move(info)});
     tp = &h->tails.back();
   }
   Op o;
   o.kind = OP_TAIL; o.cls = C_COARSE; o.prog = tp->prog; o.n = tp->n; o.bytes = tp->bytes;
   o.r0 = tp->lds;   // dynamic LDS bytes (0: the program reads global vectors)
-  o.r1 = (tp->xl ? 1 : 0) | (tp->res ? 2 : 0);
+  o.r1 = (tp->xl ? 1 : 0) | (tp->res ? 2 : 0) | (tp->kops ? 4 : 0);
   o.tail_pl = tp->prog_lds;
   ops->push_back(o);
   return true;
@@ -6473,7 +6724,7 @@ void launch(const Op& o, hipStream_t s) {
     case OP_KUPD:
       if (o.n) launch_kstep(o, s);
       break;
-    case OP_TAIL:   // r1: bit 0 = every gathered x in LDS, bit 1 = register-resident rows
+    case OP_TAIL:   // r1: bit 0 = every gathered x in LDS, bit 1 = register-resident rows, bit 2 = K ops
       if (o.n) tail_launch<false>((int)o.r1, o.prog, (int)o.n, o.tail_pl, (size_t)o.r0, nullptr, s);
       break;
     case OP_CSCALE:
@@ -7460,6 +7711,50 @@ int dev_set_cycle_storage(DeviceHandle* h, int storage, std::string* err) {
   return MAMG_OK;
 }
 
+// The K ops of the Krylov levels below the tail level join the tail programs
+// (on) or stay launches (off, the state after setup).  Everything planned or
+// captured with the other state is dropped: the next apply plans again.
+int dev_set_kcycle_tail(DeviceHandle* h, int on, std::string* err) {
+  std::lock_guard<std::recursive_mutex> lock(capture_mutex());
+  if (h->p.cycle_type != MAMG_NL_AMLI_CYCLE) {
+    *err = "kcycle tail: the handle's cycle is not the nonlinear AMLI cycle (MAMG_NL_AMLI_CYCLE)";
+    return MAMG_ERR_UNSUPPORTED;
+  }
+  if (!h->bsr) {
+    *err = "kcycle tail: the coarse tail needs the BSR2 layout (this handle holds the CSR layout)";
+    return MAMG_ERR_UNSUPPORTED;
+  }
+  if (h->tail_level == 0 || h->kcycle_tail == (on != 0)) {   // no tail to plan, or nothing to change
+    h->kcycle_tail = on != 0;
+    return MAMG_OK;
+  }
+  HIPCHK(hipSetDevice(h->device));
+  if (h->last) HIPCHK(hipEventSynchronize(h->last));
+  if (h->cap) HIPCHK(hipStreamSynchronize(h->cap));
+  h->graphs.clear();
+  release_all(&h->pcgs);
+  for (auto& t : h->tails) (void)raw_free(t.prog);
+  h->tails.clear();
+  h->tail_refused = false;
+  h->kcycle_tail = on != 0;
+  return MAMG_OK;
+}
+
+int dev_kcycle_tail(const DeviceHandle* h) { return h->kcycle_tail ? 1 : 0; }
+
+// what launch() issues for one apply: every op of the list with work, a tail
+// program as one (building the list plans the tail programs, launches nothing)
+int dev_apply_launches(const DeviceHandle* h, int64_t* launches, std::string* err) {
+  std::lock_guard<std::recursive_mutex> lock(capture_mutex());
+  HIPCHK(hipSetDevice(h->device));
+  std::vector<Op> ops;
+  apply_ops(h, h->hr, h->hz, &ops);
+  int64_t c = 0;
+  for (const Op& o : ops) c += o.n > 0 ? 1 : 0;
+  *launches = c;
+  return MAMG_OK;
+}
+
 mamg_params dev_params(const DeviceHandle* h) { return h->p; }
 const Switches& dev_switches(const DeviceHandle* h) { return h->sw; }
 void dev_kregion(const DeviceHandle* h, std::vector<double>* ms, int* kept) {
@@ -7696,7 +7991,7 @@ int dev_time_apply(DeviceHandle* h, const double* d_r, double* d_z, int reps, in
       HIPCHK(raw_malloc((void**)&dst, 2 * (tp.n + 1) * sizeof(uint64_t), "tmp"));
       HIPCHK(hipMemcpy(prog.data(), tp.prog, tp.n * sizeof(TOp), hipMemcpyDeviceToHost));
       for (int rep = 0; rep < 2; ++rep)
-        tail_launch<true>((tp.xl ? 1 : 0) | (tp.res ? 2 : 0), tp.prog, tp.n, tp.prog_lds, (size_t)tp.lds, dst, s);
+        tail_launch<true>((tp.xl ? 1 : 0) | (tp.res ? 2 : 0) | (tp.kops ? 4 : 0), tp.prog, tp.n, tp.prog_lds, (size_t)tp.lds, dst, s);
       HIPCHK(hipStreamSynchronize(s));
       HIPCHK(hipMemcpy(st.data(), dst, 2 * (tp.n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
       (void)raw_free(dst);

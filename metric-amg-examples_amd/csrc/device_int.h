@@ -163,7 +163,18 @@ struct DPcgCtx {
 
 // the coarse tail's ops (tail_kernel, kernels.hip; planned in cycle.hip)
 enum TKind { T_BSR = 0, T_BD = 1, T_GEMV = 2, T_AXPY = 3, T_ZERO = 4, T_GS = 5, T_DOT2 = 6, T_CSCALE = 7,
-             T_COPY = 8, T_RLOAD = 9 };
+             T_COPY = 8, T_RLOAD = 9,
+             // nonlinear AMLI (mamg_set_kcycle_tail): kdot_kernel / korth_kernel / kupd_kernel as one workgroup,
+             // step r0 of r1 on a Krylov level whose vectors the op names through a side table (ptr, KT_*)
+             T_KDOT = 10, T_KORTH = 11, T_KUPD = 12 };
+// A K op's vector operands: one table of tagged addresses per (program, Krylov
+// level), in the program's allocation behind the ops; TOp::ptr points at it
+// (TOp::nb: its index while the program is planned).  A step names up to
+// twelve vectors, more than a TOp has vector fields, and a wider descriptor
+// would cost every op of every program.
+enum KTab { KT_R = 0, KT_Z = 1, KT_W = 2, KT_B = 3, KT_X = 4, KT_PART = 5, KT_P = 6, KT_Q = KT_P + MAMG_NL_AMLI_MAX,
+            KT_SIZE = KT_Q + MAMG_NL_AMLI_MAX };
+struct KTable { const double* v[KT_SIZE]; };
 // LDS residency (tail_lds_plan): the program itself and every work vector of
 // the tail levels live in the workgroup's LDS for the whole launch; a vector
 // field of a TOp then holds (byte offset in the dynamic LDS) | 1 instead of a
@@ -583,10 +594,12 @@ struct DeviceHandle : HandleMem, HandleOrder {
   int kregion_best = -1;
   struct TailProg {
     const double* b; double* x; TOp* prog; int n; double bytes; int64_t lds; bool xl; int prog_lds; bool res;
+    bool kops;                     // it holds nonlinear AMLI steps (tail_kernel KOPS)
     std::vector<int64_t> info;     // what the planner decided (dev_tail_info; mamg_test.h mamg_tail_info)
   };
   mutable std::vector<TailProg> tails;
   mutable bool tail_refused = false;   // the last plan attempt met an op the tail cannot express (to_tail)
+  bool kcycle_tail = false;            // nonlinear AMLI: the K ops run inside the tail (dev_set_kcycle_tail)
   double* hr = nullptr;            // host-apply staging (device)
   double* hz = nullptr;
   double *cr = nullptr, *cz = nullptr, *cd = nullptr, *cq = nullptr;  // PCG
@@ -734,7 +747,7 @@ Op gs_op(const LV& L, int c, double* x, const double* b, int64_t bs, int cls) {
 }
 // mamg_tail_info's values (include/mamg_test.h): the header, then (n, matrix in LDS) per T_GEMV
 enum TailInfo { TI_PROGS = 0, TI_LEVEL, TI_OPS, TI_LDS, TI_XL, TI_RES, TI_PROG_LDS, TI_ROWS, TI_NOV, TI_VEC_LDS,
-                TI_VEC_GLOBAL, TI_REFUSED, TI_GEMVS, TI_OPS_RES, TI_OPS_BSR, TI_MAX_VL, TI_REPLANNED, TAIL_INFO_HEAD };
+                TI_VEC_GLOBAL, TI_REFUSED, TI_GEMVS, TI_OPS_RES, TI_OPS_BSR, TI_MAX_VL, TI_REPLANNED, TI_OPS_K, TAIL_INFO_HEAD };
 
 // stored values of an operator's main array (rehome_bsr's count)
 inline int64_t value_count(const DBsr& M) {

@@ -113,12 +113,21 @@ def _storage_kw(cycle_storage, precond):
     return dict(cycle_storage=cycle_storage)
 
 
-def _solve(A, W, b, precond, idofs, tol, maxiter, monolithic_params=None, cycle_storage='f64'):
+def _ktail_kw(kcycle_tail, precond):
+    """-kcycle_tail as the factories' keyword; nothing for the default 0"""
+    if not kcycle_tail:
+        return {}
+    if precond in ('diag', 'metric_hazmath'):
+        raise ValueError('-kcycle_tail 1 needs an AMG preconditioner built by a factory, not -precond %s' % precond)
+    return dict(kcycle_tail=True)
+
+
+def _solve(A, W, b, precond, idofs, tol, maxiter, monolithic_params=None, cycle_storage='f64', kcycle_tail=0):
     """setup + CG, timed together (the reference's timeKSP)."""
     then = time.time()
     Asp = A.scipy() if hasattr(A, 'scipy') else A
     nf = 2 if W[0] == W[1] else 1
-    skw = _storage_kw(cycle_storage, precond)
+    skw = dict(_storage_kw(cycle_storage, precond), **_ktail_kw(kcycle_tail, precond))
     if precond in ('metric_mono', 'hazmath_HEM'):   # hazmath_HEM: the same factory, parameters_metric
         BB = get_hazmath_metric_precond_mono(A, W, parameters=monolithic_params, interface_dofs=idofs,
                                              num_functions=nf, **skw)
@@ -166,6 +175,8 @@ def bidomain_parser(dim):
                     help="AMG parameters: the reference driver's dicts, or the GPU profile")
     ap.add_argument('-cycle_storage', type=str, default='f64', choices=('f64', 'f32'),
                     help='storage of the operators the cycle streams (f32: MetricAMG.set_cycle_storage)')
+    ap.add_argument('-kcycle_tail', type=int, default=0, choices=(0, 1),
+                    help="1: the K-cycle's inner CG steps inside the coarse tail (MetricAMG.set_kcycle_tail)")
     return ap
 
 
@@ -189,11 +200,12 @@ def bidomain(argv, dim):
             b = problems.seeded_rhs(s.N)
         if args.precond == 'metric_hazmath':     # the whole solve in the library (src/bidomain_2d.py:181-186)
             _storage_kw(args.cycle_storage, args.precond)   # f32: refused, the solve builds its own handle
+            _ktail_kw(args.kcycle_tail, args.precond)
             niters, xb, dt = solve_haznics(s, b, s.W, interface_dofs=s.idofs, parameters=prm)
             x, cond, r = np.concatenate(xb), -1, 0
         else:
             x, niters, cond, dt, r, _ = _solve(s, s.W, b, args.precond, s.idofs, 1e-8, 500, prm,
-                                               cycle_storage=args.cycle_storage)
+                                               cycle_storage=args.cycle_storage, kcycle_tail=args.kcycle_tail)
         h = np.sqrt(dim) / n            # dolfin hmin: the simplices' longest edge
         row = (s.N, niters, cond, dt, r, h)
         rows.append(row)
@@ -228,6 +240,8 @@ def emi(argv, dim):
                     help="AMG parameters: the reference's default dict (src/utils.py:60-82), or the GPU profile")
     ap.add_argument('-cycle_storage', type=str, default='f64', choices=('f64', 'f32'),
                     help='storage of the operators the cycle streams (f32: MetricAMG.set_cycle_storage)')
+    ap.add_argument('-kcycle_tail', type=int, default=0, choices=(0, 1),
+                    help="1: the K-cycle's inner CG steps inside the coarse tail (MetricAMG.set_kcycle_tail)")
     args, _ = ap.parse_known_args(argv)
     prm = _profile_params(args.profile, args.precond)
     rdir = os.path.join(args.results, 'emi_%dd' % dim)
@@ -246,10 +260,12 @@ def emi(argv, dim):
             b = [problems.seeded_rhs(s.W[0], 1234), problems.seeded_rhs(s.W[1], 4321)]
         then = time.time()
         if args.precond == 'diag':
+            _ktail_kw(args.kcycle_tail, args.precond)
             BB = get_block_diag_precond(s.blocks, s.W)
         else:
             BB = get_hazmath_metric_precond(s.blocks, s.W, parameters=prm, interface_dofs=s.idofs,
-                                            num_functions=2, **_storage_kw(args.cycle_storage, args.precond))
+                                            num_functions=2, **_storage_kw(args.cycle_storage, args.precond),
+                                            **_ktail_kw(args.kcycle_tail, args.precond))
         solver = ConjGrad(s, precond=BB, tolerance=1e-10, maxiter=500)   # src/emi_3d.py:143
         x = solver * b
         dt = time.time() - then
