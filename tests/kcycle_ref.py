@@ -18,7 +18,8 @@ A_c e = b_c, preconditioned by the cycle of that level,
 with a fixed step count (no residual-based exit) and a dropped direction where
 d_j is not positive.  ``visit`` = 'V' or 'W' runs the oracle's own visits
 through the same restatement (tests/test_kcycle_ref.py: bitwise the oracle's
-cycle, so only the visit differs).
+cycle, so only the visit differs).  ``trace`` records every step's d_j and
+``guards=False`` removes the dropped-direction rule (tests/kcycle_edge_cases.py).
 
 ``KPointGS`` / ``KPointRings`` do the same on the CSR-layout restatements
 (tests/pointgs_ref.py, tests/pointrings_ref.py).  A helper, not a test.
@@ -29,13 +30,31 @@ import mamg_oracle as mo
 
 
 class KCycle:
-    def __init__(self, h, degree=2, visit='K'):
+    def __init__(self, h, degree=2, visit='K', trace=None, guards=True):
+        """trace: a list that every step of a K visit appends
+        (level, step, d, ||p|| ||q||) to (None: nothing is recorded; the
+        arithmetic is the same either way).  guards=False: the cycle a library
+        without the dropped-direction rule would run -- alpha, the beta's and
+        the coarse scaling always divide (tests/test_kcycle_edges_ref.py)."""
         assert visit in ('K', 'V', 'W') and degree >= 1
         self.h = h
         self.levels = h.levels
         self.params = h.params
         self.degree = degree
         self.visit_type = visit
+        self.trace = trace
+        self.guards = guards
+
+    def guarded(self, guard):
+        return self.guards is True or (bool(self.guards) and guard in self.guards)
+
+    def ratio(self, num, den, dead, guard):
+        """num / den where den is positive, else ``dead``; without the guard
+        the quotient whatever den is (0 / 0 = NaN, as the hardware gives)"""
+        if self.guarded(guard):
+            return num / den if den > 0 else dead
+        with np.errstate(all='ignore'):
+            return float(np.float64(num) / np.float64(den))
 
     # ------------------------------------------------------------ the visit
     def visit(self, c, bc):
@@ -52,13 +71,15 @@ class KCycle:
         for j in range(self.degree):
             z = self.cycle(c, r)
             w = C.A @ z
-            betas = [float(np.dot(z, qs[i])) / ds[i] if ds[i] > 0 else 0.0 for i in range(j)]
+            betas = [self.ratio(float(np.dot(z, qs[i])), ds[i], 0.0, 'beta') for i in range(j)]
             p, q = z, w
             for i in range(j):
                 p = p - betas[i] * ps[i]
                 q = q - betas[i] * qs[i]
             d = float(np.dot(p, q))
-            alpha = float(np.dot(p, r)) / d if d > 0 else 0.0
+            alpha = self.ratio(float(np.dot(p, r)), d, 0.0, 'alpha')
+            if self.trace is not None:
+                self.trace.append((c, j, d, float(np.linalg.norm(p) * np.linalg.norm(q))))
             e = e + alpha * p
             if j < self.degree - 1:
                 r = r - alpha * q
@@ -130,8 +151,10 @@ class KCycle:
         bc = lev.R @ r
         C = self.levels[l + 1]
         e = self.visit(l + 1, bc)
-        if p.coarse_scaling:
+        if p.coarse_scaling and self.guarded('scale'):
             e = mo.coarse_scale(C.A, bc, e)
+        elif p.coarse_scaling:
+            e = self.ratio(float(np.dot(bc, e)), float(np.dot(e, C.A @ e)), 1.0, 'scale') * e
         x = x + lev.P @ e
         return self.post(l, x, b)
 
