@@ -551,8 +551,12 @@ enum { MAMG_FMT_SELL = 1, MAMG_FMT_SYM = 2, MAMG_FMT_POST_FUSED = 4, MAMG_FMT_PO
                                    on the CSR layout level 0 reports MAMG_FMT_RINGS | MAMG_FMT_GS) */
        MAMG_FMT_R_BANDS = 1024,    /* restriction rows walked plane band by plane band per XCD */
        MAMG_FMT_K_COL16 = 2048,    /* K's columns as 16-bit offsets from a per-slice base */
-       MAMG_FMT_ROWDICT = 4096 };  /* A stored as one row-type code per node row plus a table of the
+       MAMG_FMT_ROWDICT = 4096,    /* A stored as one row-type code per node row plus a table of the
                                       distinct rows (its rows repeat; neither SELL nor HALF is then set) */
+       MAMG_FMT_POST_MF = 8192 };  /* matrix-free prolongation (level 0 on the dictionary): P e =
+                                      (I - w D_B^-1 A)(T e) through the aggregate index and A's dictionary,
+                                      no stored K or P; neither POST_FUSED nor POST_K is then set, and
+                                      every post sweep is the plain block-Jacobi pass */
 int mamg_level_format(const mamg_handle* h, int level);
 /* The parameters the handle runs (as mamg_hier_params). */
 int mamg_handle_params(const mamg_handle* h, mamg_params* out);

@@ -91,6 +91,28 @@ int mamg_test_set_rowdict(int64_t min_rows, int max_types, int hash_bits);
  *   3 longest row in blocks      4 bytes of the type table */
 int mamg_rowdict_info(const mamg_handle* h, int64_t* info, int cap);
 
+/* The matrix-free level-0 post step, for the process:
+ * mode 0 never takes it, any other mode takes it where eligible (negative:
+ * the default, which is on); min_rows is the node rows of level 0 from which
+ * it is taken (negative: the default, 1 << 22).  A threshold of its own, not
+ * the dictionary's: lowering only the dictionary's keeps the stored K.  Read
+ * by every setup at its entry, with the switches. */
+int mamg_test_set_post_mf(int mode, int64_t min_rows);
+
+/* What the layout builder decided for the handle's level-0 post step.  Writes
+ * up to cap values, returns how many there are (3), MAMG_ERR_ARG for a bad
+ * argument.  info[]:
+ *   0 taken (1 / 0)
+ *   1 refusal reason: 0 none, 1 switched off (mode 0), 2 fewer rows than the
+ *     threshold, 3 level-0 A is not a row dictionary, 4 the prolongator is not
+ *     (I - w D_B^-1 A) T (AMG_type is not SA with sa_block_diag, or the setup
+ *     handed no aggregates over), 5 the smoother is not Jacobi-like (GS / SGS,
+ *     patches, rings), 6 post_fusion is off or there is no post sweep, 7 not
+ *     tried (CSR layout or a single level), 8 a row type without a positive
+ *     diagonal block
+ *   2 bytes of the per-type table Wp = w D_B^-1 */
+int mamg_post_mf_info(const mamg_handle* h, int64_t* info, int cap);
+
 /* Where the GPU setups run the Vanek-Mandel-Brezina aggregation
  * (aggregation_type VMB), for the process.
  *   mode 1, the default: on the device, by worklist rounds that reach the

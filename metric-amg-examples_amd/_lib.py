@@ -159,6 +159,8 @@ SIGNATURES = {
     'mamg_tail_info': (C.c_int, [VP, C.c_int, P_I64, C.c_int]),
     'mamg_test_set_rowdict': (C.c_int, [C.c_int64, C.c_int, C.c_int]),
     'mamg_rowdict_info': (C.c_int, [VP, P_I64, C.c_int]),
+    'mamg_test_set_post_mf': (C.c_int, [C.c_int, C.c_int64]),
+    'mamg_post_mf_info': (C.c_int, [VP, P_I64, C.c_int]),
     'mamg_test_set_vmb': (C.c_int, [C.c_int, C.c_int64]),
     'mamg_test_vmb_info': (C.c_int, [C.c_int, P_I64, C.c_int]),
     'mamg_apply': (C.c_int, [VP, P_F64, P_F64]),
@@ -212,7 +214,14 @@ def set_rowdict(min_rows=-1, max_types=-1, hash_bits=-1):
     check(lib().mamg_test_set_rowdict(int(min_rows), int(max_types), int(hash_bits)))
 
 
-VMB_INFO_KEYS = ('path', 'rounds', 'evaluations', 'roots', 'nonisolated', 'joiners', 'host_bytes', 'micros')
+def set_post_mf(mode=-1, min_rows=-1):
+    """mamg_test_set_post_mf (include/mamg_test.h): the matrix-free level-0
+    post step for the setups that follow: mode 0 never, otherwise from
+    ``min_rows`` node rows (negative: default)."""
+    check(lib().mamg_test_set_post_mf(int(mode), int(min_rows)))
+
+
+VMB_INFO_KEYS =('path', 'rounds', 'evaluations', 'roots', 'nonisolated', 'joiners', 'host_bytes', 'micros')
 
 
 def set_vmb(mode=1, max_rounds=-1):

@@ -286,7 +286,7 @@ class MetricAMG:
                 'post_k': bool(f & 8), 'post_sell': bool(f & 16), 'half': bool(f & 32),
                 'bands': bool(f & 64), 'patches': bool(f & 128), 'gs': bool(f & 256),
                 'rings': bool(f & 512), 'r_bands': bool(f & 1024), 'k_col16': bool(f & 2048),
-                'rowdict': bool(f & 4096)}
+                'rowdict': bool(f & 4096), 'post_mf': bool(f & 8192)}
 
     def set_cycle_storage(self, storage):
         """'f32': narrow the operators the cycle streams to fp32 storage
@@ -339,6 +339,16 @@ class MetricAMG:
         reasons = (None, 'types', 'length', 'verification', 'threshold', 'not square', 'table', 'not tried')
         return {'taken': bool(v[0]), 'reason': reasons[int(v[1])], 'types': int(v[2]), 'maxlen': int(v[3]),
                 'table_bytes': int(v[4])}
+
+    def post_mf_info(self) -> dict:
+        """What the layout builder decided for level 0's post step
+        (mamg_post_mf_info, a test hook): ``taken``, the refusal ``reason``
+        (None when taken) and the ``table_bytes`` of the per-type w D_B^-1."""
+        v = (C.c_int64 * 4)()
+        _lib.check(min(self._L.mamg_post_mf_info(self._h, v, 4), 0))
+        reasons = (None, 'off', 'threshold', 'no dictionary', 'not SA', 'smoother', 'no fusion', 'not tried',
+                   'diagonal')
+        return {'taken': bool(v[0]), 'reason': reasons[int(v[1])], 'table_bytes': int(v[2])}
 
     def tail_info(self) -> dict:
         """Which plan the coarse tail took (mamg_tail_info, a test hook):
@@ -811,7 +821,7 @@ class DistMetricAMG:
                 'post_k': bool(f & 8), 'post_sell': bool(f & 16), 'half': bool(f & 32),
                 'bands': bool(f & 64), 'patches': bool(f & 128), 'gs': bool(f & 256),
                 'rings': bool(f & 512), 'r_bands': bool(f & 1024), 'k_col16': bool(f & 2048),
-                'rowdict': bool(f & 4096)}
+                'rowdict': bool(f & 4096), 'post_mf': bool(f & 8192)}
 
     def set_cycle_storage(self, storage):
         """'f32': narrow the rank-local operators the cycle streams to fp32

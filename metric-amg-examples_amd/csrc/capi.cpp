@@ -1134,6 +1134,23 @@ int mamg_rowdict_info(const mamg_handle* h, int64_t* info, int cap) {
   GUARD_END
 }
 
+int mamg_test_set_post_mf(int mode, int64_t min_rows) {
+  GUARD_BEGIN
+  mamg::set_post_mf_hook(mode, min_rows);
+  return MAMG_OK;
+  GUARD_END
+}
+
+int mamg_post_mf_info(const mamg_handle* h, int64_t* info, int cap) {
+  GUARD_BEGIN
+  if (!h || cap < 0 || (cap > 0 && !info)) {
+    set_error("mamg_post_mf_info: bad handle or buffer");
+    return MAMG_ERR_ARG;
+  }
+  return mamg::dev_post_mf_info(h->d, info, cap);
+  GUARD_END
+}
+
 int mamg_handle_options(const mamg_handle* h, char* buf, int64_t cap) {
   GUARD_BEGIN
   return write_options(h ? mamg::dev_switches(h->d) : mamg::read_switches(), buf, cap);

@@ -52,6 +52,8 @@ int dev_apply_launches(const DeviceHandle* h, int64_t* launches, std::string* er
 int dev_tail_info(const DeviceHandle* h, int index, int64_t* info, int cap);
 // the row-pattern dictionary's decision for level 0's A (mamg_test.h mamg_rowdict_info)
 int dev_rowdict_info(const DeviceHandle* h, int64_t* info, int cap);
+// the matrix-free level-0 post step's decision (mamg_test.h mamg_post_mf_info)
+int dev_post_mf_info(const DeviceHandle* h, int64_t* info, int cap);
 mamg_params dev_params(const DeviceHandle* h);
 // the switches the handle was built with (dev_upload's sw, dev_from_ghier's G->sw)
 const Switches& dev_switches(const DeviceHandle* h);

@@ -894,8 +894,12 @@ __global__ __launch_bounds__(256) void rowdict2_kernel(
   if (EPI == EPI_RESID || EPI == EPI_BJAC)
     bb = MAMG_HSELL_NT >= 2 ? double2{ld_once(b + (bs ? node : 2 * node)), ld_once(b + (bs ? bs + node : 2 * node + 1))}
                             : double2{vget(b, bs, node, 0), vget(b, bs, node, 1)};
-  if (EPI == EPI_YADD || EPI == EPI_BJAC) yy = reinterpret_cast<const double2*>(y)[node];
+  if (EPI == EPI_YADD || EPI == EPI_BJAC || EPI == EPI_PSM) yy = reinterpret_cast<const double2*>(y)[node];
   if (EPI == EPI_BJAC) w = W[node];
+  if (EPI == EPI_PSM) {   // the row type's w D_B^-1: four scalars on the wave-uniform path
+    if (!mixed) w = W[first];
+    else w = W[code];
+  }
   double o0, o1;
   if (EPI == EPI_Y) {
     o0 = s0; o1 = s1;
@@ -903,6 +907,10 @@ __global__ __launch_bounds__(256) void rowdict2_kernel(
     o0 = yy.x + s0; o1 = yy.y + s1;
   } else if (EPI == EPI_RESID) {
     o0 = bb.x - s0; o1 = bb.y - s1;
+  } else if (EPI == EPI_PSM) {   // u = x1 + y - Wp (A y), y = T e the gathered vector itself
+    const double2 ty = xget<XFM>(x, xs, (int32_t)node);
+    o0 = (yy.x + ty.x) - (w.x * s0 + w.y * s1);
+    o1 = (yy.y + ty.y) - (w.z * s0 + w.w * s1);
   } else {  // EPI_BJAC
     const double r0 = bb.x - s0, r1 = bb.y - s1;
     o0 = yy.x + (w.x * r0 + w.y * r1);
@@ -915,6 +923,20 @@ __global__ __launch_bounds__(256) void rowdict2_kernel(
     vset(out, os, node, 0, o0);
     vset(out, os, node, 1, o1);
   }
+}
+
+// y = T e on level 0 (the matrix-free post step): T is
+// the tentative prolongator, one 1 per aggregated node, so y(I) = e(agg[I]),
+// both fields, and 0 for an isolated node.  e is the coarse level's
+// node-interleaved correction (L2-resident), agg streams once.
+__global__ __launch_bounds__(256) void tgather_kernel(int64_t nv, const int32_t* __restrict__ agg,
+                                                      const double* __restrict__ e, double* __restrict__ y) {
+  const int64_t I = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (I >= nv) return;
+  const int32_t a = ld_once(agg + I);
+  double2 v = {0.0, 0.0};
+  if (a >= 0) v = reinterpret_cast<const double2*>(e)[a];
+  reinterpret_cast<double2*>(y)[I] = v;
 }
 
 // fused prolongation + first post sweep on a SELL-64 [P | AP] (see
@@ -5202,6 +5224,94 @@ int build_rings(DeviceHandle* h, TmpPool* T, const TBsr& B, const LevelSrc& S, D
   return MAMG_OK;
 }
 
+// ---- matrix-free level-0 post step (DLevel::post_mf) --
+// Wp[t] = w D_t^-1 per row type of the dictionary: D_t is the type's diagonal
+// block (the entry with column - row == 0), inverted by the setup's 2x2
+// Gauss-Jordan without pivoting (gsetup.hip node_inverse_kernel).  *bad is
+// set for a type without a diagonal entry or with a non-positive pivot.
+__global__ __launch_bounds__(256) void post_mf_table_kernel(int nt, int rw, int sym, int64_t nbs,
+                                                            const int32_t* __restrict__ rlen,
+                                                            const int32_t* __restrict__ rdelta,
+                                                            const double* __restrict__ rval, double w,
+                                                            dv4* __restrict__ Wp, int* bad) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= nt) return;
+  int k = -1;
+  for (int j = 0; j < rlen[t]; ++j)
+    if (rdelta[t * rw + j] == 0) { k = t * rw + j; break; }
+  if (k < 0) { atomicOr(bad, 1); Wp[t] = dv4{0.0, 0.0, 0.0, 0.0}; return; }
+  const dv4 a = sym ? dv4{rval[2 * k], rval[2 * nbs + k], rval[2 * nbs + k], rval[2 * k + 1]}
+                    : reinterpret_cast<const dv4*>(rval)[k];
+  double M[2][4] = {{a.x, a.y, 1.0, 0.0}, {a.z, a.w, 0.0, 1.0}};
+  bool ok = true;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const double p = M[q][q];
+    if (!(p > 0.0)) ok = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) M[q][j] = M[q][j] / p;
+    const int i = 1 - q;
+    const double fi = M[i][q];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) M[i][j] = M[i][j] - fi * M[q][j];
+  }
+  if (!ok) atomicOr(bad, 1);
+  Wp[t] = dv4{w * M[0][2], w * M[0][3], w * M[1][2], w * M[1][3]};
+}
+
+__global__ __launch_bounds__(256) void agg_i32_kernel(int64_t nv, const int64_t* __restrict__ agg,
+                                                      int32_t* __restrict__ out) {
+  const int64_t I = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (I < nv) out[I] = agg[I] < 0 ? -1 : (int32_t)agg[I];
+}
+
+// Decides whether level 0 prolongates through the aggregate index and A's
+// dictionary instead of a stored K (or P): P = (I - w D_B^-1 A) T holds for
+// the nodal SA prolongator only, and the post sweeps must be the block-Jacobi
+// passes.  MAMG_OK with D->post_mf set, or with it false and the reason in
+// D->mfinfo[PM_REASON] (the caller then builds K / P as without the attempt).
+int try_post_mf(DeviceHandle* h, TmpPool* T, const LevelSrc& S, int64_t nvc, DLevel* D, std::string* err) {
+  const mamg_params& p = h->p;
+  int64_t* info = D->mfinfo;
+  info[PM_TAKEN] = 0;
+  info[PM_TABLE_BYTES] = 0;
+  auto refuse = [&](int why) { info[PM_REASON] = why; return MAMG_OK; };
+  const DBsr& A = D->Ab;
+  if (h->sw.post_mf_mode == 0) return refuse(PMR_OFF);
+  if (!p.post_fusion || p.postsmooth_iter < 1) return refuse(PMR_NO_FUSION);
+  if (gs_smoother(p) || patch_schwarz(p) || rings_schwarz(p)) return refuse(PMR_SMOOTHER);
+  if (p.AMG_type != MAMG_SA_AMG || !p.sa_block_diag || !S.agg || !(S.w_sa > 0.0)) return refuse(PMR_NOT_SA);
+  if (!A.rowdict) return refuse(PMR_NO_DICT);
+  if (A.nr < h->sw.post_mf_min_rows) return refuse(PMR_THRESHOLD);
+  if (nvc > (int64_t)INT32_MAX) return refuse(PMR_NOT_SA);
+  int rc;
+  dv4* wp = nullptr;
+  int* bad = nullptr;
+  if ((rc = T->alloc(&wp, A.rtypes, err))) return rc;
+  if ((rc = T->alloc(&bad, 1, err))) return rc;
+  HIPCHK(dev_memset(bad, 0, sizeof(int)));
+  post_mf_table_kernel<<<nblocks(A.rtypes), 256>>>(A.rtypes, A.rw, A.sym ? 1 : 0, A.nbs, A.rlen, A.rdelta, A.val,
+                                                   S.w_sa, wp, bad);
+  HIPCHK(hipGetLastError());
+  int hb = 1;
+  HIPCHK(hipMemcpy(&hb, bad, sizeof(int), hipMemcpyDeviceToHost));
+  if (hb) {
+    T->release(wp); T->release(bad);
+    return refuse(PMR_DIAG);
+  }
+  if ((rc = dalloc(h, &D->mf_wp, A.rtypes, err))) return rc;
+  if ((rc = dalloc(h, &D->mf_agg, A.nr, err))) return rc;
+  HIPCHK(dev_copy(D->mf_wp, wp, (size_t)A.rtypes * sizeof(dv4)));
+  agg_i32_kernel<<<nblocks(A.nr), 256>>>(A.nr, S.agg, D->mf_agg);
+  HIPCHK(hipGetLastError());
+  T->release(wp); T->release(bad);
+  D->post_mf = true;
+  info[PM_TAKEN] = 1;
+  info[PM_REASON] = PMR_NONE;
+  info[PM_TABLE_BYTES] = 32 * (int64_t)A.rtypes;
+  return MAMG_OK;
+}
+
 int build_bsr_level(DeviceHandle* h, int l, const LevelSrc& S, int64_t nvc, int lanesA, std::string* err) {
   DLevel& D = h->L[l];
   const mamg_params& p = h->p;
@@ -5238,8 +5348,13 @@ int build_bsr_level(DeviceHandle* h, int l, const LevelSrc& S, int64_t nvc, int 
     if ((rc = poly_scaled(h, S.W, 4 * nv, &wk, err))) return rc;
     for (double* q : wk) D.Wk.push_back(reinterpret_cast<dv4*>(q));
   }
-  if (p.post_fusion && p.postsmooth_iter >= 1 && S.AP.n == D.n && !gs_smoother(p) &&
-      !(l == 0 && (patch_schwarz(p) || rings_schwarz(p)))) {
+  if (l == 0 && (rc = try_post_mf(h, &T, S, nvc, &D, err))) return rc;
+  if (D.post_mf) {
+    // level 0 prolongates through agg and A's dictionary: no K, no [P | AP], and
+    // no P either (its only other readers are the GS and unfused paths, which
+    // the eligibility rules out)
+  } else if (p.post_fusion && p.postsmooth_iter >= 1 && S.AP.n == D.n && !gs_smoother(p) &&
+             !(l == 0 && (patch_schwarz(p) || rings_schwarz(p)))) {
     TBsr Pb, Qb, M;
     if ((rc = dev_csr_to_bsr(&T, S.P, nv, nvc, &Pb, err))) return rc;
     if ((rc = dev_csr_to_bsr(&T, S.AP, nv, nvc, &Qb, err))) return rc;
@@ -5319,6 +5434,7 @@ double bsr_bytes(const DBsr& M, int epi) {
     if (epi == EPI_YADD) b += 16.0 * M.nr;
     if (epi == EPI_RESID) b += 16.0 * M.nr;
     if (epi == EPI_BJAC || epi == EPI_KPOST) b += 16.0 * M.nr + 16.0 * M.nr + 32.0 * M.nr;   // y, b, W
+    if (epi == EPI_PSM) b += 16.0 * M.nr + 32.0 * M.rtypes;   // x1 and the per-type table w D_B^-1
     return b;
   }
   double b = M.half ? sym_b * (M.nb - M.nlo) + 4.0 * M.nlo + 4.0 * M.nr + (M.ngs ? 8.0 * (M.nr / SELL_C + 2) : 0.0) +
@@ -6297,7 +6413,17 @@ void cycle_ops_bsr(const DeviceHandle* h, int l, const double* b, int64_t bs, do
     return;
   }
   int s0 = 0;
-  if (L.KPb.nr > 0 && npost >= 1) {   // z = x1 + W r1 + K e (one operator, K built with this W)
+  if (L.post_mf && npost >= 1) {
+    // matrix-free prolongation (level 0 on the dictionary, DESIGN.md section
+    // 4.9): y = T e into L.r (r1 is dead once restricted on this path), then
+    // u = x1 + y - Wp (A y); every post sweep is the plain pass below
+    Op g;
+    g.kind = OP_TGATHER; g.cls = C_L0_P; g.n = nv; g.perm = L.mf_agg; g.x = C.x; g.out = L.r;
+    g.bytes = 4.0 * nv + 16.0 * nv + 8.0 * C.n;
+    ops->push_back(g);
+    ops->push_back(bsr_op(cyc_A(L), EPI_PSM, C_L0_P, tagA, L.r, 0, X, nullptr, 0, L.mf_wp, X2, 0));
+    std::swap(X, X2);
+  } else if (L.KPb.nr > 0 && npost >= 1) {   // z = x1 + W r1 + K e (one operator, K built with this W)
     const bool last = npost == 1;
     ops->push_back(bsr_op(L.KPb, EPI_KPOST, clsS, tagA, C.x, 0, X, L.r, 0, step_wd(L, 0, false),
                           last ? xout : X2, last ? os : 0));
@@ -6562,9 +6688,10 @@ void launch_rowdict(const Op& o, hipStream_t s) {
   with_bools([&](auto xfm, auto sym) {
     constexpr bool SYM = decltype(sym)::value;
     const size_t lds = MAMG_ROWDICT_LDS ? (size_t)M.nbs * (4 + (SYM ? 3 : 4) * sizeof(VT)) : 0;
-    with_block_epi(o.epi, [&](auto epi) {
+    // the dictionary holds A, never K: EPI_PSM (node-interleaved vectors only) in EPI_KPOST's place
+    with_epi<EPI_BJAC, EPI_Y, EPI_YADD, EPI_RESID, EPI_PSM>(o.epi, [&](auto epi) {
       constexpr int E = decltype(epi)::value;
-      if constexpr (E != EPI_KPOST)
+      if constexpr (E != EPI_PSM || !decltype(xfm)::value)
         rowdict2_kernel<E, decltype(xfm)::value, SYM, ROWDICT_U, TAG, VT><<<g, 256, lds, s>>>(
             r0, r1, M.rcode, M.rlen, M.rdelta, reinterpret_cast<const VT*>(M.val), M.nbs, M.rw, o.x, o.xs, o.y, o.b,
             o.bs, o.W, o.out, o.os, 1, (r0 == 0 && r1 == M.nr && (int64_t)g == M.nsched) ? M.sched : nullptr);
@@ -6677,6 +6804,9 @@ void launch(const Op& o, hipStream_t s) {
       break;
     case OP_BD:
       if (o.n) bd2_kernel<false><<<nblocks(o.n), 256, 0, s>>>(o.n, o.W, o.b, o.bs, nullptr, o.out, 0);
+      break;
+    case OP_TGATHER:
+      if (o.n) tgather_kernel<<<nblocks(o.n), 256, 0, s>>>(o.n, o.perm, o.x, o.out);
       break;
     case OP_SCALE:
       if (o.n) scale_kernel<<<nblocks(o.n), 256, 0, s>>>(o.n, o.w, o.x, o.out);
@@ -7022,18 +7152,23 @@ void select_k_region(DeviceHandle* h) {
 
 void rehome_operators(DeviceHandle* h) {
   if (!h->sw.rehome) return;   // the operators stay where the layout builder put them (tests)
-  if (!h->bsr || h->L.size() < 2 || h->L[0].KPb.nr < h->sw.sell_min_rows || !h->L[0].KPb.sell) return;
+  if (!h->bsr || h->L.size() < 2) return;
   DLevel& L = h->L[0];
+  // a matrix-free level 0 has no K to place; the rest is re-homed as with one
+  const bool mf = L.post_mf && L.Ab.nr >= h->sw.sell_min_rows;
+  if (!mf && (L.KPb.nr < h->sw.sell_min_rows || !L.KPb.sell)) return;
   auto lap = [t = std::chrono::steady_clock::now()]() mutable {
     const auto n = std::chrono::steady_clock::now();
     const double ms = std::chrono::duration<double, std::milli>(n - t).count();
     t = n;
     return ms;
   };
-  select_k_region(h);            // the largest stream first, placed by measurement
-  h->layout_ms[LT_KREGION] = lap();
-  if (L.KPb.col16) rehome_array(h, (void**)&L.KPb.col16, (size_t)L.KPb.nbs * sizeof(uint16_t));
-  else rehome_array(h, (void**)&L.KPb.col, (size_t)L.KPb.nbs * sizeof(int32_t));
+  if (!mf) {
+    select_k_region(h);            // the largest stream first, placed by measurement
+    h->layout_ms[LT_KREGION] = lap();
+    if (L.KPb.col16) rehome_array(h, (void**)&L.KPb.col16, (size_t)L.KPb.nbs * sizeof(uint16_t));
+    else rehome_array(h, (void**)&L.KPb.col, (size_t)L.KPb.nbs * sizeof(int32_t));
+  }
   if (L.Ab.half) rehome_bsr(h, L.Ab);
   if (!L.Rb.sell && !L.Rb.sym)
     rehome_array(h, (void**)&L.Rb.val, (size_t)L.Rb.nb * 4 * sizeof(double));
@@ -7220,6 +7355,13 @@ int dev_upload(const Hierarchy& H, const CsrView& A0, const mamg_params& p, cons
         HIPCHK(hipMemcpy(dW, blk.data(), 4 * nv * sizeof(double), hipMemcpyHostToDevice));
         S.W = dW;
         S.seeds = &H.seeds;
+        if (l == 0 && h->sw.post_mf_mode != 0 && (int64_t)hl.agg.size() == nv) {   // try_post_mf's inputs
+          int64_t* dagg = nullptr;
+          if ((rc = T.alloc(&dagg, nv, err))) return rc;
+          HIPCHK(hipMemcpy(dagg, hl.agg.data(), nv * sizeof(int64_t), hipMemcpyHostToDevice));
+          S.agg = dagg;
+          S.w_sa = hl.w_sa;
+        }
         if ((rc = build_bsr_level(h.get(), l, S, nvc, lanesA, err))) return rc;
       }
     } else if (D.coarsest) {     // CSR layout, or a single-level hierarchy
@@ -7423,6 +7565,7 @@ int dev_from_ghier(GHier* G, const DevMat& A0, const mamg_params& p, DeviceHandl
       S.A = l == 0 ? A0 : g.A;
       S.P = g.P; S.R = g.R; S.AP = g.AP; S.W = g.W; S.Ainv = g.Ainv;
       S.seeds = &G->seeds;
+      if (l == 0) { S.agg = g.agg; S.w_sa = g.w_sa; }
       const int64_t nvc = D.coarsest ? 0 : G->levels[l + 1].n / 2;
       if ((rc = build_bsr_level(h.get(), l, S, nvc, l == 0 ? p.spmv_lanes : 0, err))) return rc;
     }
@@ -7513,7 +7656,7 @@ int dev_layout(const DeviceHandle* h) { return h->bsr ? 1 : 0; }
 int dev_level_format(const DeviceHandle* h, int level) {
   const DLevel& L = h->L[level];
   return (L.Ab.sell ? MAMG_FMT_SELL : 0) | (L.Ab.sym ? MAMG_FMT_SYM : 0) | (L.Ab.half ? MAMG_FMT_HALF : 0) |
-         (L.Ab.rowdict ? MAMG_FMT_ROWDICT : 0) |
+         (L.Ab.rowdict ? MAMG_FMT_ROWDICT : 0) | (L.post_mf ? MAMG_FMT_POST_MF : 0) |
          (L.PAb.nr > 0 || L.KPb.nr > 0 ? MAMG_FMT_POST_FUSED : 0) | (L.KPb.nr > 0 ? MAMG_FMT_POST_K : 0) |
          (L.KPb.sell ? MAMG_FMT_POST_SELL : 0) | (L.Ab.nsched > 0 || L.Ab.nsched_r > 0 ? MAMG_FMT_BANDS : 0) |
          (L.pcs.size() > 1 ? MAMG_FMT_PATCHES : 0) | (L.gcs.size() > 1 ? MAMG_FMT_GS : 0) |
@@ -7631,6 +7774,12 @@ int dev_rowdict_info(const DeviceHandle* h, int64_t* info, int cap) {
   return RD_INFO_N;
 }
 
+int dev_post_mf_info(const DeviceHandle* h, int64_t* info, int cap) {
+  const DLevel& L = h->L[0];
+  for (int i = 0; i < cap && i < PM_INFO_N; ++i) info[i] = L.mfinfo[i];
+  return PM_INFO_N;
+}
+
 int dev_tail_info(const DeviceHandle* h, int index, int64_t* info, int cap) {
   std::lock_guard<std::recursive_mutex> lock(capture_mutex());
   const int np = (int)h->tails.size();
@@ -7704,6 +7853,9 @@ int dev_set_cycle_storage(DeviceHandle* h, int storage, std::string* err) {
   int rc = narrow_values(jobs, &h->allocs, drop_cached, [&](void* old) { release_owned(h, old); }, err);
   if (rc) return rc;
   for (size_t k = 0; k < jobs.size(); ++k) h->L[lev_bit[k].first].storage |= lev_bit[k].second;
+  // a matrix-free level 0 holds no K / P to narrow (its post step reads A's
+  // fp32 table, Wp stays fp64): the bit is reported as requested
+  if (h->L[0].post_mf && (h->L[0].storage & 1)) h->L[0].storage |= 2;
   std::vector<Op> ops;
   apply_ops(h, h->hr, h->hz, &ops);
   h->apply_bytes = 0.0;

@@ -41,7 +41,11 @@ namespace mamg {
 // x' = x + W_I (b_I - s_I) (2x2 block, BSR only) |
 // z = x1_I + W_I r1_I + s_I with s = K e, K = P - W (A P) (BSR only: the
 // prolongation fused with the first post sweep through one operator)
-enum Epi { EPI_Y = 0, EPI_YADD = 1, EPI_RESID = 2, EPI_JACOBI = 3, EPI_BJAC = 4, EPI_KPOST = 5, EPI_YBD = 6 };
+enum Epi { EPI_Y = 0, EPI_YADD = 1, EPI_RESID = 2, EPI_JACOBI = 3, EPI_BJAC = 4, EPI_KPOST = 5, EPI_YBD = 6,
+           EPI_PSM = 7 };
+// EPI_PSM (rowdict2_kernel only): out = y_I + x_I - Wp[type of row I] s_I, the
+// smoothed prolongation u = x1 + (I - w D_B^-1 A)(T e) with x = T e, y = x1
+// and W the per-type table w D_B^-1
 // EPI_YBD (bsr2_kernel only): out = A x as EPI_Y, and the next level's first
 // sweep from x = 0 in the same pass, y <- W out (the restriction b_c = R r
 // writing x1_c = W_c b_c: one launch and one b_c read fewer per coarse level;
@@ -296,6 +300,11 @@ enum RowdictInfo { RD_TAKEN = 0, RD_REASON, RD_TYPES, RD_MAXLEN, RD_TABLE_BYTES,
 enum RowdictReason { RDR_NONE = 0, RDR_TYPES = 1, RDR_LENGTH = 2, RDR_VERIFY = 3, RDR_THRESHOLD = 4, RDR_NOT_SQUARE = 5,
                      RDR_TABLE = 6, RDR_NOT_TRIED = 7 };
 
+// mamg_post_mf_info's values and refusal reasons (include/mamg_test.h)
+enum PostMfInfo { PM_TAKEN = 0, PM_REASON, PM_TABLE_BYTES, PM_INFO_N };
+enum PostMfReason { PMR_NONE = 0, PMR_OFF = 1, PMR_THRESHOLD = 2, PMR_NO_DICT = 3, PMR_NOT_SA = 4, PMR_SMOOTHER = 5,
+                    PMR_NO_FUSION = 6, PMR_NOT_TRIED = 7, PMR_DIAG = 8 };
+
 struct DLevel {
   int64_t n = 0;           // dofs
   bool coarsest = false;
@@ -309,6 +318,14 @@ struct DLevel {
   // other narrowed levels Ab's values are replaced in place.
   DBsr Ac;
   int storage = 0;         // mamg_level_storage bits: 1 A, 2 K / P, 4 R stored fp32
+  // matrix-free post step of level 0 on the row dictionary (post_mf == true,
+  // DESIGN.md section 4.9): P e = (I - w D_B^-1 A)(T e) without a stored K or
+  // P.  mf_agg: the aggregate of each node as int32 (-1 isolated: a zero row
+  // of T); mf_wp: w D_B^-1 per row type of Ab's dictionary (fp64 always).
+  bool post_mf = false;
+  int32_t* mf_agg = nullptr;
+  dv4* mf_wp = nullptr;
+  int64_t mfinfo[3] = {0, 7, 0};   // mamg_post_mf_info, PM_* (not tried until the builder ran)
   dv4* Wd = nullptr;       // BSR2 layout: 2x2 smoother block per node
   double* winv = nullptr;
   // SMOOTHER_POLY: the step smoothers w_k W, k = 1..m (BSR2: Wk; CSR: WBk
@@ -395,7 +412,8 @@ enum OpKind { OP_CSR = 0, OP_SCALE = 1, OP_GEMV = 2, OP_AXPY = 3, OP_BSR = 4, OP
               // korth_kernel, kupd_kernel)
               OP_KDOT = 27,    // block partials of <z, q_i>, i < r0
               OP_KORTH = 28,   // beta_i from them; p_j, q_j; block partials of <p_j, q_j>, <p_j, r>
-              OP_KUPD = 29 };  // d_j stored, alpha; e (+)= alpha p_j, r -= alpha q_j
+              OP_KUPD = 29,    // d_j stored, alpha; e (+)= alpha p_j, r -= alpha q_j
+              OP_TGATHER = 30 };   // out(I) = perm[I] < 0 ? 0 : x(perm[I]), n nodes: y = T e (tgather_kernel)
 // kernel classes (kernel_ms / class_bytes slots)
 enum Cls {
   C_L0_RESID = 0,   // dominant: r = b - A0 x (once per apply)
@@ -709,6 +727,10 @@ struct LevelSrc {
   const double* W = nullptr;      // 4 nv node blocks (device)
   const double* Ainv = nullptr;   // coarsest: n x n dof order (device)
   const std::vector<int32_t>* seeds = nullptr;   // level 0, SCHWARZ_RINGS
+  // level 0: the aggregate of each node (device, -1 isolated; nullptr: not
+  // handed over) and w = sa_omega / rho_B of P = (I - w D_B^-1 A) T
+  const int64_t* agg = nullptr;
+  double w_sa = 0.0;
 };
 
 inline bool gs_smoother(const mamg_params& p) {

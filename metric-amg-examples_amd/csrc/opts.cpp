@@ -29,6 +29,8 @@ struct Table {
   std::string names;
   int64_t rd_min_rows = -1;            // set_rowdict_hook (negative: default)
   int rd_max_types = -1, rd_hash_bits = -1;
+  int mf_mode = -1;                    // set_post_mf_hook (negative: default)
+  int64_t mf_min_rows = -1;
   int vmb_mode = 1;                    // set_vmb_hook
   int64_t vmb_max_rounds = -1;
 };
@@ -115,6 +117,8 @@ Switches read_switches() {
     if (t.rd_min_rows >= 0) s.rowdict_min_rows = t.rd_min_rows;
     if (t.rd_max_types >= 0) s.rowdict_max_types = std::max(1, std::min(2048, t.rd_max_types));
     if (t.rd_hash_bits >= 0) s.rowdict_hash_bits = std::max(1, std::min(62, t.rd_hash_bits));
+    if (t.mf_mode >= 0) s.post_mf_mode = t.mf_mode;
+    if (t.mf_min_rows >= 0) s.post_mf_min_rows = t.mf_min_rows;
     s.vmb_mode = t.vmb_mode;
     s.vmb_max_rounds = t.vmb_max_rounds;
   }
@@ -133,6 +137,13 @@ void set_rowdict_hook(int64_t min_rows, int max_types, int hash_bits) {
   t.rd_min_rows = min_rows;
   t.rd_max_types = max_types;
   t.rd_hash_bits = hash_bits;
+}
+
+void set_post_mf_hook(int mode, int64_t min_rows) {
+  Table& t = table();
+  std::lock_guard<std::mutex> g(t.m);
+  t.mf_mode = mode;
+  t.mf_min_rows = min_rows;
 }
 
 void set_vmb_hook(int mode, int64_t max_rounds) {

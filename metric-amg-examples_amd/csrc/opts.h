@@ -66,6 +66,11 @@ constexpr int ROWDICT_MAX_LEN = 32;       // blocks in a row at most
 constexpr int ROWDICT_HASH_BITS = 62;     // bits kept of a row's hash
 constexpr int64_t ROWDICT_MAX_TABLE = 64 << 10;   // bytes of the type table at most
 
+// Matrix-free level-0 prolongation + first post pass through the dictionary
+// (DESIGN.md section 4.9): taken from POST_MF_MIN_ROWS node rows.  A bound of
+// its own, so that a test which lowers only the dictionary's keeps the K path.
+constexpr int64_t POST_MF_MIN_ROWS = ROWDICT_MIN_ROWS;
+
 struct Switches {
 #define X(name, field, type, def) type field = def;
   MAMG_SWITCHES(X)
@@ -79,6 +84,10 @@ struct Switches {
   int64_t rowdict_min_rows = ROWDICT_MIN_ROWS;
   int rowdict_max_types = ROWDICT_MAX_TYPES;
   int rowdict_hash_bits = ROWDICT_HASH_BITS;
+  // the matrix-free level-0 post step (mamg_test.h mamg_test_set_post_mf; a
+  // test hook as the three above): 0 never, else from post_mf_min_rows node rows
+  int post_mf_mode = 1;
+  int64_t post_mf_min_rows = POST_MF_MIN_ROWS;
   // where the GPU setup runs the VMB aggregation (mamg_test.h
   // mamg_test_set_vmb; a test hook as the three above): 1 on the device from
   // VMB_MIN_NODES nodes up and on the host below, 2 on the device whatever the
@@ -91,6 +100,9 @@ struct Switches {
 // process-wide thresholds of the row-pattern dictionary, read by the next
 // read_switches() (a negative value: the default)
 void set_rowdict_hook(int64_t min_rows, int max_types, int hash_bits);
+// process-wide mode (0: never; negative: default) and threshold (negative:
+// default) of the matrix-free level-0 post step, read likewise
+void set_post_mf_hook(int mode, int64_t min_rows);
 // process-wide path and round cap of the GPU setup's VMB aggregation, read
 // likewise
 void set_vmb_hook(int mode, int64_t max_rounds);

@@ -12,7 +12,11 @@ the bytes written (full and half 128-byte lines alike).  So
     bytes = 2 * 1024 * FETCH_SIZE + 1024 * WRITE_SIZE.
 Kernel -> class (per launch, medians over the launches of the largest grid):
   L0_resid        rowdict2 / sell2 / hsell2 / bsr2 with EPI_RESID = 2, TAG 0
-  L0_smooth_spmv  the fused post kernel: msell <.., KPOST, .., TAG 0> / bsr2_post TAG 0
+  L0_smooth_spmv  the fused post kernel: msell <.., KPOST, .., TAG 0> / bsr2_post TAG 0;
+                  on a matrix-free handle (level_format post_mf) rowdict2 with EPI_BJAC = 4
+  L0_prolong      rowdict2 with EPI_PSM = 7 (u = x1 + y - Wp (A y)), matrix-free handles only
+  L0_prolong_gather  tgather_kernel (y = T e), matrix-free handles only; bench.py's L0_prolong
+                  class holds both, so the ratio is given for their sum
   L0_restrict     bsr2 with EPI_Y = 0, TAG 0 (R_0 r_1)
   L0_smoother     bd2_kernel at level 0's grid (the first pre-smoothing W r)
 and per apply (sum over every launch / the number of L0_resid launches):
@@ -41,6 +45,8 @@ def classify(name):
         return 'bd2'
     if re.search(r'\b(tail_kernel|gemv_kernel)\b', name):
         return 'coarse'
+    if re.search(r'\btgather_kernel\b', name):   # y = T e of the matrix-free post step
+        return 'L0_prolong_gather'
     m = re.search(FAMILY, name)
     if not m:
         return None
@@ -65,6 +71,11 @@ def classify(name):
         return 'L0_resid'
     if epi == '5':                      # EPI_KPOST: z = x1 + W r1 + K e
         return 'L0_smooth_spmv'
+    if kind == 'rowdict2_kernel' and xfm == 'false':   # the matrix-free post step
+        if epi == '7':                  # EPI_PSM: u = x1 + y - Wp (A y)
+            return 'L0_prolong'
+        if epi == '4':                  # EPI_BJAC: z = u + W (b - A u), the post sweep of a handle without K
+            return 'L0_smooth_spmv'
     if epi == '0' and kind == 'bsr2_kernel':
         return 'L0_restrict'
     return None
@@ -141,6 +152,8 @@ def main():
         bd = line.get('breakdown') or {}
         for c, b in kernels.items():
             alg = (bd.get(c) or {}).get('GB')
+            if c == 'L0_prolong':           # the class holds the gather pass too
+                b += kernels.get('L0_prolong_gather', 0.0)
             if alg:
                 ratios[c] = round(b / (alg * 1e9), 3)
                 detail[c]['algorithmic_bytes'] = alg * 1e9
